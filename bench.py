@@ -31,6 +31,13 @@ N>1 each step ends with ONE RCCL all-gather of the DECODED per-video results —
 top-256 pair proposals, 10.8 KB per video (`--gather logits` gathers the 524 KB of predicate logits per video
 instead, as round 1 did).
 
+A plain run sets up, warms up, times `--steps` steps and prints the result line (`metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` = milliseconds of one timed step, `roofline` from events inside those steps).
+`--full` adds what takes time of its own behind the timed region: the CPU baseline and, for the default cfg2 run on one
+GPU, the short legs of the other workloads under "secondary".  `--dump-outputs DIR` writes what the last timed step
+handed its caller (per-pair heads, geometry and logits, decoded triplets, pair proposals) as DIR/<name>.npy; the inputs
+depend on the arguments alone, so two builds can be compared output for output.
+
 Printed JSON (rank 0): see the task contract; extras:
   roofline     dominant kernel = the temporal conv of the tracklet projections (fp32 MFMA; Winograd
                F(6,3) by default, --conv direct for the direct taps); achieved = executed FLOP per launch /
@@ -39,7 +46,7 @@ Printed JSON (rank 0): see the task contract; extras:
                (box-to-box variance of `frac` is mostly the clock the chip holds under this kernel).
                cfg5: the backbone's convolutions as a whole (executed conv FLOP of one video / HIP-event time of
                the backbone inside the timed steps) against the dense bf16 MFMA peak.
-  cpu_baseline the oracle on a FIXED bounded sample of the same workload on the cores this process may use
+  cpu_baseline (--full) the oracle on a FIXED bounded sample of the same workload on the cores this process may use
                (cfg2/cfg4: dense fp32 forward of 248 pairs, median of 5; cfg3: bf16 restatement of 96 pairs, one
                run; cfg5: backbone of 8 frames + RoI head of their 64 boxes each + scorer of 8 pairs, one run each,
                scaled to a video).
@@ -85,9 +92,15 @@ def parse(argv=None):
                          "divide: 509 over 8 ranks = 64,64,64,64,64,63,63,63); overrides --videos")
     ap.add_argument("--batches", type=int, default=2,
                     help="different input batches resident in HBM, rotated step by step")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own behind the timed region: the CPU baseline and, for the "
+                         "default cfg2 run on one GPU, the short legs of the other workloads under \"secondary\"")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB: "
+                         "larger outputs as a seeded row sample, the kept rows in DIR/<name>_rows.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="default cfg2 run on one GPU only: skip the short cfg2-direct / cfg4-shard / cfg3 / cfg5 legs that run AFTER the "
+                    help="--full cfg2 run on one GPU only: skip the short cfg2-direct / cfg4-shard / cfg3 / cfg5 legs that run AFTER the "
                          "timed region and are printed under \"secondary\"")
     ap.add_argument("--cpu-runs", type=int, default=5, help="timed runs of the cfg2 CPU baseline (median reported)")
     ap.add_argument("--conv", choices=["winograd6", "direct"], default="winograd6",
@@ -144,6 +157,8 @@ def parse(argv=None):
     steps, warm = DEFAULT_STEPS[args.workload]
     args.steps = steps if args.steps is None else args.steps
     args.warmup = warm if args.warmup is None else args.warmup
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     return args
 
 
@@ -334,6 +349,39 @@ def backbone_traffic(frames, h, w):
         return {"traffic": None}
 
 
+DUMP_BYTES = 48 << 20   # --dump-outputs stays below 64 MB: larger outputs are written as a row sample of this size
+
+
+def write_outputs(path, tensors, torch, np):
+    """--dump-outputs: every tensor as `path`/<name>.npy, floating point as float32 (float64 kept), integers as float64
+    (exact below 2**53).  When they exceed DUMP_BYTES together, every array above 1 MB keeps the same share of its rows
+    (axis 0), drawn by a seed that is the row count itself: arrays over the same pairs keep the same rows, run after run.
+    The kept row indices go to <name>_rows.npy.  Returns {name: shape written}."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        t = t.detach().cpu()
+        wide = not t.is_floating_point() or t.dtype == torch.float64
+        host[name] = np.ascontiguousarray(t.to(torch.float64 if wide else torch.float32).numpy())
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_BYTES:
+        big = sorted(k for k, a in host.items() if a.nbytes > (1 << 20) and a.shape[0] > 1)
+        small = total - sum(host[k].nbytes for k in big)
+        share = (DUMP_BYTES - small) / float(total - small)
+        for k in big:
+            n = host[k].shape[0]
+            rows = np.sort(np.random.default_rng(n).permutation(n)[:max(1, int(n * share))])
+            host[k] = np.ascontiguousarray(host[k][rows])
+            host[k + "_rows"] = rows.astype(np.float64)
+    if sum(a.nbytes for a in host.values()) > (64 << 20):
+        raise RuntimeError("bench.py --dump-outputs: the outputs do not fit in 64 MB even as a row sample")
+    for name, a in host.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in host.items()}
+
+
 class ClockSampler:
     """Shader clock (MHz) of the device while the timed steps run, read from the amdgpu hwmon node
     (`freq1_input`, Hz) by a background thread every few ms.  None when the node is not readable."""
@@ -490,6 +538,9 @@ class StubWorkload:
     def sync(self):
         pass
 
+    def outputs(self):
+        return dict(zip(("scores", "triplets", "pair_tids", "pair_proposals"), self.gather.last))
+
     def report(self, elapsed, clock_mhz):
         return {"metric": f"tracklet-pairs/sec scored (N={self.n_trk}, T={T_FRAMES}, D={D_ROI})", "dtype": "none", "stub": True,
                 "config": {"workload": f"STUB ({self.args.workload} shape): recorded decoded rows instead of the GPU step (CPU "
@@ -521,6 +572,9 @@ class ScoringWorkload:
         self.total_units_per_step = self.total_videos * self.P_vid
         self.via_model = not args.ops_level
         total_steps = args.warmup + args.steps
+        # --dump-outputs: the last step keeps references to what it handed out (no copy inside the timed region)
+        self.dump_step = total_steps - 1 if args.dump_outputs else None
+        self.last = None
 
         # ---- weights (seed 0) and inputs (seed 1 + global video index), random-init / synthetic
         sd = self.sd = tspn.synth.make_weights(0, c=C, a=A_ANCH, k=K_PRED)
@@ -612,8 +666,13 @@ class ScoringWorkload:
             return torch.stack(ts) if v is None else v.view((len(ts),) + tuple(ts[0].shape))
         sc, trip, tid = (batched([d[k] for d in dec]) for k in range(3))
         self.geom = dur_props[0].geom
-        self.gather(sc, trip, tid, batched(list(pair_props)),
-                    logits=torch.stack(rel_logits) if self.args.gather == "logits" else None)
+        idx = batched(list(pair_props))
+        self.gather(sc, trip, tid, idx, logits=torch.stack(rel_logits) if self.args.gather == "logits" else None)
+        if i == self.dump_step:
+            self.last = {"relness": [d.relness for d in dur_props], "duration": [d.duration for d in dur_props],
+                         "geom": [d.geom for d in dur_props] if self.geom is not None else None,
+                         "rel_logits": list(rel_logits), "scores": sc, "triplets": trip, "pair_tids": tid,
+                         "pair_proposals": idx}
 
     # -- ops level: caller-held packed weights, workspace and outputs
     def _init_ops(self, d):
@@ -643,7 +702,7 @@ class ScoringWorkload:
         # two logits buffers: the second stream may still be decoding step i - 1 while step i writes its logits
         self.out_logits2 = [torch.empty((P, K_PRED), dtype=torch.float32, device=dev) for _ in range(2)]
 
-    def _tail(self, lg, cls, boxes):
+    def _tail(self, lg, cls, boxes, i, heads):
         """What only needs the logits (and the boxes): pair geometry, PPN, top-k decode, result gather."""
         tspn = self.tspn
         # the bbox half of the N^2 pair builder: relative geometry [P, 8, T] of every pair (one lane per
@@ -655,15 +714,18 @@ class ScoringWorkload:
         sc, trip, tid = tspn.ops.decode_topk(lg3, self.local_pairs, cls, row_mul=1, topk_per_pair=TOPK_PAIR,
                                              topk_per_seg=TOPK_SEG, check_pairs=False)
         self.gather(sc, trip, tid, idx, logits=lg3 if self.args.gather == "logits" else None)
+        if i == self.dump_step:
+            self.last = {"relness": heads[:, :A_ANCH], "duration": heads[:, A_ANCH:], "geom": self.geom, "rel_logits": lg,
+                         "scores": sc, "triplets": trip, "pair_tids": tid, "pair_proposals": idx}
 
     def _step_ops(self, i):
         tspn, torch = self.tspn, self.torch
         feats, cls, boxes = self.feats_all[i % self.nb], self.cls_all[i % self.nb], self.boxes_all[i % self.nb]
         if self.bf16:
-            _, lg = tspn.ops.forward_fused_bf16(feats, self.pairs, self.B, self.N, self.packed, self.conv_b, self.head_pk,
-                                                self.head_b, self.cls_w, self.cls_b, workspace=self.ws,
-                                                conv_events=self.events[i])
-            return self._tail(lg, cls, boxes)
+            heads, lg = tspn.ops.forward_fused_bf16(feats, self.pairs, self.B, self.N, self.packed, self.conv_b, self.head_pk,
+                                                    self.head_b, self.cls_w, self.cls_b, workspace=self.ws,
+                                                    conv_events=self.events[i])
+            return self._tail(lg, cls, boxes, i, heads)
         lg = self.out_logits2[i % 2]
         main = torch.cuda.current_stream()
         if self.overlap and i >= 2:
@@ -675,10 +737,10 @@ class ScoringWorkload:
                                check_pairs=False, conv_events=self.events[i], canonical_pairs=True,
                                logits_event=self.ev_logits[i] if self.overlap else None)
         if not self.overlap:
-            return self._tail(lg, cls, boxes)
+            return self._tail(lg, cls, boxes, i, self.out_heads)
         with torch.cuda.stream(self.side):
             self.side.wait_event(self.ev_logits[i])
-            self._tail(lg, cls, boxes)
+            self._tail(lg, cls, boxes, i, self.out_heads)
             self.ev_side[i].record(self.side)
 
     def step(self, i):
@@ -686,6 +748,13 @@ class ScoringWorkload:
 
     def sync(self):
         self.torch.cuda.synchronize()
+
+    def outputs(self):
+        """The last timed step's results as its caller holds them: per-pair tensors of all videos back to back
+        (relness [B*P,A,T], duration [B*P,2A,T], geom [B*P,8,T], rel_logits [B*P,K]), per-video decoded rows
+        (scores [B,200], triplets [B,200,3], pair_tids [B,200,2]) and PPN pair proposals [B,256]."""
+        cat = lambda x: x if x is None or isinstance(x, self.torch.Tensor) else self.torch.cat(x)  # noqa: E731
+        return {k: cat(v) for k, v in self.last.items()}
 
     def report(self, elapsed, clock_mhz):
         np, args, bf16 = self.np, self.args, self.bf16
@@ -833,6 +902,8 @@ class Cfg5Workload:
             self.boxes.append(torch.cat([xy, xy + wh], dim=2).contiguous())
             self.cls.append(torch.rand((N, 35), device=dev, generator=gen))
         total = args.warmup + args.steps
+        self.dump_step = total - 1 if args.dump_outputs else None
+        self.last = None
         self.events = [tuple(torch.cuda.Event(enable_timing=True) for _ in range(4)) for _ in range(total)]
         for ev in self.events:
             for e in ev:
@@ -916,7 +987,7 @@ class Cfg5Workload:
         feats = self.head(maps, boxes)                  # [N, T, 2048] bf16
         e2.record()
         plist = tspn.PairList.from_tracklets(feats, boxes, cls)
-        pair_props, _, rel_logits = self.model([plist], None)
+        pair_props, dur_props, rel_logits = self.model([plist], None)
         dec = self.model.decode([plist], rel_logits, topk_per_pair=TOPK_PAIR, topk_per_seg=TOPK_SEG)
         e3.record()
         if self.assoc is not None:
@@ -929,7 +1000,16 @@ class Cfg5Workload:
                 st["beside_ms"].append(ms)
             st["pending"] = st["pool"].submit(st["run"], e3)
         sc, trip, tid = (torch.stack([d[k] for d in dec]) for k in range(3))
-        self.gather(sc, trip, tid, torch.stack(pair_props))
+        idx = torch.stack(pair_props)
+        self.gather(sc, trip, tid, idx)
+        if i == self.dump_step:
+            self.last = {"relness": dur_props[0].relness, "duration": dur_props[0].duration, "rel_logits": rel_logits[0],
+                         "scores": sc, "triplets": trip, "pair_tids": tid, "pair_proposals": idx}
+
+    def outputs(self):
+        """The last timed video's results: relness [P,A,T], duration [P,2A,T], rel_logits [P,K], decoded rows
+        [1,200(,3|2)] and PPN pair proposals [1,256]."""
+        return dict(self.last)
 
     def sync(self):
         self.torch.cuda.synchronize()
@@ -1021,7 +1101,7 @@ def secondary_legs(args, tspn, torch, np, dev):
                        ("cfg3", {"workload": "cfg3", "steps": 5, "warmup": 2}),
                        ("cfg5", {"workload": "cfg5", "steps": 2, "warmup": 1})):
         a = copy.copy(args)
-        a.videos = a.total_videos = None
+        a.videos = a.total_videos = a.dump_outputs = None
         for k, v in over.items():
             setattr(a, k, v)
         t_leg = time.perf_counter()
@@ -1156,6 +1236,11 @@ def main():
         per_rank["backend"] = dist.get_backend()
 
     if rank == 0:
+        if args.dump_outputs:
+            outs = wl.outputs()
+            if gather.gathered is not None:      # N > 1: what every rank holds after the step's all-gather
+                outs.update({"gathered_" + k: v for k, v in gather.gathered.items() if isinstance(v, torch.Tensor)})
+            write_outputs(args.dump_outputs, outs, torch, np)
         rep = wl.report(elapsed, clock_mhz)
         out = {
             "metric": rep["metric"],
@@ -1173,10 +1258,10 @@ def main():
             out["stub"] = True
         if per_rank is not None:
             out["per_rank"] = per_rank
-        if (world == 1 and not use_dist and not stub and not args.no_secondary and args.workload == "cfg2"
+        if (args.full and world == 1 and not use_dist and not stub and not args.no_secondary and args.workload == "cfg2"
                 and args.conv == "winograd6" and not args.ops_level and args.host_inputs == "off"):
             out["secondary"] = secondary_legs(args, tspn, torch, np, dev)
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not stub:
             out["cpu_baseline"] = wl.cpu_baseline()
         sys.stdout.flush()
         os.dup2(real_stdout, 1)

@@ -165,6 +165,24 @@ def test_bench_rank_body_world2_with_stubbed_gpu_step():
         assert json.loads([l for l in r1.stdout.splitlines() if l.startswith("{")][0])["n_gpus"] == 1
 
 
+def test_bench_dump_outputs_through_the_stubbed_rank_body(tmp_path):
+    """`--dump-outputs DIR` writes the last step's results as float32 / float64 .npy files, the same from run to run with
+    the same arguments; with two ranks rank 0 adds the all-gathered rows.  A plain run carries no CPU baseline."""
+    import numpy as np
+    for run in ("a", "b"):
+        out = _run_bench("--stub-gpu", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / run))
+        assert "cpu_baseline" not in out and "secondary" not in out and out["ms_per_step"] > 0
+    a = {p.name: np.load(p) for p in (tmp_path / "a").glob("*.npy")}
+    b = {p.name: np.load(p) for p in (tmp_path / "b").glob("*.npy")}
+    assert set(a) == {"scores.npy", "triplets.npy", "pair_tids.npy", "pair_proposals.npy"} == set(b)
+    assert a["scores.npy"].dtype == np.float32 and a["triplets.npy"].dtype == np.float64
+    assert a["triplets.npy"].shape == (4, 200, 3) and all(np.array_equal(a[k], b[k]) for k in a)
+    _run_bench("--gpus", "2", "--stub-gpu", "--steps", "2", "--warmup", "1", "--videos", "3",
+               "--dump-outputs", str(tmp_path / "w2"))
+    g = np.load(tmp_path / "w2" / "gathered_scores.npy")
+    assert g.shape == (6, 200) and np.array_equal(g[:3], np.load(tmp_path / "w2" / "scores.npy"))
+
+
 def _run_bench(*flags, timeout=600):
     import json
     import subprocess

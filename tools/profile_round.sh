@@ -7,7 +7,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
 cd $ROOT
-python3 bench.py > $OUT/bench_latest.json 2> $OUT/bench_latest.err
+python3 bench.py --full > $OUT/bench_latest.json 2> $OUT/bench_latest.err
 echo "bench done"; cut -c1-300 $OUT/bench_latest.json
 cd /tmp && export TMPDIR=/tmp
 ( cd $ROOT && rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 bench.py --no-cpu-baseline > $OUT/bench_under_rocprof.log 2>&1 )

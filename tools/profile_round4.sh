@@ -6,13 +6,13 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/prof4
 rm -rf $OUT; mkdir -p $OUT
 cd $ROOT
-python3 bench.py > $OUT/bench_latest.json 2> $OUT/bench_latest.err; echo "cfg2 done"; cut -c1-200 $OUT/bench_latest.json
+python3 bench.py --full > $OUT/bench_latest.json 2> $OUT/bench_latest.err; echo "cfg2 done"; cut -c1-200 $OUT/bench_latest.json
 python3 bench.py --ops-level --no-cpu-baseline > $OUT/bench_ops_level.json 2>> $OUT/bench_latest.err
 python3 bench.py --workload cfg4 --no-cpu-baseline > $OUT/bench_cfg4_shard.json 2>> $OUT/bench_latest.err; echo "cfg4 done"
 python3 bench.py --force-collective --no-cpu-baseline > $OUT/bench_force_collective.json 2>> $OUT/bench_latest.err; echo "collective done"
 for m in naive pageable pinned prefetch prefetch-pinned; do python3 bench.py --no-cpu-baseline --host-inputs $m > $OUT/bench_host_$m.json 2>> $OUT/bench_latest.err; done; echo "host modes done"
-python3 bench.py --workload cfg3 > $OUT/bench_cfg3.json 2>> $OUT/bench_latest.err; echo "cfg3 done"
-python3 bench.py --workload cfg5 > $OUT/bench_cfg5.json 2>> $OUT/bench_latest.err; echo "cfg5 done"; cut -c1-200 $OUT/bench_cfg5.json
+python3 bench.py --workload cfg3 --full > $OUT/bench_cfg3.json 2>> $OUT/bench_latest.err; echo "cfg3 done"
+python3 bench.py --workload cfg5 --full > $OUT/bench_cfg5.json 2>> $OUT/bench_latest.err; echo "cfg5 done"; cut -c1-200 $OUT/bench_cfg5.json
 python3 tools/bench_association.py --runs 3 > $OUT/association_bench.json 2>> $OUT/bench_latest.err; echo "association done"
 python3 tools/bench_backbone.py --frames 72 --chunk 9 --bf16 --iters 5 > $OUT/backbone.txt 2>> $OUT/bench_latest.err
 python3 tools/bench_backbone.py --frames 72 --chunk 8 --bf16 --iters 5 >> $OUT/backbone.txt 2>> $OUT/bench_latest.err

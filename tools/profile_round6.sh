@@ -7,9 +7,9 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/prof6
 rm -rf $OUT; mkdir -p $OUT
 cd $ROOT
-python3 bench.py > $OUT/bench_latest.json 2> $OUT/bench_latest.err; echo "cfg2 (+ secondary legs) done"; cut -c1-200 $OUT/bench_latest.json
-python3 bench.py --workload cfg3 > $OUT/bench_cfg3.json 2>> $OUT/bench_latest.err; echo "cfg3 done"
-python3 bench.py --workload cfg5 > $OUT/bench_cfg5.json 2>> $OUT/bench_latest.err; echo "cfg5 done"; cut -c1-200 $OUT/bench_cfg5.json
+python3 bench.py --full > $OUT/bench_latest.json 2> $OUT/bench_latest.err; echo "cfg2 (+ secondary legs) done"; cut -c1-200 $OUT/bench_latest.json
+python3 bench.py --workload cfg3 --full > $OUT/bench_cfg3.json 2>> $OUT/bench_latest.err; echo "cfg3 done"
+python3 bench.py --workload cfg5 --full > $OUT/bench_cfg5.json 2>> $OUT/bench_latest.err; echo "cfg5 done"; cut -c1-200 $OUT/bench_cfg5.json
 python3 bench.py --workload cfg5 --no-cpu-baseline --frame-chunk 36 > $OUT/bench_cfg5_chunk36.json 2>> $OUT/bench_latest.err; echo "cfg5 (round-5 chunk) done"
 python3 bench.py --workload cfg5 --associate process --no-cpu-baseline --steps 10 --warmup 2 > $OUT/bench_cfg5_associate.json 2>> $OUT/bench_latest.err; echo "cfg5 + association (process) done"
 python3 bench.py --workload cfg5 --associate thread --no-cpu-baseline --steps 6 --warmup 2 > $OUT/bench_cfg5_associate_thread.json 2>> $OUT/bench_latest.err; echo "cfg5 + association (thread) done"
