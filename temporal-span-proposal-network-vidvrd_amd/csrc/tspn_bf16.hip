@@ -15,7 +15,7 @@
 //                               ([tracklet*frame][2C]) so that the pair stage finds the 8 channels a
 //                               lane needs contiguous;
 //   heads_pairgrid_bf16_kernel  pair stage: relu(U[s]+V[o]) -> bf16 in registers (v_pk_add_f32,
-//                               v_cvt_pk_bf16_f32, v_pk_max_i16) as B operand of the [3A,C] head GEMM
+//                               v_maximum3_f32, v_cvt_pk_bf16_f32) as B operand of the [3A,C] head GEMM
 //                               on v_mfma_f32_16x16x32_bf16;
 //   helpers                     fp32->bf16 cast, weight packing, temporal mean.
 #include <algorithm>
@@ -372,8 +372,10 @@ __global__ __launch_bounds__(G_THREADS, 1) void conv3_bf16_big_kernel(
 // channels the 16 projection rows (8 U + 8 V) x 16 frames x 32 ch fp32 = 32 KB are staged by LDS-DMA
 // (double-buffered).  The DMA source of each lane is chosen (comment at `src` below) so that a piece
 // fetches complete 128-byte lines AND the B fragment of lane (f = l&15, kg = l>>4) -- channels
-// 8kg .. 8kg+7 of frame f -- is two conflict-free ds_read_b128.  The VALU work (1.5 packed
-// instructions per activation) hides under the operand stream, which is what bounds the kernel.
+// 8kg .. 8kg+7 of frame f -- is two conflict-free ds_read_b128.  The VALU work (2 instructions per
+// activation since the NaN-propagating ReLU, 1.5 before) no longer hides entirely under the operand stream:
+// cfg3 step 8.17 -> 8.61 ms.  No cheaper correct form exists on gfx950: v_pk_max_i16 on the bf16 pair
+// zeroes a NaN whose sign bit is set, and there is no packed fp32 or bf16 maximum.
 #ifndef TSPN_HPB_SW
 #define TSPN_HPB_SW 2        // subjects per wave of the <8, 16> form (probe knob: 4 = 4 subjects x 8 objects per wave)
 #endif
@@ -382,11 +384,10 @@ constexpr int HP_KC = 32;
 constexpr int HP_ROW = HP_FB * HP_KC * 4;  // 2048 B
 
 __device__ __forceinline__ unsigned relu_pack(float a, float b) {
-  f32x2 s = {a, b};
-  const bf16x2 h = __builtin_convertvector(s, bf16x2);
-  const s16x2 z = {0, 0};
-  // ReLU on the packed pair: negative floats are negative int16 (v_pk_max_i16); -0 -> +0
-  return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, h), z));
+  // ReLU in fp32 with the NaN-propagating maximum (F.relu(NaN) = NaN; -0 -> +0; two v_maximum3_f32), then one rounding to
+  // bf16.  The packed int16 maximum on the bf16 pair this replaces zeroed a NaN whose sign bit is set (a negative int16).
+  const f32x2 s = {tspn::relu_f32(a), tspn::relu_f32(b)};
+  return __builtin_bit_cast(unsigned, __builtin_convertvector(s, bf16x2));
 }
 
 // NW waves; workgroup = 2 NW subjects x OB objects x 16 frames, wave w owns subjects 2w, 2w+1.

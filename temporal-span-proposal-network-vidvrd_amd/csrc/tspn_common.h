@@ -36,6 +36,23 @@ inline int check_launch(const char* what) {
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// ---- non-finite contract
+// ReLU as torch's F.relu: NaN in -> NaN out (fmaxf(v, 0) would return 0).  One v_maximum3_f32 on gfx950.
+__device__ __forceinline__ float relu_f32(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+
+// torch's descending sort order as an unsigned key: larger value -> larger key, every NaN (any sign, any payload)
+// -> 0xffffffff above +Inf (0xff800000), -0 == +0.  Real values never map to 0, which is left for padding.
+__device__ __forceinline__ unsigned order_key(float v) {
+  if (v != v) return 0xffffffffu;
+  const unsigned u = __float_as_uint(v + 0.f);   // -0 + 0 = +0
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// (key, index) order of a stable descending sort: larger key first, lower index first on ties
+__device__ __forceinline__ bool key_before(unsigned ka, int ia, unsigned kb, int ib) {
+  return ka > kb || (ka == kb && ia < ib);
+}
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel.  One static
 // LdsLimit per launch site remembers, per device ordinal, the largest limit already set there, so the
 // attribute call is paid once per (kernel, device) — not once per thread, which left every device but

@@ -295,7 +295,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_mfma_kernel(
         if (m < M) {
           float v = acc[mi][ni][e];
           if (bias != nullptr) v += bias[m];
-          if (relu) v = fmaxf(v, 0.f);
+          if (relu) v = tspn::relu_f32(v);
           ycol[(int64_t)m * ldy] = v;
         }
       }
@@ -560,7 +560,7 @@ __global__ __launch_bounds__(THREADS, (KCD == 8 ? 4 : 2)) void conv3_mfma_dma_ke
         if (m < M) {
           float v = acc[mi][ni][e];
           if (bias != nullptr) v += bias[m];
-          if (relu) v = fmaxf(v, 0.f);
+          if (relu) v = tspn::relu_f32(v);
           ycol[(int64_t)m * ldy] = v;
         }
       }
@@ -779,7 +779,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_mfma_cl_kernel(
         if (m < M) {
           float v = acc[mi][ni][e];
           if (bias != nullptr) v += bias[m];
-          if (relu) v = fmaxf(v, 0.f);
+          if (relu) v = tspn::relu_f32(v);
           ycol[(int64_t)m * ldy] = v;
         }
       }

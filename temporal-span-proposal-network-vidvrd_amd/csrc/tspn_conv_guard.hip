@@ -10,6 +10,8 @@
 // not only random: the Winograd error is largest where an input outlier sits (its rounding error, amplified by the
 // transforms, lands on the other frames of its sextet), so the input transform reports the sextet that holds the
 // launch's largest |x| (`hot`) and that sextet's six frames are always among the checked columns.
+// Non-finite values: an output equal to its float64 value (both NaN, the same infinity) is error 0, any other
+// non-finite deviation is +Inf, so a NaN that F(6,3) smears over a sextet (the direct taps touch three frames) trips it.
 // Result: float bits of the largest |y - y_ref| -> status word TSPN_STATUS_CONV_ERR (system-scope atomic max), number of
 // outputs checked -> TSPN_STATUS_CONV_CHECKS.  The host reads them without a synchronisation before its next call and
 // decides (model.py: warn once, use the direct kernel from then on).
@@ -126,7 +128,12 @@ __global__ __launch_bounds__(THREADS) void conv3_spot_check_kernel(
       double ref = part[0][tid] + part[1][tid] + part[2][tid] + part[3][tid] + (bias ? (double)bias[m] : 0.0);
       if (relu && ref < 0.0) ref = 0.0;
       const float got = y[(bs[s] * Mp + m) * ldy + t];
-      atomicMax(&worst_bits, __float_as_uint((float)fabs((double)got - ref)));
+      // equal values (both NaN, or the same infinity, included) are error 0; any other non-finite deviation is +Inf.
+      // The error is never NaN, so the unsigned max of its bits orders it (an error bit pattern of NaN would mask
+      // every later measurement: the word is only zeroed when the guard trips)
+      const double d = fabs((double)got - ref);
+      const float e = ((double)got == ref || (got != got && ref != ref)) ? 0.f : (d == d ? (float)d : INFINITY);
+      atomicMax(&worst_bits, __float_as_uint(e));
       atomicAdd(&nchecked, 1u);
     }
   }

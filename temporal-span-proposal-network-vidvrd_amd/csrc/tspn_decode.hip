@@ -11,7 +11,9 @@
 // everything upstream of it must cross PCIe; here the [P,K] logits never leave HBM and only
 // topk_seg x (score, triplet, pair) does — which also shrinks the multi-GPU result gather ~500x.
 //
-// Order: larger score first, lower index first on ties (= stable descending sort) at both levels.
+// Order: torch's stable descending sort at both levels -- larger score first, every NaN (any sign or payload) above
+// +Inf, lower index first on ties (NaN ties included); the class argmax returns the first NaN, as torch.argmax.  All
+// compares run on tspn::order_key, so every emitted index is in range whatever the scores hold.
 // Integer / compare work only: bit-exact against the oracle.
 //
 //   kernel 1  one wave per pair: R rounds of wave arg-max over the K scores held in registers
@@ -29,15 +31,8 @@ constexpr int VPT = 4;        // values per lane in kernel 1 -> K <= 256
 constexpr int SEG_THREADS = 1024;
 constexpr int MAX_M = 1024;
 
-__device__ __forceinline__ unsigned order_key(float v) {
-  // monotone map float -> uint32 (larger float => larger key); -0 < +0 is harmless here
-  const unsigned u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ bool better(float va, int ia, float vb, int ib) {
-  return va > vb || (va == vb && ia < ib);
-}
+using tspn::key_before;
+using tspn::order_key;
 
 __global__ __launch_bounds__(256) void pair_topk_kernel(const float* __restrict__ logits,
                                                         int64_t rows, int K, int R,
@@ -48,48 +43,57 @@ __global__ __launch_bounds__(256) void pair_topk_kernel(const float* __restrict_
   if (row >= rows) return;
   const float* src = logits + row * K;
   float v[VPT];
+  unsigned kv[VPT];
 #pragma unroll
   for (int i = 0; i < VPT; ++i) {
     const int k = lane + 64 * i;
-    v[i] = k < K ? src[k] : -INFINITY;
+    v[i] = k < K ? src[k] : 0.f;
+    kv[i] = order_key(v[i]);
   }
   unsigned used = 0;
+  // R <= K and every real score has a key > 0: each round selects an unused k < K
   for (int r = 0; r < R; ++r) {
-    float bv = -INFINITY;
+    unsigned bk = 0;
     int bi = 0x7fffffff;
 #pragma unroll
     for (int i = 0; i < VPT; ++i) {
       const int k = lane + 64 * i;
-      if (k < K && !((used >> i) & 1u) && better(v[i], k, bv, bi)) {
-        bv = v[i];
+      if (k < K && !((used >> i) & 1u) && key_before(kv[i], k, bk, bi)) {
+        bk = kv[i];
         bi = k;
       }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-      const float ov = __shfl_xor(bv, off);
+      const unsigned ok = __shfl_xor(bk, off);
       const int oi = __shfl_xor(bi, off);
-      if (better(ov, oi, bv, bi)) {
-        bv = ov;
+      if (key_before(ok, oi, bk, bi)) {
+        bk = ok;
         bi = oi;
       }
     }
-    if ((bi & 63) == lane && bi < K) used |= 1u << (bi >> 6);
-    if (lane == 0) {
+    if ((bi & 63) == lane && bi < K) {           // the owner of the winner writes its value (NaN payloads kept)
+      float bv = v[0];
+#pragma unroll
+      for (int i = 1; i < VPT; ++i)
+        if ((bi >> 6) == i) bv = v[i];
+      used |= 1u << (bi >> 6);
       sc[row * R + r] = bv;
       ix[row * R + r] = bi;
     }
   }
 }
 
-__device__ int argmax_first(const float* p, int n) {
-  float bv = p[0];
+__device__ int argmax_first(const float* p, int n) {   // torch.argmax: the first NaN, else the first maximum
+  unsigned bk = order_key(p[0]);
   int bi = 0;
-  for (int i = 1; i < n; ++i)
-    if (p[i] > bv) {
-      bv = p[i];
+  for (int i = 1; i < n; ++i) {
+    const unsigned k = order_key(p[i]);
+    if (k > bk) {
+      bk = k;
       bi = i;
     }
+  }
   return bi;
 }
 
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(SEG_THREADS) void segment_topk_kernel(
     int64_t* __restrict__ out_trip, int64_t* __restrict__ out_tid) {
   __shared__ unsigned hist[256];
   __shared__ unsigned s_prefix, s_need, s_count;
-  __shared__ float kv[MAX_M];
+  __shared__ unsigned kk[MAX_M];
   __shared__ int ki[MAX_M];
 
   const int tid = threadIdx.x;
@@ -175,12 +179,11 @@ __global__ __launch_bounds__(SEG_THREADS) void segment_topk_kernel(
   if (tid == 0) s_count = 0;
   __syncthreads();
   for (int i = tid; i < Q; i += SEG_THREADS) {
-    const float v = cand[i];
-    const unsigned k = order_key(v);
+    const unsigned k = order_key(cand[i]);
     if (k > kth || (k == kth && (unsigned)i <= last_tie_idx)) {
       const unsigned slot = atomicAdd(&s_count, 1u);
       if (slot < (unsigned)MAX_M) {
-        kv[slot] = v;
+        kk[slot] = k;
         ki[slot] = i;
       }
     }
@@ -190,7 +193,7 @@ __global__ __launch_bounds__(SEG_THREADS) void segment_topk_kernel(
   while (m2 < M) m2 <<= 1;
   for (int i = tid; i < m2; i += SEG_THREADS)
     if (i >= M) {
-      kv[i] = -INFINITY;
+      kk[i] = 0u;                                  // below every real key
       ki[i] = 0x7fffffff;
     }
   __syncthreads();
@@ -199,13 +202,13 @@ __global__ __launch_bounds__(SEG_THREADS) void segment_topk_kernel(
       for (int i = tid; i < m2; i += SEG_THREADS) {
         const int l = i ^ j;
         if (l > i) {
-          const float vi = kv[i], vl = kv[l];
+          const unsigned vi = kk[i], vl = kk[l];
           const int ii = ki[i], il = ki[l];
           const bool fwd = (i & k) == 0;
-          const bool swap = fwd ? better(vl, il, vi, ii) : better(vi, ii, vl, il);
+          const bool swap = fwd ? key_before(vl, il, vi, ii) : key_before(vi, ii, vl, il);
           if (swap) {
-            kv[i] = vl;
-            kv[l] = vi;
+            kk[i] = vl;
+            kk[l] = vi;
             ki[i] = il;
             ki[l] = ii;
           }
@@ -221,7 +224,7 @@ __global__ __launch_bounds__(SEG_THREADS) void segment_topk_kernel(
     const int pi = flat / R;
     const int64_t ts = pairs[(seg * P + pi) * 2], to = pairs[(seg * P + pi) * 2 + 1];
     const int64_t o = seg * M + r;
-    out_score[o] = kv[r];
+    out_score[o] = cand[flat];
     out_tid[2 * o] = ts;
     out_tid[2 * o + 1] = to;
     out_trip[3 * o] = argmax_first(cls_sub + (seg * seg_rows + row_mul * ts) * ld, NO);

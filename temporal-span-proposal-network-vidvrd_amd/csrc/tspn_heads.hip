@@ -106,15 +106,15 @@ __global__ __launch_bounds__(WAVES * 64) void heads_kernel(
         h1 = va.y;
         if (MODE == 1) {
           const float2 vb = *reinterpret_cast<const float2*>(pb[q] + roff + lA);
-          h0 = fmaxf(h0 + vb.x + bc, 0.f);
-          h1 = fmaxf(h1 + vb.y + bc, 0.f);
+          h0 = tspn::relu_f32(h0 + vb.x + bc);
+          h1 = tspn::relu_f32(h1 + vb.y + bc);
         }
       } else {
         h0 = pa[q][roff + lA];
         h1 = pa[q][roff + lB];
         if (MODE == 1) {
-          h0 = fmaxf(h0 + pb[q][roff + lA] + bc, 0.f);
-          h1 = fmaxf(h1 + pb[q][roff + lB] + bc, 0.f);
+          h0 = tspn::relu_f32(h0 + pb[q][roff + lA] + bc);
+          h1 = tspn::relu_f32(h1 + pb[q][roff + lB] + bc);
         }
       }
       acc[q][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa, h0, acc[q][0], 0, 0, 0);
@@ -267,8 +267,8 @@ __global__ __launch_bounds__(256, 2) void heads_pairgrid_kernel(
       for (int si = 0; si < 2; ++si)
 #pragma unroll
         for (int oj = 0; oj < PG_O; ++oj) {
-          const float h0 = fmaxf(u[si].x + v[oj].x, 0.f);
-          const float h1 = fmaxf(u[si].y + v[oj].y, 0.f);
+          const float h0 = tspn::relu_f32(u[si].x + v[oj].x);
+          const float h1 = tspn::relu_f32(u[si].y + v[oj].y);
           acc[si][oj][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, h0, acc[si][oj][0], 0, 0, 0);
           acc[si][oj][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(w, h1, acc[si][oj][1], 0, 0, 0);
         }
@@ -427,8 +427,8 @@ __global__ __launch_bounds__(256, 2) void heads_pairgrid3_kernel(
     HB r;
 #pragma unroll
     for (int oj = 0; oj < PG_O; ++oj) {
-      r.h[oj][0] = fmaxf(f.u[si].x + f.v[oj].x, 0.f);
-      r.h[oj][1] = fmaxf(f.u[si].y + f.v[oj].y, 0.f);
+      r.h[oj][0] = tspn::relu_f32(f.u[si].x + f.v[oj].x);
+      r.h[oj][1] = tspn::relu_f32(f.u[si].y + f.v[oj].y);
     }
     return r;
   };
@@ -630,7 +630,7 @@ __global__ __launch_bounds__(256, CK == 8 ? 3 : 2) void heads_pairgrid4_kernel(
     for (int e = 0; e < 2; ++e) {
 #pragma unroll
       for (int op = 0; op < PG_O / 2; ++op) {
-        const f32x2 a{fmaxf(st.u[e] + st.v[2 * op][e], 0.f), fmaxf(st.u[e] + st.v[2 * op + 1][e], 0.f)};
+        const f32x2 a{tspn::relu_f32(st.u[e] + st.v[2 * op][e]), tspn::relu_f32(st.u[e] + st.v[2 * op + 1][e])};
 #pragma unroll
         for (int h = 0; h < H; h += 2) {
           const f32x4& wq = w[3 * e + (h >> 2)];

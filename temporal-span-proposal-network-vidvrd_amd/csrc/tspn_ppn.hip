@@ -9,7 +9,8 @@
 // with every intermediate in LDS.  The sort is a bitonic network over
 // (value, flat index) with the total order "larger value first, lower index
 // first on ties" (= a stable descending sort; the reference's unstable sort
-// leaves tie order unspecified — SURVEY.md §7 hard part 3).
+// leaves tie order unspecified — SURVEY.md §7 hard part 3).  The keys are tspn::order_key, torch's order: a NaN
+// entry (a tracklet with NaN class logits) ranks above +Inf and leaves the order of the finite ones intact.
 // Indices are into the N x N matrix including the diagonal (s*N + o).
 #include <algorithm>
 #include <cmath>
@@ -19,10 +20,6 @@
 namespace {
 
 constexpr int PPN_THREADS = 1024;
-
-__device__ __forceinline__ bool before(float ka, int ia, float kb, int ib) {
-  return ka > kb || (ka == kb && ia < ib);
-}
 
 __global__ __launch_bounds__(PPN_THREADS) void ppn_kernel(
     const float* __restrict__ cls, int N, int Cin, int H, int Cout,
@@ -35,8 +32,8 @@ __global__ __launch_bounds__(PPN_THREADS) void ppn_kernel(
   float* s_hid = s_cls + N * Cin;                      // [N][H]
   float* s_es = s_hid + N * H;                         // [N][Cout]
   float* s_eo = s_es + N * Cout;                       // [N][Cout]
-  float* s_key = s_eo + N * Cout;                      // [n2p]
-  int* s_idx = reinterpret_cast<int*>(s_key + n2p);    // [n2p]
+  unsigned* s_key = reinterpret_cast<unsigned*>(s_eo + N * Cout);   // [n2p] order keys
+  int* s_idx = reinterpret_cast<int*>(s_key + n2p);                  // [n2p]
 
   const int tid = threadIdx.x;
   const int64_t b = blockIdx.x;
@@ -55,7 +52,7 @@ __global__ __launch_bounds__(PPN_THREADS) void ppn_kernel(
       float acc = 0.f;
       for (int k = 0; k < Cin; ++k) acc += s_cls[n * Cin + k] * w1[h * Cin + k];
       acc += b1[h];
-      s_hid[i] = fmaxf(acc, 0.f);
+      s_hid[i] = tspn::relu_f32(acc);
     }
     __syncthreads();
     for (int i = tid; i < N * Cout; i += PPN_THREADS) {
@@ -75,10 +72,10 @@ __global__ __launch_bounds__(PPN_THREADS) void ppn_kernel(
       for (int k = 0; k < Cout; ++k) acc += s_es[s * Cout + k] * s_eo[o * Cout + k];
       const float v = 1.f / (1.f + expf(-acc));
       out_mat[b * n2 + i] = v;
-      s_key[i] = v;
+      s_key[i] = tspn::order_key(v);
       s_idx[i] = i;
     } else {
-      s_key[i] = -INFINITY;
+      s_key[i] = 0u;                                  // below every real key
       s_idx[i] = 0x7fffffff;
     }
   }
@@ -89,10 +86,10 @@ __global__ __launch_bounds__(PPN_THREADS) void ppn_kernel(
       for (int i = tid; i < n2p; i += PPN_THREADS) {
         const int l = i ^ j;
         if (l > i) {
-          const float ki = s_key[i], kl = s_key[l];
+          const unsigned ki = s_key[i], kl = s_key[l];
           const int ii = s_idx[i], il = s_idx[l];
           const bool fwd = (i & k) == 0;
-          const bool swap = fwd ? before(kl, il, ki, ii) : before(ki, ii, kl, il);
+          const bool swap = fwd ? tspn::key_before(kl, il, ki, ii) : tspn::key_before(ki, ii, kl, il);
           if (swap) {
             s_key[i] = kl;
             s_key[l] = ki;

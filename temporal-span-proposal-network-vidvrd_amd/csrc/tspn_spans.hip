@@ -8,6 +8,7 @@
 //   candidate c = t*A + a: centre t, width sizes[a];  (d_c, d_w) = duration channels (2a, 2a+1)
 //   ctr = t + d_c*size ; w = size*exp(min(d_w, log(1000/16)))          -- in float64
 //   start/end = clip(ctr -+ w/2, 0, T) rounded to fp32 ; frames [floor(start), ceil(end))
+//   a candidate whose logit, d_c or d_w is NaN is not a proposal (skipped before the NMS); +-Inf rank / clamp normally
 //   rank by relationness logit (larger first, lower c first), first `pre_nms` enter a greedy NMS
 //   (suppress j if inter > thr*union, float64 on the fp32 spans), first `top_k` survivors kept.
 // The float64 arithmetic makes the result reproducible to the bit on any IEEE machine, so the
@@ -32,10 +33,6 @@ struct SpanSizes {
   float v[SP_MAX_A];
 };
 
-__device__ __forceinline__ bool sp_before(float ka, int ia, float kb, int ib) {
-  return ka > kb || (ka == kb && ia < ib);
-}
-
 __global__ __launch_bounds__(SP_THREADS) void decode_spans_kernel(
     const float* __restrict__ heads, int A, int T, SpanSizes sizes, int top_k, double thr, int m,
     int n2, int64_t* __restrict__ out_anchor, int64_t* __restrict__ out_span,
@@ -47,11 +44,12 @@ __global__ __launch_bounds__(SP_THREADS) void decode_spans_kernel(
   float* c_logit = c_end + SP_MAX_PRE;
   int* c_cand = reinterpret_cast<int*>(c_logit + SP_MAX_PRE);
   char* u = reinterpret_cast<char*>(c_cand + SP_MAX_PRE);
-  float* s_key = reinterpret_cast<float*>(u);
+  unsigned* s_key = reinterpret_cast<unsigned*>(u);
   int* s_idx = reinterpret_cast<int*>(s_key + n2);
   unsigned long long* s_mask = reinterpret_cast<unsigned long long*>(u);
   __shared__ int s_kept[SP_MAX_PRE];
   __shared__ int s_nkept;
+  __shared__ int s_m;
 
   const int tid = threadIdx.x;
   const int64_t p = blockIdx.x;
@@ -59,15 +57,18 @@ __global__ __launch_bounds__(SP_THREADS) void decode_spans_kernel(
   const float* rel = heads + p * 3 * A * (int64_t)T;  // rows [0,A) relationness, [A,3A) duration
   const float* dur = rel + (int64_t)A * T;
 
+  // sort key: tspn::order_key of the logit for a proposal, 0 (below every real key) for a candidate with a NaN logit,
+  // d_c or d_w and for the padding; the valid ones lead the sorted list in the oracle's order
+  if (tid == 0) s_m = 0;
   for (int c = tid; c < n2; c += SP_THREADS) {
+    unsigned key = 0u;
     if (c < n) {
       const int t = c / A, a = c - t * A;
-      s_key[c] = rel[a * T + t];
-      s_idx[c] = c;
-    } else {
-      s_key[c] = -INFINITY;
-      s_idx[c] = 0x7fffffff;
+      const float lg = rel[a * T + t], dc = dur[(2 * a) * T + t], dw = dur[(2 * a + 1) * T + t];
+      key = (lg == lg && dc == dc && dw == dw) ? tspn::order_key(lg) : 0u;
     }
+    s_key[c] = key;
+    s_idx[c] = c < n ? c : 0x7fffffff;
   }
   __syncthreads();
   for (int k = 2; k <= n2; k <<= 1) {
@@ -75,10 +76,10 @@ __global__ __launch_bounds__(SP_THREADS) void decode_spans_kernel(
       for (int i = tid; i < n2; i += SP_THREADS) {
         const int l = i ^ j;
         if (l > i) {
-          const float ki = s_key[i], kl = s_key[l];
+          const unsigned ki = s_key[i], kl = s_key[l];
           const int ii = s_idx[i], il = s_idx[l];
           const bool fwd = (i & k) == 0;
-          const bool swap = fwd ? sp_before(kl, il, ki, ii) : sp_before(ki, ii, kl, il);
+          const bool swap = fwd ? tspn::key_before(kl, il, ki, ii) : tspn::key_before(ki, ii, kl, il);
           if (swap) {
             s_key[i] = kl;
             s_key[l] = ki;
@@ -90,6 +91,11 @@ __global__ __launch_bounds__(SP_THREADS) void decode_spans_kernel(
       __syncthreads();
     }
   }
+  // ---- the proposals among the m leaders: the first m_eff (the sorted keys fall to 0 where they end)
+  for (int i = tid; i < m; i += SP_THREADS)
+    if (s_key[i] != 0u && (i + 1 == m || s_key[i + 1] == 0u)) s_m = i + 1;
+  __syncthreads();
+  m = s_m;
   // ---- decode the m leaders (float64), compact
   const double dw_clamp = 4.135166556742356;  // log(1000/16)
   for (int i = tid; i < m; i += SP_THREADS) {
@@ -104,7 +110,7 @@ __global__ __launch_bounds__(SP_THREADS) void decode_spans_kernel(
     const double hi = fmin(fmax(ctr + 0.5 * w, 0.0), (double)T);
     c_start[i] = (float)lo;
     c_end[i] = (float)hi;
-    c_logit[i] = s_key[i];
+    c_logit[i] = rel[a * T + t];
     c_cand[i] = c;
   }
   __syncthreads();

@@ -139,10 +139,16 @@ __global__ __launch_bounds__(256) void wino63_input_transform_kernel(
     d[i] = (ok && t >= 0 && t < T) ? v : f32x4{0.f, 0.f, 0.f, 0.f};
   }
   if (hot) {                                                         // uniform
+    // NaN-propagating maxima (fmaxf drops NaN): a NaN input makes its sextet hot, and |NaN| (sign cleared by fabsf)
+    // has larger bits than +Inf, so NaN ranks above Inf in the key.  Only the sextet's OWN frames d[1..6] count: a value
+    // in the halo d[0] / d[7] enters one transformed column of the neighbour (one of its outputs), while the sextet that
+    // holds it carries it into all six -- with the window counted, the equal keys of both went to the later sextet.
     float m = 0.f;
 #pragma unroll
-    for (int i = 0; i < 8; ++i)
-      m = fmaxf(fmaxf(m, fmaxf(fabsf(d[i][0]), fabsf(d[i][1]))), fmaxf(fabsf(d[i][2]), fabsf(d[i][3])));
+    for (int i = 1; i < 7; ++i)
+      m = __builtin_elementwise_maximum(
+          __builtin_elementwise_maximum(m, __builtin_elementwise_maximum(fabsf(d[i][0]), fabsf(d[i][1]))),
+          __builtin_elementwise_maximum(fabsf(d[i][2]), fabsf(d[i][3])));
     unsigned long long key = ((unsigned long long)__float_as_uint(m) << 32) | (unsigned)(S < nsext ? S : 0);
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
@@ -414,7 +420,7 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
           }
           if (relu) {
 #pragma unroll
-            for (int i = 0; i < 6; ++i) o[i] = fmaxf(o[i], 0.f);
+            for (int i = 0; i < 6; ++i) o[i] = tspn::relu_f32(o[i]);
           }
           float* dst = ycol + (int64_t)m * ldy;
           if (vec2) {

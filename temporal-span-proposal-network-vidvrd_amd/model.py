@@ -849,14 +849,16 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                 return True
             err = float(words[_abi.STATUS_CONV_ERR:_abi.STATUS_CONV_ERR + 1].view(np.float32)[0])
             self.conv_err_seen = max(self.conv_err_seen, err)
-            if err > self.conv_tol:
+            if not (err <= self.conv_tol):     # a non-finite measurement (+Inf: a NaN / Inf where float64 has none) trips
                 checks = int(words[_abi.STATUS_CONV_CHECKS])
                 words[_abi.STATUS_CONV_ERR] = 0
                 words[_abi.STATUS_CONV_CHECKS] = 0
                 self.conv_fallback = True
                 warnings.warn(
                     f"TSPN: the Winograd F(6,3) temporal conv measured an absolute error of {err:.3g} against float64 "
-                    f"on this model's inputs ({checks} outputs spot-checked), above RELPN.DPN.CONV_TOL = {self.conv_tol:g}: "
+                    f"on this model's inputs ({checks} outputs spot-checked), above RELPN.DPN.CONV_TOL = {self.conv_tol:g}"
+                    + (" (inf: a NaN or Inf output where float64 has a different value -- non-finite inputs, which F(6,3) "
+                       "smears over their sextet)" if not np.isfinite(err) else "") + ": "
                     "using the direct kernel (reference-order fp32 taps, about 2.2x slower) from this call on.  Set "
                     "RELPN.DPN.CONV_ALGO = 'direct' to start there, or raise CONV_TOL if the features' scale makes "
                     "1e-4 absolute meaningless (INTEGRATION.md §3).", RuntimeWarning, stacklevel=3)

@@ -275,3 +275,49 @@ def test_roi_align_oracle_known_answers():
     const = ro.roi_align_nhwc(np.full((1, 5, 5, 3), 2.5, dtype=np.float32), np.array([[0, 1, 1, 30, 40]], dtype=np.float32),
                               3, 0.1, 0, True)
     np.testing.assert_allclose(const.numpy(), 2.5, rtol=1e-6)
+
+
+# ------------------------------------------------------------------ non-finite rules
+def test_decode_topk_oracle_ranks_nan_first_like_torch():
+    """Hand-computed: every NaN (either sign) above +Inf, ties (NaN ties too) to the lower index, argmax = first NaN."""
+    nan_neg = float(np.uint32(0xffc00000).view(np.float32))
+    logit = torch.tensor([[1.0, float("nan"), float("inf"), nan_neg],
+                          [float("inf"), 2.0, float("-inf"), 2.0]])
+    feat = torch.zeros(2, 70)
+    feat[0, 4] = float("nan")
+    feat[0, 6] = float("nan")
+    feat[0, 9] = float("inf")                        # subject of tracklet 0: first NaN = class 4
+    feat[1, 35 + 2] = 5.0                            # object of tracklet 1: class 2
+    pairs = torch.tensor([[0, 1], [1, 0]])
+    sc, trip, tids = oracle.decode_topk(logit, feat, pairs, num_tracklets=2, topk_per_pair=3, topk_per_seg=5)
+    # per pair: row 0 -> (nan@1, nan@3, inf@2); row 1 -> (inf@0, 2@1, 2@3); over the segment: NaN, NaN, inf, inf, 2
+    assert [int(k) for k in trip[:, 1]] == [1, 3, 2, 0, 1]
+    assert [list(map(int, p)) for p in tids] == [[0, 1], [0, 1], [0, 1], [1, 0], [1, 0]]
+    assert torch.isnan(sc[:2]).all() and sc[2] == float("inf") and sc[3] == float("inf") and sc[4] == 2.0
+    assert int(trip[0, 0]) == 4 and int(trip[0, 2]) == 2
+
+
+def test_decode_spans_oracle_skips_nan_candidates():
+    """A = 1, T = 4, size 2: candidate 1 has a NaN d_w, candidate 2 a NaN logit -- neither is a proposal, nor does it take a
+    pre_nms place; a -Inf logit still ranks, a +Inf d_c clips to [T, T] and d_w = +Inf takes the clamp."""
+    rel = torch.tensor([[[0.5, 3.0, float("nan"), float("-inf")]]])
+    dur = torch.tensor([[[0.0, 0.0, 0.0, float("inf")],
+                         [0.0, float("nan"), 0.0, float("inf")]]])
+    out = oracle.decode_spans(rel, dur, [2.0], top_k=4, nms_threshold=0.5, pre_nms=2)
+    assert int(out["count"][0]) == 2
+    assert out["anchor"][0].tolist() == [0, 3, -1, -1]
+    assert out["span_f"][0, 0].tolist() == [0.0, 1.0] and out["span_f"][0, 1].tolist() == [4.0, 4.0]
+    assert out["span"][0, 1].tolist() == [3, 4]
+    assert float(out["score"][0, 1]) == 0.0
+
+
+def test_dpn_head_oracle_propagates_nan_through_relu():
+    x = torch.zeros(1, 2, 5, dtype=torch.float64)
+    x[0, 0, 2] = float("nan")
+    w = torch.ones(2, 2, 3, dtype=torch.float64)
+    b = torch.full((2,), -1.0, dtype=torch.float64)        # relu(conv) is 0 wherever x is finite
+    dw = torch.ones(2, 2, 1, dtype=torch.float64)
+    rel, dur, t = oracle.dpn_head(x, w, b, dw, torch.zeros(2, dtype=torch.float64))
+    assert rel is None
+    assert torch.isnan(t[0, :, 1:4]).all() and (t[0, :, [0, 4]] == 0).all()
+    assert torch.isnan(dur[0, :, 1:4]).all() and (dur[0, :, [0, 4]] == 0).all()
