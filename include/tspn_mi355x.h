@@ -92,7 +92,9 @@ int tspn_status_selftest(int32_t* reached_end, void* stream);
 /* tspn_fused_desc.conv_algo: which temporal-conv kernel consumes `conv_packed` (the packing IS the choice) */
 enum {
   TSPN_CONV_DIRECT = 0,      /* conv_packed = tspn_pack_conv3_f32(conv.weight, C, C, split = D): [3][D][2C]; any shape */
-  TSPN_CONV_WINOGRAD63 = 1   /* conv_packed = tspn_pack_conv3_wino63_frag_f32(conv.weight, C, C, split = D); D % 32 == 0 */
+  TSPN_CONV_WINOGRAD63 = 1,  /* conv_packed = tspn_pack_conv3_wino63_frag_f32(conv.weight, C, C, split = D); D % 32 == 0 */
+  TSPN_CONV_WINOGRAD63_F16X3 = 2   /* conv_packed = tspn_pack_conv3_wino63_f16x3(conv.weight, C, C, split = D) (int16
+                                      storage); D % 64 == 0; the same F(6,3) on split-fp16 MFMAs */
 };
 
 int tspn_version(void);
@@ -258,6 +260,23 @@ int tspn_conv3_tc_wino63_f32(const float* x, int64_t B, int64_t T, int64_t Cin, 
  * workspace is below 4 GB, 64-bit pointers above; 1 = pointers everywhere.  Both forms land the same bytes in LDS
  * (tests compare them bit for bit).  Process-wide; returns the previous value, TSPN_EINVAL for any other `form`. */
 int tspn_conv3_tc_wino63_set_piece_form(int form);
+
+/* Split-fp16 form of the same F(6,3) conv (tspn_wino63.hip; additive, no layout change): the 8 point GEMMs run on
+ * v_mfma_f32_32x32x16_f16 with every operand split into fp16 hi + lo parts, x.w ~ hi.hi + hi.lo + lo.hi (three f16
+ * products, each exact in fp32, one fp32 accumulator), and power-of-two scales per (point, weight row) and per
+ * (point, sextet column of the transformed input) that keep both parts inside fp16's range.  Error against float64
+ * not above the fp32 form's bounds (tests/test_gpu_wino63_f16x3.py).
+ *   packed = tspn_pack_conv3_wino63_f16x3(conv.weight [M, Cin, 3], split): int16 storage of
+ *            [8 points][2 Cin'/8 + 1][M'][8] (hi parts, lo parts, one 16-byte slot per row holding its int32 exponent),
+ *            tspn_pack_conv3_wino63_f16x3_elements(M, Cin, split) elements, 16-byte aligned
+ *   workspace >= tspn_conv3_tc_wino63_f16x3_workspace_bytes(B, T, Cin, M), 256-byte aligned
+ * Needs Cin % 32 == 0, M % 256 == 0.  tspn_forward_fused_f32 runs it for conv_algo TSPN_CONV_WINOGRAD63_F16X3.      */
+size_t tspn_pack_conv3_wino63_f16x3_elements(int64_t M, int64_t Cin, int64_t split);
+int tspn_pack_conv3_wino63_f16x3(const float* W, int64_t M, int64_t Cin, int64_t split, int16_t* packed, void* stream);
+size_t tspn_conv3_tc_wino63_f16x3_workspace_bytes(int64_t B, int64_t T, int64_t Cin, int64_t M);
+int tspn_conv3_tc_wino63_f16x3(const float* x, int64_t B, int64_t T, int64_t Cin, const int16_t* packed,
+                               int64_t M, const float* bias, int relu, float* y,
+                               void* workspace, size_t workspace_bytes, void* stream);
 
 
 

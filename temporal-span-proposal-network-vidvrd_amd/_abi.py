@@ -27,7 +27,7 @@ STATUS_FAULT, STATUS_FAULT_INFO, STATUS_CONV_ERR, STATUS_CONV_CHECKS = 0, 1, 2, 
 FAULT_HANDOVER = 1
 CONV_CHECK_HOT_OFFSET, CONV_CHECK_SCRATCH_BYTES = 256, 256 + 256 * 64   # tspn_conv3_spot_check_f32's scratch layout
 GEOM_CHANNELS = 8
-CONV_DIRECT, CONV_WINOGRAD63 = 0, 1   # tspn_fused_desc.conv_algo
+CONV_DIRECT, CONV_WINOGRAD63, CONV_WINOGRAD63_F16X3 = 0, 1, 2   # tspn_fused_desc.conv_algo
 
 _c_f32p = ctypes.c_void_p   # device pointers travel as integers
 _c_i64p = ctypes.c_void_p
@@ -149,6 +149,10 @@ PROTOTYPES = {
     "tspn_conv3_tc_wino63_workspace_bytes": (_sz, [_i64, _i64, _i64]),
     "tspn_conv3_tc_wino63_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _int, _vp, _vp, _sz, _vp]),
     "tspn_conv3_tc_wino63_set_piece_form": (_int, [_int]),
+    "tspn_pack_conv3_wino63_f16x3_elements": (_sz, [_i64, _i64, _i64]),
+    "tspn_pack_conv3_wino63_f16x3": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
+    "tspn_conv3_tc_wino63_f16x3_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
+    "tspn_conv3_tc_wino63_f16x3": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _int, _vp, _vp, _sz, _vp]),
     "tspn_span_predicate_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "tspn_span_predicate_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "tspn_cast_bf16": (_int, [_vp, _i64, _vp, _vp]),

@@ -73,6 +73,12 @@ _DEFAULTS = {
                 # its next call on (model.BaseModel._winograd).  0 rows = guard off.
                 "CONV_TOL": 1e-4,
                 "CONV_CHECK_ROWS": 128,
+                # build extension: once CONV_F16X3_AFTER calls of a model have read a guard measurement of its fp32 F(6,3)
+                # passes within CONV_TOL, its later calls run the same F(6,3) on split-fp16 MFMAs (hi + lo parts, three f16
+                # products, fp32 accumulation; needs D % 128 == 0), spot-checked the same way.  False keeps every call on
+                # the fp32 form.
+                "CONV_F16X3": True,
+                "CONV_F16X3_AFTER": 4,
                 # build extension: tracklet features handed over in HOST memory (predict.py:50-57) go to the device in
                 # chunks of this many videos, pipelined under the encoder (model._HostPipeline)
                 "HOST_CHUNK_VIDEOS": 4},

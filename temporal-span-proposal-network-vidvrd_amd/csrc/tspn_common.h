@@ -90,6 +90,15 @@ int wino63_contract(const void* workspace, int64_t B, int64_t T, int64_t Cin, co
 int conv3_tc_wino63(const float* x, int64_t B, int64_t T, int64_t Cin, const float* frag, int64_t M,
                     const float* bias, int relu, float* y, int64_t ldy, void* workspace,
                     size_t workspace_bytes, void* stream);
+// Split-fp16 F(6,3) (TSPN_CONV_WINOGRAD63_F16X3, tspn_wino63.hip): Cin % 32 == 0, M % 256 == 0; the workspace holds the
+// split transformed input and the contraction's parking area
+bool wino63_f16x3_supported(int64_t Cin, int64_t M);
+size_t wino63_f16x3_workspace_bytes(int64_t B, int64_t T, int64_t Cin, int64_t M);
+int wino63_f16x3_input_transform(const float* x, int64_t B, int64_t T, int64_t Cin, int64_t M, void* workspace,
+                                 size_t workspace_bytes, void* stream, uint64_t* hot = nullptr);
+int wino63_f16x3_contract(void* workspace, size_t workspace_bytes, int64_t B, int64_t T, int64_t Cin,
+                          const int16_t* packed, int64_t M, const float* bias, int relu, float* y, int64_t ldy,
+                          void* stream);
 int heads_pairgrid(const float* y, int64_t ldt, int64_t B, int64_t N, int64_t C, int64_t T,
                    const float* Wh, const float* bh, int64_t H, float* out, void* stream, float* Wp12 = nullptr);
 inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }

@@ -44,6 +44,9 @@ FusedLayout layout_of(const tspn_fused_desc* d) {
   L.lin = take(L.lin_bytes);
   // Winograd-transformed input V of the F(6,3) kernel (conv_algo TSPN_CONV_WINOGRAD63)
   L.vt_bytes = (D % 32 == 0) ? tspn::wino63_workspace_bytes((int64_t)NT, (int64_t)T, (int64_t)D) : 0;
+  // (split-fp16 F(6,3): its split input and the contraction's parking area instead)
+  if (d->conv_algo == TSPN_CONV_WINOGRAD63_F16X3)
+    L.vt_bytes = tspn::wino63_f16x3_workspace_bytes((int64_t)NT, (int64_t)T, (int64_t)D, (int64_t)(2 * C));
   L.vt = take(L.vt_bytes);
   L.hwp = take(C * 12 * sizeof(float));   // head weights packed [C][12] for the scalar-weight pair stage (H == 12)
   L.hot = take(TSPN_CONV_CHECK_SCRATCH_BYTES);   // accuracy guard: scratch of tspn_conv3_spot_check_f32 (tspn_conv_guard.hip)
@@ -114,13 +117,19 @@ extern "C" int tspn_forward_fused_f32(const tspn_fused_desc* d, void* stream) {
   // through a transpose to channels-first [NT,D,T] and the general kernel.
   const bool tc = (D % 16 == 0) && ((reinterpret_cast<uintptr_t>(d->feats) & 15) == 0) &&
                   ((reinterpret_cast<uintptr_t>(d->conv_packed) & 15) == 0);
-  TSPN_REQUIRE(d->conv_algo == TSPN_CONV_DIRECT || d->conv_algo == TSPN_CONV_WINOGRAD63, TSPN_EINVAL,
-               "tspn_forward_fused: conv_algo must be TSPN_CONV_DIRECT (0) or TSPN_CONV_WINOGRAD63 (1), got %d",
-               d->conv_algo);
-  const bool w63 = d->conv_algo == TSPN_CONV_WINOGRAD63;
+  TSPN_REQUIRE(d->conv_algo == TSPN_CONV_DIRECT || d->conv_algo == TSPN_CONV_WINOGRAD63 ||
+                   d->conv_algo == TSPN_CONV_WINOGRAD63_F16X3,
+               TSPN_EINVAL,
+               "tspn_forward_fused: conv_algo must be TSPN_CONV_DIRECT (0), TSPN_CONV_WINOGRAD63 (1) or "
+               "TSPN_CONV_WINOGRAD63_F16X3 (2), got %d",
+               (int)d->conv_algo);
+  const bool f16x3 = d->conv_algo == TSPN_CONV_WINOGRAD63_F16X3;
+  const bool w63 = d->conv_algo == TSPN_CONV_WINOGRAD63 || f16x3;
   TSPN_REQUIRE(!w63 || (tc && tspn::wino63_supported(D, 2 * C)), TSPN_EUNSUPPORTED,
                "tspn_forward_fused: TSPN_CONV_WINOGRAD63 needs D %% 32 == 0 and 16-byte aligned operands "
                "(pack the weights with tspn_pack_conv3_f32 and pass TSPN_CONV_DIRECT otherwise)");
+  TSPN_REQUIRE(!f16x3 || tspn::wino63_f16x3_supported(D, 2 * C), TSPN_EUNSUPPORTED,
+               "tspn_forward_fused: TSPN_CONV_WINOGRAD63_F16X3 needs D %% 64 == 0 (4D %% 256 == 0)");
   // On the fast path the rows of y are padded to ldy = ceil4(T) frames so that the blocked pair stage
   // can stage them with 16-byte LDS-DMA pieces that never leave a row (pad frames are never read out).
   // (needs what the DMA pair-stage kernel needs: even T, C % 16 == 0 — implied by tc)
@@ -136,11 +145,18 @@ extern "C" int tspn_forward_fused_f32(const tspn_fused_desc* d, void* stream) {
   // (scratch of the spot check: the workgroups' meeting point + the slots the transform reports the hot sextet into)
   if (guard && hipMemsetAsync(hot, 0, TSPN_CONV_CHECK_SCRATCH_BYTES, s) != hipSuccess)
     return tspn::fail(TSPN_ELAUNCH, "tspn_forward_fused: guard staging: %s", hipGetErrorString(hipGetLastError()));
-  if (w63 && (rc = tspn::wino63_input_transform(d->feats, NT, T, D, ws + L.vt, L.vt_bytes, stream,
-                                                hot ? hot + TSPN_CONV_CHECK_HOT_OFFSET / 8 : nullptr)))
+  uint64_t* hot_slots = hot ? hot + TSPN_CONV_CHECK_HOT_OFFSET / 8 : nullptr;
+  if (f16x3) {
+    if ((rc = tspn::wino63_f16x3_input_transform(d->feats, NT, T, D, 2 * C, ws + L.vt, L.vt_bytes, stream, hot_slots)))
+      return rc;
+  } else if (w63 && (rc = tspn::wino63_input_transform(d->feats, NT, T, D, ws + L.vt, L.vt_bytes, stream, hot_slots))) {
     return rc;
+  }
   if (d->ev_conv_begin) (void)hipEventRecord(static_cast<hipEvent_t>(d->ev_conv_begin), s);
-  if (w63)
+  if (f16x3)
+    rc = tspn::wino63_f16x3_contract(ws + L.vt, L.vt_bytes, NT, T, D, reinterpret_cast<const int16_t*>(d->conv_packed), 2 * C,
+                                     bias2, 0, y, ldy, stream);
+  else if (w63)
     rc = tspn::wino63_contract(ws + L.vt, NT, T, D, d->conv_packed, 2 * C, bias2, 0, y, ldy, stream);
   else
     rc = tc ? tspn::conv3_tc_direct(d->feats, NT, T, D, d->conv_packed, 2 * C, bias2, 0, y, ldy, stream)

@@ -438,7 +438,438 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
   }
 }
 
+// ================================================================================================================
+// Split-fp16 form (TSPN_CONV_WINOGRAD63_F16X3): the same F(6,3) algorithm, its 8 point GEMMs on the f16 MFMA
+// (v_mfma_f32_32x32x16_f16, 16x the FLOP per clock of the fp32 one).  Every operand is split into two fp16 parts,
+// x ~ hi + lo (11 + 11 significand bits), and a product is x.w ~ hi_x.hi_w + hi_x.lo_w + lo_x.hi_w (Ootomo & Yokota
+// 2022): three f16 MFMAs, each product exact in fp32, one fp32 accumulator.  fp16's exponent range is handled by
+// power-of-two scales, exact and free to undo: one per (point, output row) of the weights, one per (point, sextet)
+// column of the transformed input, chosen so that the largest |value| of the row / column lies in [2^14, 2^15).  The
+// unscale 2^-(e_row + e_col) is applied to each point's accumulator before the inverse transform.  Measured accuracy
+// in tests/test_gpu_wino63_f16x3.py, the MFMA's rounding behaviour in tools/probes/mfma_f16_split_probe.hip.
+//
+// Split weights, int16 [8 j][2 Cp/8 + 1][Mp][8]: per point j the hi parts [Cp/8][Mp][8 ch] (an A fragment = 16 bytes
+// of one row), the lo parts in the same layout, then one 16-byte slot per row whose first int32 is e_row.
+// Split input (workspace): fp16 [8 j][2 hl][Cin/8][nsp2][8 ch], then int32 e_col [8 j][nsp2] (nsp2: sextets padded
+// to the 256-sextet tile), then the parking area of the contraction.
+constexpr int F_BM = 256, F_BN = 256;          // contraction tile: output rows x sextets
+constexpr int F_THREADS = 512;                 // 8 waves (2 per SIMD), wave tile 128 rows x 64 sextets
+constexpr int F_ST = 4 * 2 * 256 * 16;         // one k-step (16 channels) of Wh, Wl, Vh, Vl: 32 KB
+constexpr int F_NST = 4;                       // ring of stages, filled three k-steps ahead by LDS-DMA
+constexpr size_t F_SMEM = (size_t)F_NST * F_ST;
+constexpr size_t F_SMEM_ALL = F_SMEM + 2 * 256 * sizeof(int);   // + the exponent table of the unscale
+constexpr size_t F_PARK_PER_TILE = (size_t)7 * F_THREADS * 128 * sizeof(float);   // points 0..6 of a tile, fp32
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// power-of-two exponent e with max * 2^e in [2^14, 2^15); 0 for a zero or non-finite maximum (a non-finite value then
+// stays non-finite through the split, and so does every output it reaches)
+__device__ __forceinline__ int split_exponent(double mx) {
+  if (!(mx > 0.0) || !(mx <= 1.7976931348623157e308)) return 0;
+  int k;
+  (void)frexp(mx, &k);           // mx = f 2^k, f in [0.5, 1)
+  return 15 - k;
+}
+
+__device__ __forceinline__ double wino63_u(int j, double g0, double g1, double g2) {
+  switch (j) {
+    case 0: return g0;
+    case 1: return -2.0 / 9.0 * (g0 + g1 + g2);
+    case 2: return -2.0 / 9.0 * (g0 - g1 + g2);
+    case 3: return g0 / 90.0 + g1 / 45.0 + 2.0 * g2 / 45.0;
+    case 4: return g0 / 90.0 - g1 / 45.0 + 2.0 * g2 / 45.0;
+    case 5: return (32.0 * g0 + 16.0 * g1 + 8.0 * g2) / 45.0;
+    case 6: return (32.0 * g0 - 16.0 * g1 + 8.0 * g2) / 45.0;
+    default: return g2;
+  }
+}
+
+// Split weights: one thread per (point j, row m) -- the row's scale needs all of its Cp channels.  Runs once per weight
+// version.  U_j = G g in float64 from the raw taps, scaled exactly, hi = fp16(u), lo = fp16(u - hi) (u - hi exact in
+// float64).
+__global__ void pack_wino63_frag_kernel(const float* __restrict__ W, int64_t M, int64_t Cin, int64_t split,
+                                        int16_t* __restrict__ out) {
+  const int64_t Mp = split ? 2 * M : M, Cp = split ? split : Cin;
+  const int64_t ncg = Cp / 8;
+  const int64_t o = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (o >= NJ * Mp) return;
+  const int j = (int)(o / Mp);
+  const int64_t m = o - j * Mp;
+  const float* g = (split && m >= M) ? W + ((m - M) * Cin + split) * 3 : W + (m * Cin) * 3;
+  double mx = 0.0;
+  for (int64_t c = 0; c < Cp; ++c) {
+    const double u = fabs(wino63_u(j, g[3 * c], g[3 * c + 1], g[3 * c + 2]));
+    mx = (u > mx || u != u) ? u : mx;      // NaN-propagating
+  }
+  const int e = split_exponent(mx);
+  int16_t* pj = out + (int64_t)j * (2 * ncg + 1) * Mp * 8;
+  for (int64_t cg = 0; cg < ncg; ++cg) {
+    f16x8 hi, lo;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int64_t c = 8 * cg + i;
+      const double u = ldexp(wino63_u(j, g[3 * c], g[3 * c + 1], g[3 * c + 2]), e);
+      const _Float16 h = (_Float16)(float)u;
+      hi[i] = h;
+      lo[i] = (_Float16)(float)(u - (double)(float)h);
+    }
+    *reinterpret_cast<f16x8*>(pj + (cg * Mp + m) * 8) = hi;
+    *reinterpret_cast<f16x8*>(pj + ((ncg + cg) * Mp + m) * 8) = lo;
+  }
+  *reinterpret_cast<int4*>(pj + (2 * ncg * Mp + m) * 8) = int4{e, 0, 0, 0};   // the whole slot: no undefined bytes
+}
+
+// Split input transform: V = B^T d exactly as the fp32 form computes it, then one scale per (sextet, point) column over
+// ALL Cin channels, so a workgroup owns whole columns: 8 sextets x all channels; thread = (sextet s = tid & 7, channel
+// group slot tid >> 3 of 32), 8 channels per group.  Pass 1 takes the column maxima (and the guard's hot-sextet key),
+// pass 2 recomputes V (the x lines are in L2 by then) and writes the hi / lo halves: for each (j, channel group) the
+// 8 sextets of the workgroup are one 128-byte run.
+__global__ __launch_bounds__(256) void wino63_input_transform_kernel(
+    const float* __restrict__ x, _Float16* __restrict__ Vh, int* __restrict__ Ve, int T, int Cin, int nq,
+    int64_t nsext, int64_t nsp2, int64_t ncols, unsigned long long* __restrict__ hot) {
+  __shared__ float red[4][8][NJ];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int s = tid & 7, cgs = tid >> 3;
+  const int64_t S = (int64_t)blockIdx.x * 8 + s;        // < nsp2 by construction of the grid
+  const bool ok = S < nsext;
+  const int64_t b = ok ? S / nq : 0;
+  const int q = ok ? (int)(S - b * nq) : 0;
+  const int ncg = Cin >> 3;
+  auto transform = [&](int cg, f32x4 (&V)[2][8], bool want_max, float& xmax) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      f32x4 d[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int t = 6 * q + i - 1;
+        int64_t n = b * T + t;
+        n = n < 0 ? 0 : (n < ncols ? n : ncols - 1);
+        const f32x4 v = *reinterpret_cast<const f32x4*>(x + n * Cin + 8 * cg + 4 * h);
+        d[i] = (ok && t >= 0 && t < T) ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+      }
+      if (want_max) {
+#pragma unroll
+        for (int i = 1; i < 7; ++i)
+          xmax = __builtin_elementwise_maximum(
+              __builtin_elementwise_maximum(xmax, __builtin_elementwise_maximum(fabsf(d[i][0]), fabsf(d[i][1]))),
+              __builtin_elementwise_maximum(fabsf(d[i][2]), fabsf(d[i][3])));
+      }
+      V[h][0] = d[0] - d[6] + 5.25f * (d[4] - d[2]);
+      V[h][7] = d[7] - d[1] + 5.25f * (d[3] - d[5]);
+      {
+        const f32x4 t1 = d[2] + d[6] - 4.25f * d[4], t2 = d[1] + d[5] - 4.25f * d[3];
+        V[h][1] = t1 + t2;
+        V[h][2] = t1 - t2;
+      }
+      {
+        const f32x4 t1 = d[6] + 0.25f * d[2] - 1.25f * d[4], t2 = 0.5f * d[1] - 2.5f * d[3] + 2.f * d[5];
+        V[h][3] = t1 + t2;
+        V[h][4] = t1 - t2;
+      }
+      {
+        const f32x4 t1 = d[6] + 4.f * (d[2] - 1.25f * d[4]), t2 = 2.f * d[1] - 2.5f * d[3] + 0.5f * d[5];
+        V[h][5] = t1 + t2;
+        V[h][6] = t1 - t2;
+      }
+    }
+  };
+  // ---- pass 1: column maxima (NaN-propagating), hot-sextet key
+  float cmax[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) cmax[j] = 0.f;
+  float xm = 0.f;
+  for (int cg = cgs; cg < ncg; cg += 32) {
+    f32x4 V[2][8];
+    transform(cg, V, hot != nullptr, xm);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j)
+#pragma unroll
+      for (int h = 0; h < 2; ++h)
+        cmax[j] = __builtin_elementwise_maximum(
+            __builtin_elementwise_maximum(cmax[j], __builtin_elementwise_maximum(fabsf(V[h][j][0]), fabsf(V[h][j][1]))),
+            __builtin_elementwise_maximum(fabsf(V[h][j][2]), fabsf(V[h][j][3])));
+  }
+  if (hot) {                                                       // uniform; as in the fp32 transform
+    unsigned long long key = ((unsigned long long)__float_as_uint(xm) << 32) | (unsigned)(ok ? S : 0);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const unsigned long long other = __shfl_xor(key, o, 64);
+      key = other > key ? other : key;
+    }
+    if (lane == 0)
+      __hip_atomic_fetch_max(hot + 32 * ((blockIdx.x * 4 + wave) & (TSPN_CONV_CHECK_HOT_SLOTS - 1)), key,
+                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    float m = cmax[j];
+#pragma unroll
+    for (int o = 8; o < 64; o <<= 1) m = __builtin_elementwise_maximum(m, __shfl_xor(m, o, 64));
+    if (lane < 8) red[wave][lane][j] = m;
+  }
+  __syncthreads();
+  int ecol[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    const float m = __builtin_elementwise_maximum(__builtin_elementwise_maximum(red[0][s][j], red[1][s][j]),
+                                                  __builtin_elementwise_maximum(red[2][s][j], red[3][s][j]));
+    ecol[j] = split_exponent((double)m);
+  }
+  if (cgs == 0) {
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) Ve[(int64_t)j * nsp2 + S] = ecol[j];
+  }
+  // ---- pass 2: scaled hi / lo halves
+  for (int cg = cgs; cg < ncg; cg += 32) {
+    f32x4 V[2][8];
+    transform(cg, V, false, xm);
+#pragma unroll
+    for (int j = 0; j < NJ; ++j) {
+      f16x8 hi, lo;
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const float u = ldexpf(V[i >> 2][j][i & 3], ecol[j]);
+        const _Float16 h = (_Float16)u;
+        hi[i] = h;
+        lo[i] = (_Float16)(u - (float)h);     // exact in fp32
+      }
+      _Float16* dst = Vh + (((int64_t)j * 2 * ncg + cg) * nsp2 + S) * 8;
+      *reinterpret_cast<f16x8*>(dst) = hi;
+      *reinterpret_cast<f16x8*>(dst + (int64_t)ncg * nsp2 * 8) = lo;
+    }
+  }
+}
+
+template <int N>
+__device__ __forceinline__ void wait_vm() {
+  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// Split contraction.  Workgroup = 256 rows x 256 sextets, ALL 8 points one after another: per point a GEMM over the
+// Cin channels, k-step = 16 channels, acc += Wh.Vh + Wh.Vl + Wl.Vh (24 MFMAs per wave and k-step).  The operands of a
+// k-step (Wh, Wl, Vh, Vl: 4 x 8 KB, [2 channel groups][256][16 B], a lane's fragment = one ds_read_b128) go into a ring
+// of 4 LDS stages by LDS-DMA three k-steps ahead, with a counted vmcnt and one bare s_barrier per k-step (the ring of
+// conv3_bf16_big_kernel).  At the end of a point the accumulator is unscaled and, for points 0..6, parked in the
+// workspace (each lane reads back exactly what it wrote: no synchronisation, deterministic); after point 7 the lane
+// reads its 7 parked tiles back, applies the inverse transform and the bias and writes y as the fp32 form does.
+__global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
+    const _Float16* __restrict__ Vh, const int* __restrict__ Ve, const int16_t* __restrict__ Wp,
+    const float* __restrict__ bias, float* __restrict__ y, float* __restrict__ park, int Cin, int T, int M, int nq,
+    int64_t nsext, int64_t nsp2, int tiles_m, int tiles_n, int relu, int ldy, int GM, int vec2) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+
+  const int nwg = gridDim.x;
+  const int bid = blockIdx.x;
+  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
+  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int group_sz = GM * tiles_n;
+  const int group = wg / group_sz;
+  const int first_m = group * GM;
+  const int gm = min(GM, tiles_m - first_m);
+  const int in_group = wg - group * group_sz;
+  const int tile_m = first_m + in_group % gm;
+  const int tile_n = in_group / gm;
+  const int m0 = tile_m * F_BM;
+  const int64_t S0 = (int64_t)tile_n * F_BN;
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int wm = wave >> 2, wn = wave & 3;
+  const int li = lane & 31, kh = lane >> 5;
+  const int ncg = Cin >> 3, nk = Cin >> 4;
+  const int G = NJ * nk;                             // k-steps of the whole workgroup (8 points)
+
+  // DMA pieces: piece p = 4 wave + i of a stage (1 KB each): region p >> 3 (Wh, Wl, Vh, Vl), channel group (p >> 2) & 1,
+  // rows / sextets 64 (p & 3) + lane.  Element offsets at k-step 0 of point 0, and the strides per k-step / point.
+  const int16_t* src[4];
+  int64_t kstride[4], jstride[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int p = 4 * wave + i;
+    const int region = p >> 3, cgi = (p >> 2) & 1, r = 64 * (p & 3) + lane;
+    if (region < 2) {
+      src[i] = Wp + (((int64_t)region * ncg + cgi) * M + m0 + r) * 8;
+      kstride[i] = (int64_t)2 * M * 8;
+      jstride[i] = (int64_t)(2 * ncg + 1) * M * 8;
+    } else {
+      src[i] = reinterpret_cast<const int16_t*>(Vh) + (((int64_t)(region - 2) * ncg + cgi) * nsp2 + S0 + r) * 8;
+      kstride[i] = (int64_t)2 * nsp2 * 8;
+      jstride[i] = (int64_t)2 * ncg * nsp2 * 8;
+    }
+  }
+  auto issue = [&](int g) {                          // k-step g (point g / nk) into ring stage g & 3
+    const int j = g / nk, k = g - j * nk;
+    char* dst = smem_raw + (g & 3) * F_ST + (4 * wave) * 1024;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[i] + j * jstride[i] + k * kstride[i]),
+                                       (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
+  };
+
+  f32x16 acc[4][2];
+#pragma unroll
+  for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
+
+  // this lane's parking slots: [tile][point 0..6][32 f32x4 registers][512 lanes] (one 1 KB store per wave and register)
+  float* my_park = park + (int64_t)(tile_m * tiles_n + tile_n) * (F_PARK_PER_TILE / sizeof(float)) + tid * 4;
+  // unscale the accumulator of point j: 2^-(e_row + e_col), exact.  The tile's 256 row and 256 column exponents go
+  // through LDS behind the ring (one load per thread instead of 64 per lane).
+  int* etab = reinterpret_cast<int*>(smem_raw + F_SMEM);        // [256 rows][256 columns]
+  auto unscale = [&](int j) {
+    if (tid < F_BM)
+      etab[tid] = reinterpret_cast<const int*>(Wp + (int64_t)j * (2 * ncg + 1) * M * 8 + (int64_t)2 * ncg * M * 8)[(int64_t)(m0 + tid) * 4];
+    else
+      etab[tid] = Ve[(int64_t)j * nsp2 + S0 + tid - F_BM];
+    __syncthreads();
+    int ec[2];
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) ec[ni] = etab[F_BM + wn * 64 + ni * 32 + li];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int r = etab[wm * 128 + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh];
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) acc[mi][ni][e] = ldexpf(acc[mi][ni][e], -(r + ec[ni]));
+      }
+  };
+
+  issue(0);
+  if (G > 1) issue(1);
+  if (G > 2) issue(2);
+  for (int g = 0; g < G; ++g) {
+    if (g + 2 < G) wait_vm<8>(); else if (g + 1 < G) wait_vm<4>(); else wait_vm<0>();
+    __builtin_amdgcn_sched_barrier(0);
+    __builtin_amdgcn_s_barrier();                   // stage g landed for every wave; stage g - 1 is read out
+    __builtin_amdgcn_sched_barrier(0);
+    if (g + 3 < G) issue(g + 3);
+    __builtin_amdgcn_sched_barrier(0);
+    const char* st = smem_raw + (g & 3) * F_ST;
+    f16x8 ah[4], al[4], bh[2], bl[2];
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+      const int off = (kh * 256 + wm * 128 + mi * 32 + li) * 16;
+      ah[mi] = *reinterpret_cast<const f16x8*>(st + off);
+      al[mi] = *reinterpret_cast<const f16x8*>(st + 8192 + off);
+    }
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) {
+      const int off = (kh * 256 + wn * 64 + ni * 32 + li) * 16;
+      bh[ni] = *reinterpret_cast<const f16x8*>(st + 16384 + off);
+      bl[ni] = *reinterpret_cast<const f16x8*>(st + 24576 + off);
+    }
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mi], bh[ni], acc[mi][ni], 0, 0, 0);
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < 4; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
+    __builtin_amdgcn_sched_barrier(0);
+    if (g % nk == nk - 1) {
+      const int j = g / nk;
+      unscale(j);
+      if (j < NJ - 1) {
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+          for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int eq = 0; eq < 4; ++eq) {
+              const f32x4 v = {acc[mi][ni][4 * eq], acc[mi][ni][4 * eq + 1], acc[mi][ni][4 * eq + 2], acc[mi][ni][4 * eq + 3]};
+              *reinterpret_cast<f32x4*>(my_park + ((int64_t)j * 32 + (mi * 2 + ni) * 4 + eq) * F_THREADS * 4) = v;
+#pragma unroll
+              for (int e = 0; e < 4; ++e) acc[mi][ni][4 * eq + e] = 0.f;
+            }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+
+  // ---- inverse transform + bias + store: acc holds M7; M0..M6 come back from the parking area (this lane's own
+  // stores, complete before they are read)
+  wait_vm<0>();
+#pragma unroll
+  for (int ni = 0; ni < 2; ++ni) {
+    const int64_t Sx = S0 + wn * 64 + ni * 32 + li;
+    const bool col_ok = Sx < nsext;
+    const int64_t b = col_ok ? Sx / nq : 0;
+    const int q = col_ok ? (int)(Sx - b * nq) : 0;
+    const int t = 6 * q;
+    float* ycol = y + (b * M) * (int64_t)ldy + t;
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+      for (int eq = 0; eq < 4; ++eq) {
+        f32x4 P[NJ - 1];
+#pragma unroll
+        for (int j = 0; j < NJ - 1; ++j)
+          P[j] = *reinterpret_cast<const f32x4*>(my_park + ((int64_t)j * 32 + (mi * 2 + ni) * 4 + eq) * F_THREADS * 4);
+        if (!col_ok) continue;
+#pragma unroll
+        for (int e4 = 0; e4 < 4; ++e4) {
+          const int e = 4 * eq + e4;
+          const int m = m0 + wm * 128 + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
+          const float p12 = P[1][e4] + P[2][e4], m12 = P[1][e4] - P[2][e4];
+          const float p34 = P[3][e4] + P[4][e4], m34 = P[3][e4] - P[4][e4];
+          const float p56 = P[5][e4] + P[6][e4], m56 = P[5][e4] - P[6][e4];
+          float o[6];
+          o[0] = P[0][e4] + p12 + p34 + p56;
+          o[1] = m12 + 2.f * m34 + 0.5f * m56;
+          o[2] = p12 + 4.f * p34 + 0.25f * p56;
+          o[3] = m12 + 8.f * m34 + 0.125f * m56;
+          o[4] = p12 + 16.f * p34 + 0.0625f * p56;
+          o[5] = m12 + 32.f * m34 + 0.03125f * m56 + acc[mi][ni][e];
+          if (bias != nullptr) {
+            const float bb = bias[m];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) o[i] += bb;
+          }
+          if (relu) {
+#pragma unroll
+            for (int i = 0; i < 6; ++i) o[i] = tspn::relu_f32(o[i]);
+          }
+          float* dst = ycol + (int64_t)m * ldy;
+          if (vec2) {
+            *reinterpret_cast<f32x2*>(dst) = f32x2{o[0], o[1]};
+            *reinterpret_cast<f32x2*>(dst + 2) = f32x2{o[2], o[3]};
+            *reinterpret_cast<f32x2*>(dst + 4) = f32x2{o[4], o[5]};
+          } else {
+#pragma unroll
+            for (int i = 0; i < 6; ++i)
+              if (t + i < T) dst[i] = o[i];
+          }
+        }
+      }
+  }
+}
+
 int64_t padded_sextets(int64_t B, int64_t T) { return tspn::ceil_div(B * tspn::ceil_div(T, 6), SWG) * SWG; }
+int64_t padded_sextets_f16x3(int64_t B, int64_t T) { return tspn::ceil_div(B * tspn::ceil_div(T, 6), F_BN) * F_BN; }
+
+// workspace of the split form: [split V | column exponents | parking area], each 256-byte aligned
+struct F16x3Layout {
+  size_t v, e, park, total;
+};
+F16x3Layout f16x3_layout(int64_t B, int64_t T, int64_t Cin, int64_t M) {
+  F16x3Layout L{};
+  const size_t nsp2 = (size_t)padded_sextets_f16x3(B, T);
+  L.v = 0;
+  L.e = tspn::align_up((size_t)NJ * 2 * Cin * nsp2 * sizeof(_Float16), 256);
+  L.park = L.e + tspn::align_up((size_t)NJ * nsp2 * sizeof(int), 256);
+  L.total = L.park + (size_t)tspn::ceil_div(M, F_BM) * (nsp2 / F_BN) * F_PARK_PER_TILE;
+  return L;
+}
 
 int check_common(const char* what, int64_t B, int64_t T, int64_t Cin, int64_t M, int64_t ldy) {
   TSPN_REQUIRE(B >= 0 && Cin > 0 && T > 0 && M > 0 && ldy >= T && ldy < (1 << 24), TSPN_EINVAL,
@@ -553,4 +984,107 @@ extern "C" int tspn_conv3_tc_wino63_f32(const float* x, int64_t B, int64_t T, in
                                         int64_t M, const float* bias, int relu, float* y, void* workspace,
                                         size_t workspace_bytes, void* stream) {
   return tspn::conv3_tc_wino63(x, B, T, Cin, frag, M, bias, relu, y, T, workspace, workspace_bytes, stream);
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Split-fp16 form (TSPN_CONV_WINOGRAD63_F16X3)
+bool tspn::wino63_f16x3_supported(int64_t Cin, int64_t M) {
+  return Cin > 0 && M > 0 && Cin % 32 == 0 && M % F_BM == 0 && Cin < (1 << 24) && M < (1 << 24);
+}
+
+size_t tspn::wino63_f16x3_workspace_bytes(int64_t B, int64_t T, int64_t Cin, int64_t M) {
+  if (B <= 0 || T <= 0 || Cin <= 0 || M <= 0) return 0;
+  return f16x3_layout(B, T, Cin, M).total;
+}
+
+extern "C" size_t tspn_conv3_tc_wino63_f16x3_workspace_bytes(int64_t B, int64_t T, int64_t Cin, int64_t M) {
+  return tspn::wino63_f16x3_workspace_bytes(B, T, Cin, M);
+}
+
+extern "C" size_t tspn_pack_conv3_wino63_f16x3_elements(int64_t M, int64_t Cin, int64_t split) {
+  if (M <= 0 || Cin <= 0 || split < 0 || (split && Cin != 2 * split)) return 0;
+  const int64_t Mp = split ? 2 * M : M, Cp = split ? split : Cin;
+  return (size_t)NJ * (2 * (Cp / 8) + 1) * Mp * 8;
+}
+
+extern "C" int tspn_pack_conv3_wino63_f16x3(const float* W, int64_t M, int64_t Cin, int64_t split, int16_t* packed,
+                                            void* stream) {
+  const char* what = "tspn_pack_conv3_wino63_f16x3";
+  TSPN_REQUIRE(W && packed, TSPN_EINVAL, "%s: null pointer", what);
+  TSPN_REQUIRE(M > 0 && Cin > 0 && split >= 0, TSPN_EINVAL, "%s: bad sizes", what);
+  TSPN_REQUIRE(split == 0 || Cin == 2 * split, TSPN_EINVAL, "%s: split=%lld requires Cin == 2*split (Cin=%lld)", what,
+               (long long)split, (long long)Cin);
+  TSPN_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, TSPN_EINVAL, "%s: packed must be 16-byte aligned", what);
+  const int64_t Mp = split ? 2 * M : M, Cp = split ? split : Cin;
+  TSPN_REQUIRE(tspn::wino63_f16x3_supported(Cp, Mp), TSPN_EUNSUPPORTED,
+               "%s: needs (packed) Cin %% 32 == 0 and M %% 256 == 0 (Cin=%lld M=%lld)", what, (long long)Cp, (long long)Mp);
+  void (*kern)(const float*, int64_t, int64_t, int64_t, int16_t*) = pack_wino63_frag_kernel;
+  hipLaunchKernelGGL(kern, dim3((unsigned)tspn::ceil_div(NJ * Mp, 256)), dim3(256), 0, TSPN_STREAM(stream), W, M, Cin,
+                     split, packed);
+  return tspn::check_launch(what);
+}
+
+// step 1 of the split form: V = B^T d, split and scaled, into the workspace (+ the guard's hot-sextet report)
+int tspn::wino63_f16x3_input_transform(const float* x, int64_t B, int64_t T, int64_t Cin, int64_t M, void* workspace,
+                                       size_t workspace_bytes, void* stream, uint64_t* hot) {
+  const char* what = "tspn_conv3_tc_wino63_f16x3(input transform)";
+  if (int rc = check_common(what, B, T, Cin, 32, T)) return rc;
+  TSPN_REQUIRE(tspn::wino63_f16x3_supported(Cin, M), TSPN_EUNSUPPORTED,
+               "%s: needs Cin %% 32 == 0 and M %% 256 == 0 (Cin=%lld M=%lld)", what, (long long)Cin, (long long)M);
+  if (B == 0) return TSPN_OK;
+  TSPN_REQUIRE(x && (reinterpret_cast<uintptr_t>(x) & 15) == 0, TSPN_EINVAL, "%s: x must be a 16-byte aligned pointer", what);
+  const F16x3Layout L = f16x3_layout(B, T, Cin, M);
+  TSPN_REQUIRE(workspace && workspace_bytes >= L.total, TSPN_EWORKSPACE, "%s: workspace %zu < %zu bytes", what,
+               workspace_bytes, L.total);
+  TSPN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, TSPN_EINVAL, "%s: workspace must be 256-byte aligned",
+               what);
+  const int64_t nq = tspn::ceil_div(T, 6);
+  const int64_t nsext = B * nq, nsp2 = padded_sextets_f16x3(B, T);
+  TSPN_REQUIRE(nsp2 / 8 < (1LL << 31), TSPN_EUNSUPPORTED, "%s: grid too large", what);
+  char* ws = static_cast<char*>(workspace);
+  void (*kern)(const float*, _Float16*, int*, int, int, int, int64_t, int64_t, int64_t, unsigned long long*) =
+      wino63_input_transform_kernel;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(nsp2 / 8)), dim3(256), 0, TSPN_STREAM(stream), x,
+                     reinterpret_cast<_Float16*>(ws + L.v), reinterpret_cast<int*>(ws + L.e), (int)T, (int)Cin, (int)nq,
+                     nsext, nsp2, B * T, reinterpret_cast<unsigned long long*>(hot));
+  return tspn::check_launch(what);
+}
+
+// step 2 of the split form: the f16 MFMA contraction + inverse transform
+int tspn::wino63_f16x3_contract(void* workspace, size_t workspace_bytes, int64_t B, int64_t T, int64_t Cin,
+                                const int16_t* packed, int64_t M, const float* bias, int relu, float* y, int64_t ldy,
+                                void* stream) {
+  const char* what = "tspn_conv3_tc_wino63_f16x3";
+  if (int rc = check_common(what, B, T, Cin, M, ldy)) return rc;
+  TSPN_REQUIRE(tspn::wino63_f16x3_supported(Cin, M), TSPN_EUNSUPPORTED,
+               "%s: needs Cin %% 32 == 0 and M %% 256 == 0 (Cin=%lld M=%lld)", what, (long long)Cin, (long long)M);
+  if (B == 0) return TSPN_OK;
+  TSPN_REQUIRE(workspace && packed && y, TSPN_EINVAL, "%s: null pointer", what);
+  TSPN_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0,
+               TSPN_EUNSUPPORTED, "%s: packed weights must be 16-byte aligned", what);
+  const F16x3Layout L = f16x3_layout(B, T, Cin, M);
+  TSPN_REQUIRE(workspace_bytes >= L.total, TSPN_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes,
+               L.total);
+  const int64_t nq = tspn::ceil_div(T, 6);
+  const int64_t nsext = B * nq, nsp2 = padded_sextets_f16x3(B, T);
+  const int64_t tiles_m = M / F_BM, tiles_n = nsp2 / F_BN;
+  TSPN_REQUIRE(tiles_m * tiles_n < (1LL << 31), TSPN_EUNSUPPORTED, "%s: grid too large", what);
+  const int vec2 = (ldy % 2 == 0) && (ldy >= 6 * nq) && ((reinterpret_cast<uintptr_t>(y) & 7) == 0);
+  char* ws = static_cast<char*>(workspace);
+  static tspn::LdsLimit lds;     // 128 KB of dynamic LDS
+  void (*kern)(const _Float16*, const int*, const int16_t*, const float*, float*, float*, int, int, int, int, int64_t,
+               int64_t, int, int, int, int, int, int) = conv3_wino63_kernel;
+  if (int rc = lds.ensure(reinterpret_cast<const void*>(kern), F_SMEM_ALL, what)) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(F_THREADS), F_SMEM_ALL, TSPN_STREAM(stream),
+                     reinterpret_cast<const _Float16*>(ws + L.v), reinterpret_cast<const int*>(ws + L.e), packed, bias, y,
+                     reinterpret_cast<float*>(ws + L.park), (int)Cin, (int)T, (int)M, (int)nq, nsext, nsp2, (int)tiles_m,
+                     (int)tiles_n, relu, (int)ldy, TSPN_WINO63_GM, vec2);
+  return tspn::check_launch(what);
+}
+
+extern "C" int tspn_conv3_tc_wino63_f16x3(const float* x, int64_t B, int64_t T, int64_t Cin, const int16_t* packed,
+                                          int64_t M, const float* bias, int relu, float* y, void* workspace,
+                                          size_t workspace_bytes, void* stream) {
+  if (int rc = tspn::wino63_f16x3_input_transform(x, B, T, Cin, M, workspace, workspace_bytes, stream)) return rc;
+  return tspn::wino63_f16x3_contract(workspace, workspace_bytes, B, T, Cin, packed, M, bias, relu, y, T, stream);
 }

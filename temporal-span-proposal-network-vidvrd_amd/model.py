@@ -539,6 +539,21 @@ class DPN(nn.Module):
         return self._cache.get("conv_split", (c.weight, c.bias), dev,
                                lambda ts: (ops.pack_conv3(ts[0], split=half), ts[1]))
 
+    def _conv_f16x3(self, dev):
+        """Split-fp16 F(6,3) weights of the factorised pair form (pack_conv3_wino63_f16x3), for the calls the accuracy
+        guard has promoted (BaseModel._winograd).  Its cache key does not start with "conv_split": those are the fp32
+        packings."""
+        c = self.dpn_head.conv
+        half = self.dpn_head.in_channels // 2
+        return self._cache.get("wino63_f16x3", (c.weight, c.bias), dev,
+                               lambda ts: (ops.pack_conv3_wino63_f16x3(ts[0], split=half), ts[1]))
+
+    def _conv_packed(self, dev, algo):
+        """(packed conv weights, bias) for the algorithm BaseModel._conv_algo chose: "f16x3", "wino63" or "direct"."""
+        if algo == "f16x3":
+            return self._conv_f16x3(dev)
+        return self._conv_split(dev, winograd=algo == "wino63")
+
     def _conv_raw(self, dev):
         """conv.weight as it is (fp32, contiguous, on `dev`): what the accuracy guard recomputes outputs from."""
         return self._cache.get("conv_raw", (self.dpn_head.conv.weight,), dev, lambda ts: ts[0])
@@ -821,6 +836,13 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
         self.conv_check_rows = int(getattr(cfg.RELPN.DPN, "CONV_CHECK_ROWS", 128))
         self.conv_fallback = False
         self.conv_err_seen = 0.0     # largest spot-check error this model has read back so far
+        # split-fp16 F(6,3) (TSPN_CONV_WINOGRAD63_F16X3): once CONV_F16X3_AFTER calls have read a guard measurement
+        # <= CONV_TOL from the fp32 F(6,3) calls before them, and the shape passes the split kernels' gate, the calls
+        # from then on run the split form (spot-checked the same way); CONV_F16X3 = False keeps the fp32 form
+        self.conv_f16x3 = bool(getattr(cfg.RELPN.DPN, "CONV_F16X3", True))
+        self.conv_f16x3_after = max(1, int(getattr(cfg.RELPN.DPN, "CONV_F16X3_AFTER", 4)))
+        self.conv_clean_reads = 0    # calls that found a standing clean measurement of the fp32 form
+        self.conv_promoted = False
 
     def forward(self, pair_list, target_list=None):
         if self.training:
@@ -849,6 +871,11 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                 return True
             err = float(words[_abi.STATUS_CONV_ERR:_abi.STATUS_CONV_ERR + 1].view(np.float32)[0])
             self.conv_err_seen = max(self.conv_err_seen, err)
+            if err <= self.conv_tol and int(words[_abi.STATUS_CONV_CHECKS]) > 0 and self.conv_f16x3 and d % 128 == 0:
+                # one more call that finds the fp32 passes before it measured within CONV_TOL; the split form waits for
+                # CONV_F16X3_AFTER of them (a pass's spot check samples one batch: several batches before the switch)
+                self.conv_clean_reads += 1
+                self.conv_promoted = self.conv_clean_reads >= self.conv_f16x3_after
             if not (err <= self.conv_tol):     # a non-finite measurement (+Inf: a NaN / Inf where float64 has none) trips
                 checks = int(words[_abi.STATUS_CONV_CHECKS])
                 words[_abi.STATUS_CONV_ERR] = 0
@@ -864,6 +891,13 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                     "1e-4 absolute meaningless (INTEGRATION.md §3).", RuntimeWarning, stacklevel=3)
                 return False
         return True
+
+    def _conv_algo(self, d, dev):
+        """"f16x3", "wino63" or "direct" for this call (see _winograd; the split form needs D % 128 == 0 here, which
+        keeps the small-D models on the fp32 form)."""
+        if not self._winograd(d, dev):
+            return "direct"
+        return "f16x3" if self.conv_promoted else "wino63"
 
     def _conv_guard(self, dpn, dev, winograd):
         """(raw conv.weight, rows) for the fused pass's spot check, or (None, 0)."""
@@ -1084,10 +1118,12 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                         side.wait_stream(main)     # the geometry launch on the side stream reads this table
                 # temporal conv algorithm: RELPN.DPN.CONV_ALGO = "auto" (Winograd F(6,3) when D % 32 == 0: 4/9 of the
                 # MFMA work; its fp32 error bound is in DESIGN.md §4) or "direct" (the k=3 taps as one implicit GEMM)
-                wino = self._winograd(d, dev)
-                packed, cbias = dpn._conv_split(dev, winograd=wino)
+                algo = self._conv_algo(d, dev)
+                wino = algo != "direct"
+                packed, cbias = dpn._conv_packed(dev, algo)
                 craw, crows = self._conv_guard(dpn, dev, wino)
-                need = ops.fused_workspace_bytes(nm, n, t, d, hb.numel() // 3, cw.shape[0], allp.shape[0])
+                need = ops.fused_workspace_bytes(nm, n, t, d, hb.numel() // 3, cw.shape[0], allp.shape[0],
+                                                 conv_algo=_abi.CONV_WINOGRAD63_F16X3 if algo == "f16x3" else 0)
                 heads, lg = ops.forward_fused(feats, allp, nm, n, packed, cbias, hw, hb, cw, cb,
                                               workspace=self._workspace(dev, need), check_pairs=False,
                                               canonical_pairs=canonical, conv_events=self._conv_events,
@@ -1154,8 +1190,9 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                 lambda ts: tuple(ops.cast_bf16(x.contiguous()).float() for x in ts))
             a3, k_out = hb16.numel(), cw16.shape[0]
         else:
-            wino = self._winograd(d, dev)
-            packed, cbias = dpn._conv_split(dev, winograd=wino)
+            algo = self._conv_algo(d, dev)
+            wino = algo != "direct"
+            packed, cbias = dpn._conv_packed(dev, algo)
             craw, crows = self._conv_guard(dpn, dev, wino)
             a3, k_out = hb.numel(), cw.shape[0]
         chunks = pipe.schedule(nm, self.host_chunk_videos)
@@ -1171,8 +1208,12 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
         # would go back to the caller stream's pool while d2h still reads it)
         geom_dev = torch.empty((nm * per, 8, t), dtype=torch.float32, device=dev) if want_geom else None
         cmax = max(hi - lo for lo, hi in chunks)
-        wsb = ops.fused_bf16_workspace_bytes if bf16 else ops.fused_workspace_bytes
-        ws = self._workspace(dev, wsb(cmax, n, t, d, a3 // 3, k_out, cmax * per))
+        if bf16:
+            need = ops.fused_bf16_workspace_bytes(cmax, n, t, d, a3 // 3, k_out, cmax * per)
+        else:
+            need = ops.fused_workspace_bytes(cmax, n, t, d, a3 // 3, k_out, cmax * per,
+                                             conv_algo=_abi.CONV_WINOGRAD63_F16X3 if algo == "f16x3" else 0)
+        ws = self._workspace(dev, need)
         # the small side inputs go up NOW, while the caller's stream is empty: a blocking .to(device) issued after a
         # pass has been queued would wait for that pass and stall the pipeline
         boxes_dev = _batch_rows([pair_list[i].get_field("tracklet_boxes") for i in members], dev) if want_geom else None

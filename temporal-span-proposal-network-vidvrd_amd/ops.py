@@ -14,7 +14,7 @@ from . import _abi
 
 __all__ = [
     "predicate_head", "feature_preprocess_", "ppn_pair_matrix_topk", "traj_iou", "traj_iou_tail", "pair_index",
-    "pair_gather", "pack_conv3", "conv3", "conv3_tc", "pack_conv3_wino63", "conv3_tc_wino63", "heads", "heads_pairgrid", "temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
+    "pair_gather", "pack_conv3", "conv3", "conv3_tc", "pack_conv3_wino63", "conv3_tc_wino63", "pack_conv3_wino63_f16x3", "conv3_tc_wino63_f16x3", "heads", "heads_pairgrid", "temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
     "forward_fused", "temporal_encoder_heads", "fused_workspace_bytes", "fused_bf16_workspace_bytes", "decode_topk", "decode_spans",
     "cast_bf16", "pack_conv3_bf16", "pack_heads_bf16", "conv3_tc_bf16", "heads_pairgrid_bf16",
     "transpose_cast_bf16", "temporal_encoder_heads_bf16",
@@ -461,6 +461,53 @@ def conv3_tc_wino63(x, frag, bias=None, relu=False, workspace=None):
     return y
 
 
+def wino63_f16x3_dims(packed):
+    """(Cin, M) of a split-fp16 F(6,3) weight tensor (pack_conv3_wino63_f16x3)."""
+    if packed.dim() != 4 or packed.dtype != torch.int16 or packed.shape[0] != 8 or packed.shape[3] != 8 \
+            or packed.shape[1] % 2 != 1:
+        raise ValueError(f"not a split-fp16 F(6,3) weight tensor: {tuple(packed.shape)} {packed.dtype}")
+    return (packed.shape[1] - 1) // 2 * 8, packed.shape[2]
+
+
+def pack_conv3_wino63_f16x3(weight, split=0):
+    """nn.Conv1d weight [M,Cin,3] -> split-fp16 Winograd F(6,3) weights (tspn_pack_conv3_wino63_f16x3; split as in
+    pack_conv3): int16 storage [8 points][2 Cin'/8 + 1][M'][8] = fp16 hi parts, lo parts and one exponent slot per row.
+    Needs Cin' % 32 == 0, M' % 256 == 0."""
+    _dev(weight, "conv weight")
+    if weight.dim() != 3 or weight.shape[2] != 3:
+        raise ValueError("pack_conv3_wino63_f16x3: weight must be [M,Cin,3]")
+    M, Cin, _ = weight.shape
+    Mp, Cp = (2 * M, split) if split else (M, Cin)
+    if Cp % 32 or Mp % 256:
+        raise ValueError(f"pack_conv3_wino63_f16x3: needs Cin % 32 == 0 and M % 256 == 0 (Cin={Cp}, M={Mp})")
+    packed = torch.empty((8, 2 * (Cp // 8) + 1, Mp, 8), dtype=torch.int16, device=weight.device)
+    assert packed.numel() == _abi.lib().tspn_pack_conv3_wino63_f16x3_elements(M, Cin, split)
+    _abi.check(_abi.lib().tspn_pack_conv3_wino63_f16x3(_p(weight), M, Cin, split, _p(packed), _stream()))
+    return packed
+
+
+def conv3_tc_wino63_f16x3(x, packed, bias=None, relu=False, workspace=None):
+    """Split-fp16 Winograd F(6,3) conv3 (tspn_conv3_tc_wino63_f16x3): channels-last x[B,T,Cin] with
+    pack_conv3_wino63_f16x3 weights -> y[B,M,T].  `workspace` (uint8, >= tspn_conv3_tc_wino63_f16x3_workspace_bytes)."""
+    _dev(x, "x")
+    if bias is not None:
+        _dev(bias, "bias")
+    B, T, Cin = x.shape
+    cin_w, M = wino63_f16x3_dims(packed)
+    if cin_w != Cin:
+        raise ValueError(f"conv3_tc_wino63_f16x3: weights are for Cin={cin_w}, x has Cin={Cin}")
+    l = _abi.lib()
+    need = l.tspn_conv3_tc_wino63_f16x3_workspace_bytes(B, T, Cin, M)
+    if workspace is None:
+        workspace = _ws(need, x.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"conv3_tc_wino63_f16x3: workspace too small ({workspace.numel()} < {need})")
+    y = torch.empty((B, M, T), dtype=torch.float32, device=x.device)
+    _abi.check(l.tspn_conv3_tc_wino63_f16x3(_p(x), B, T, Cin, _p(packed), M, _p(bias), 1 if relu else 0, _p(y),
+                                            _p(workspace), workspace.numel() * workspace.element_size(), _stream()))
+    return y
+
+
 def wino63_set_piece_form(form):
     """0 = buffer-load pieces where the workspace is below 4 GB (default), 1 = 64-bit pointer pieces everywhere
     (tspn_conv3_tc_wino63_set_piece_form).  Returns the previous setting."""
@@ -620,7 +667,8 @@ def decode_spans(heads, sizes, top_k=64, nms_threshold=0.5, pre_nms=1024):
 
 def _fused_desc(feats, pairs, B, N, conv_packed, conv_bias, head_w, head_b, cls_w, cls_b):
     _dev(feats, "tracklet_feats"); _dev(pairs, "pairs", torch.int64)
-    for nm, t in (("conv_packed", conv_packed), ("conv_bias", conv_bias), ("head_w", head_w),
+    _dev(conv_packed, "conv_packed", torch.int16 if conv_packed.dtype == torch.int16 else torch.float32)
+    for nm, t in (("conv_bias", conv_bias), ("head_w", head_w),
                   ("head_b", head_b), ("cls_w", cls_w), ("cls_b", cls_b)):
         _dev(t, nm)
     NT, T, D = feats.shape
@@ -630,11 +678,15 @@ def _fused_desc(feats, pairs, B, N, conv_packed, conv_bias, head_w, head_b, cls_
     H = head_w.shape[0]
     if H % 3 or head_w.shape[1] != C or head_b.shape != (H,):
         raise ValueError("forward_fused: head_w must be [3A, 2D]")
-    w63 = conv_packed.dim() == 5     # fragment-major Winograd F(6,3) weights (pack_conv3_wino63); else direct taps
+    f16x3 = conv_packed.dtype == torch.int16   # split-fp16 F(6,3) weights (pack_conv3_wino63_f16x3)
+    w63 = conv_packed.dim() == 5 and not f16x3     # fragment-major Winograd F(6,3) weights (pack_conv3_wino63); else direct taps
+    if f16x3 and wino63_f16x3_dims(conv_packed) != (D, 2 * C):
+        raise ValueError(f"forward_fused: split-fp16 F(6,3) conv weights are for (Cin, M) = "
+                         f"{wino63_f16x3_dims(conv_packed)}, expected ({D}, {2 * C})")
     if w63 and wino63_frag_dims(conv_packed) != (D, 2 * C):
         raise ValueError(f"forward_fused: Winograd F(6,3) conv weights are for (Cin, M) = "
                          f"{wino63_frag_dims(conv_packed)}, expected ({D}, {2 * C})")
-    if (not w63 and tuple(conv_packed.shape) != (3, D, 2 * C)) or conv_bias.shape != (C,):
+    if (not w63 and not f16x3 and tuple(conv_packed.shape) != (3, D, 2 * C)) or conv_bias.shape != (C,):
         raise ValueError(f"forward_fused: conv_packed must be pack_conv3(conv.weight, split=D) = [3, D={D}, 4D={2 * C}] "
                          "or pack_conv3_wino63(conv.weight, split=D)")
     if cls_w.dim() != 2 or cls_w.shape[1] != C or cls_b.shape != (cls_w.shape[0],):
@@ -644,15 +696,19 @@ def _fused_desc(feats, pairs, B, N, conv_packed, conv_bias, head_w, head_b, cls_
     d.A, d.K = H // 3, cls_w.shape[0]
     d.feats, d.pairs, d.P = feats.data_ptr(), pairs.data_ptr(), pairs.shape[0]
     d.conv_packed, d.conv_bias = conv_packed.data_ptr(), conv_bias.data_ptr()
-    d.conv_algo = _abi.CONV_WINOGRAD63 if w63 else _abi.CONV_DIRECT   # the packing is the choice of kernel
+    # the packing is the choice of kernel
+    d.conv_algo = _abi.CONV_WINOGRAD63_F16X3 if f16x3 else _abi.CONV_WINOGRAD63 if w63 else _abi.CONV_DIRECT
     d.head_w, d.head_b = head_w.data_ptr(), head_b.data_ptr()
     d.cls_w, d.cls_b = cls_w.data_ptr(), cls_b.data_ptr()
     return d
 
 
-def fused_workspace_bytes(B, N, T, D, A, K, P):
+def fused_workspace_bytes(B, N, T, D, A, K, P, conv_algo=0):
+    """Workspace of forward_fused; `conv_algo` = _abi.CONV_WINOGRAD63_F16X3 for split-fp16 F(6,3) weights (the
+    other two algorithms need the same bytes)."""
     d = _abi.FusedDesc()
     d.B, d.N, d.T, d.D, d.A, d.K, d.P = B, N, T, D, A, K, P
+    d.conv_algo = conv_algo
     return _abi.lib().tspn_forward_fused_workspace_bytes(ctypes.byref(d))
 
 
@@ -697,7 +753,7 @@ def forward_fused(feats, pairs, B, N, conv_packed, conv_bias, head_w, head_b, cl
         d.ev_conv_begin, d.ev_conv_end = conv_events[0].cuda_event, conv_events[1].cuda_event
     if logits_event is not None:
         d.ev_logits_ready = logits_event.cuda_event
-    if conv_weight is not None and conv_check > 0 and d.conv_algo == _abi.CONV_WINOGRAD63:
+    if conv_weight is not None and conv_check > 0 and d.conv_algo in (_abi.CONV_WINOGRAD63, _abi.CONV_WINOGRAD63_F16X3):
         _dev(conv_weight, "conv_weight")
         if tuple(conv_weight.shape) != (2 * d.D, 2 * d.D, 3):
             raise ValueError(f"forward_fused: conv_weight must be conv.weight [C, C, 3] with C = {2 * d.D}")
