@@ -675,6 +675,28 @@ int tspn_max_pool_nhwc_bf16(const uint16_t* x, int64_t NB, int64_t H, int64_t W,
 int tspn_stem_pool_bf16(const float* x, int64_t NB, int64_t H, int64_t W, const uint16_t* frag, int64_t Cout,
                         const float* bias, void* workspace, size_t workspace_bytes, uint16_t* out, void* stream);
 
+/* ---- video relation detection evaluation (csrc/eval/tspn_eval.hip) -------
+ * The O(|pred| x |gt| x frames) core of the reference's eval_detection_scores
+ * (lib/evaluation/visual_relation_detection.py:8-36, common.py:65-106), float64, in the reference's operation order
+ * (sequential sums, Python's max / min tie rules), so every vIoU is bit-equal.  Operands (packed by evaluation.py):
+ *   boxes [F,4] float64 (32-byte aligned); traj [T,3] int64 = (first row in boxes, duration begin, end) with
+ *   relation r's subject trajectory at 2r and object trajectory at 2r+1; predictions are relations 0..P-1, in score
+ *   order inside their group; groups [G,5] int64 = (first prediction, #predictions, first ground-truth relation,
+ *   #ground truths, offset of the group's row-major #pred x #gt block in ov); pred_group [P] int32.
+ * tspn_eval_traj_volume_f64: vol[t] = sum over trajectory t's end-begin boxes of (x2-x1+1)*(y2-y1+1), unclamped.
+ * tspn_eval_viou_f64: ov[pair] = min(viou(subjects), viou(objects)) of every (prediction, group ground truth) pair;
+ *   zden[p] = 1 if a pair of prediction p with overlapping durations has a zero vIoU denominator (the reference
+ *   raises ZeroDivisionError there), else 0.
+ * tspn_eval_greedy_match_f64: per group, predictions in order take the undetected ground truth of the largest
+ *   ov >= viou_threshold (lowest index on a tie); hit[p] int8 = 0/1, match[p] int32 = ground-truth index within the
+ *   group or -1.  max_group_gt = the largest #ground truths of a group; above 4096, det_ws (one zeroed byte per
+ *   relation, indexed like the relations) holds the detected flags.  The contents of traj / groups are trusted. */
+int tspn_eval_traj_volume_f64(const double* boxes, const int64_t* traj, int64_t n_traj, double* vol, void* stream);
+int tspn_eval_viou_f64(const double* boxes, const int64_t* traj, const double* vol, const int64_t* groups,
+                       const int32_t* pred_group, int64_t n_pred, double* ov, int32_t* zden, void* stream);
+int tspn_eval_greedy_match_f64(const double* ov, const int64_t* groups, int64_t n_groups, int64_t max_group_gt,
+                               double viou_threshold, uint8_t* det_ws, int8_t* hit, int32_t* match, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,6 +16,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
+CSRC_EVAL = os.path.join(CSRC, "eval")   # evaluation kernels (their variant table: tests/eval_kernel_variants.py)
 LIB_NAME = "libtspn_mi355x.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 ARCH = "gfx950"
@@ -42,11 +43,12 @@ NO_SPILL_KERNELS = ("conv3_wino63_kernel", "heads_pairgrid4_kernel", "heads_pair
 
 
 def sources():
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
+    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC_EVAL, "*.hip")))
 
 
 def _headers():
-    return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(ROOT, "include", "*.h")) + \
+    return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC_EVAL, "*.h")) + \
+        glob.glob(os.path.join(ROOT, "include", "*.h")) + \
         [os.path.abspath(__file__)]
 
 

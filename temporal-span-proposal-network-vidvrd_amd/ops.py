@@ -21,6 +21,7 @@ __all__ = [
     "temporal_mean_bf16", "forward_fused_bf16", "span_predicate", "bottleneck_block_bf16", "bottleneck_block_proj_bf16", "bottleneck_block_res_bf16",
     "proposal_pair_filter", "gather_rows", "wino63_set_piece_form", "conv3_spot_check",
     "pack_conv2d", "pack_conv2d_frag", "conv2d_nhwc", "roi_align_nhwc", "pack_conv2d_frag_bf16", "conv2d_nhwc_bf16", "max_pool_nhwc", "pack_conv2d_frag_cin4", "conv2d_nhwc_cin4", "max_pool_nhwc_bf16", "pack_stem_bf16", "stem_conv_bf16", "stem_pool_bf16", "bottleneck_tail_bf16",
+    "eval_traj_volume", "eval_viou", "eval_greedy_match",
 ]
 
 
@@ -1372,6 +1373,70 @@ def conv2d_nhwc_cin4(x, frag, kernel_size, stride=1, padding=0, bias=None, relu=
                                                     _p(bias), 1 if relu else 0, _p(out), _stream()))
     return out
 
+
+
+# ---- video relation detection evaluation (csrc/eval/tspn_eval.hip; packed by evaluation.py)
+def _eval_traj(boxes, traj):
+    _dev(boxes, "boxes", torch.float64), _dev(traj, "traj", torch.int64)
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or traj.dim() != 2 or traj.shape[1] != 3:
+        raise ValueError(f"eval: boxes [F,4] and traj [T,3] expected, got {tuple(boxes.shape)} and {tuple(traj.shape)}")
+    if boxes.data_ptr() % 32:
+        raise ValueError("eval: boxes must be 32-byte aligned")
+    return traj.shape[0]
+
+
+def eval_traj_volume(boxes, traj, out=None):
+    """Volume of every packed trajectory: boxes [F,4] float64, traj [T,3] int64 (row offset, begin, end) -> [T]
+    float64, summed in frame order like the reference's viou (lib/evaluation/common.py:100-105)."""
+    T = _eval_traj(boxes, traj)
+    if out is None:
+        out = torch.empty(T, dtype=torch.float64, device=boxes.device)
+    elif _dev(out, "out", torch.float64).shape != (T,):
+        raise ValueError(f"eval_traj_volume: out must be [{T}]")
+    _abi.check(_abi.lib().tspn_eval_traj_volume_f64(_p(boxes), _p(traj), T, _p(out), _stream()))
+    return out
+
+
+def eval_viou(boxes, traj, vol, groups, pred_group, n_cand, ov=None, zden=None):
+    """ov [n_cand] float64 = min(subject vIoU, object vIoU) of every (prediction, same-triplet ground truth) pair,
+    group blocks row-major (include/tspn_mi355x.h); zden [P] int32 = 1 where a pair had a zero vIoU denominator.
+    groups [G,5] int64, pred_group [P] int32.  Returns (ov, zden)."""
+    T = _eval_traj(boxes, traj)
+    _dev(vol, "vol", torch.float64), _dev(groups, "groups", torch.int64), _dev(pred_group, "pred_group", torch.int32)
+    if vol.shape != (T,) or groups.dim() != 2 or groups.shape[1] != 5 or pred_group.dim() != 1:
+        raise ValueError("eval_viou: vol [T], groups [G,5] and pred_group [P] expected")
+    P = pred_group.shape[0]
+    if 2 * P > T:
+        raise ValueError(f"eval_viou: {P} predictions need {2 * P} trajectories, traj has {T}")
+    dev = boxes.device
+    ov = torch.empty(int(n_cand), dtype=torch.float64, device=dev) if ov is None else _dev(ov, "ov", torch.float64)
+    zden = torch.empty(P, dtype=torch.int32, device=dev) if zden is None else _dev(zden, "zden", torch.int32)
+    if ov.shape != (int(n_cand),) or zden.shape != (P,):
+        raise ValueError(f"eval_viou: ov must be [{n_cand}] and zden [{P}]")
+    _abi.check(_abi.lib().tspn_eval_viou_f64(_p(boxes), _p(traj), _p(vol), _p(groups), _p(pred_group), P, _p(ov),
+                                             _p(zden), _stream()))
+    return ov, zden
+
+
+def eval_greedy_match(ov, groups, n_pred, viou_threshold, max_group_gt, det_ws=None, hit=None, match=None):
+    """The reference's greedy match per (video, triplet) group: hit [n_pred] int8 (0/1) and match [n_pred] int32
+    (ground-truth index inside the group, -1 for none).  max_group_gt: the largest group's ground-truth count; above
+    4096 `det_ws` (uint8, one zeroed byte per packed relation) is required.  Returns (hit, match)."""
+    _dev(ov, "ov", torch.float64), _dev(groups, "groups", torch.int64)
+    if groups.dim() != 2 or groups.shape[1] != 5 or ov.dim() != 1:
+        raise ValueError("eval_greedy_match: ov [C] and groups [G,5] expected")
+    if det_ws is not None:
+        _dev(det_ws, "det_ws", torch.uint8)
+    elif max_group_gt > 4096:
+        raise ValueError("eval_greedy_match: groups of more than 4096 ground truths need det_ws")
+    dev = ov.device
+    hit = torch.empty(int(n_pred), dtype=torch.int8, device=dev) if hit is None else _dev(hit, "hit", torch.int8)
+    match = torch.empty(int(n_pred), dtype=torch.int32, device=dev) if match is None else _dev(match, "match", torch.int32)
+    if hit.shape != (int(n_pred),) or match.shape != (int(n_pred),):
+        raise ValueError(f"eval_greedy_match: hit and match must be [{n_pred}]")
+    _abi.check(_abi.lib().tspn_eval_greedy_match_f64(_p(ov), _p(groups), groups.shape[0], int(max_group_gt),
+                                                     float(viou_threshold), _p(det_ws), _p(hit), _p(match), _stream()))
+    return hit, match
 
 # every public operator runs with the device of its operands made current (see _on_tensor_device)
 for _name in __all__:
