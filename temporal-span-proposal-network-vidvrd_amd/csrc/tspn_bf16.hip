@@ -23,22 +23,11 @@
 #include <type_traits>
 
 #include "tspn_common.h"
+#include "tspn_device.h"
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef short s16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
+using namespace tspn_dev;
 
 // ------------------------------------------------------------------------------------------------
 __global__ void cast_bf16_kernel(const float* __restrict__ src, int64_t n, __bf16* __restrict__ dst) {
@@ -126,11 +115,6 @@ constexpr int BM = 128, BN = 128;
 // this ring reached 0.9 PFLOP/s and was removed: see DESIGN.md §4b.)
 constexpr int R_KC = 16, R_KG = 2, R_NST = 4;
 
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
-
 // ------------------------------------------------------------------------------------------------
 // conv3 bf16 (shipped structure): 256 x 256 tile, 8 waves (2 x 4, wave tile 128 m x 64 n =
 // 4 x 2 blocks), ring of 4 stages of one k-step each (32.1 KB per stage, 128.5 KB, 1 workgroup/CU with
@@ -179,7 +163,7 @@ __global__ __launch_bounds__(G_THREADS, 1) void conv3_bf16_big_kernel(
   // scalar offset that advances per chunk) rather than global_load_lds_dwordx4 with a 64-bit pointer per lane: beside MFMAs
   // the buffer form costs its wave 110 - 140 cycles of issue per piece against 175 - 195 (tools/probes/lds_dma_issue_probe.hip,
   // profiles/r4/lds_dma_issue_probe.txt), and the per-chunk pointer arithmetic moves from the vector to the scalar unit.
-  const __amdgpu_buffer_rsrc_t rsrc_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(Wp), 0, w_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_a = buffer_rsrc(Wp, w_bytes);
   unsigned aoff[3];
 #pragma unroll
   for (int i = 0; i < 3; ++i) {
@@ -193,8 +177,8 @@ __global__ __launch_bounds__(G_THREADS, 1) void conv3_bf16_big_kernel(
   // x pieces: wave w stages units [64w, 64w+64); wave 0 also the 8 units of piece 8.  Descriptor based at the first
   // column this tile reads (any clip count: the lane offsets stay below 260 columns)
   const int64_t nbase = n0 > 0 ? n0 - 1 : 0;
-  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<__bf16*>(x) + nbase * Cin, 0, (int)min((int64_t)(G_BN + 4) * Cin * 2, (ncols - nbase) * (int64_t)Cin * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc(
+      x + nbase * Cin, (int)min((int64_t)(G_BN + 4) * Cin * 2, (ncols - nbase) * (int64_t)Cin * 2));
   unsigned boff[2];
   bool bval[2];
 #pragma unroll
@@ -207,9 +191,6 @@ __global__ __launch_bounds__(G_THREADS, 1) void conv3_bf16_big_kernel(
     boff[q] = (unsigned)((n - nbase) * Cin * 2 + 16 * (g < R_KG ? g : 0));
   }
   int a_soff = 0, x_soff = 0;                              // scalar offsets of the next chunk to stage
-  auto bglds16 = [&](const __amdgpu_buffer_rsrc_t& r, unsigned voff, int soff, char* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)l, 16, (int)voff, soff, 0, 0);
-  };
   auto stage_chunk = [&](int st) {
     char* sa = smem + st * G_ST;
 #pragma unroll
@@ -436,8 +417,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void heads_pairgrid_bf16_
   // (buffer loads: descriptor = this video's rows of y, a fixed 32-bit lane offset per piece, one scalar offset that
   // advances 128 bytes per k-step -- cheaper to issue beside MFMAs than global_load_lds with eight 64-bit pointers per
   // lane, and eight registers and sixteen vector adds per k-step less; tools/probes/lds_dma_issue_probe.hip)
-  const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(y) + (int64_t)b * N * T * ldm, 0, (int)(unsigned)((int64_t)N * T * ldm * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_y = buffer_rsrc(y + (int64_t)b * N * T * ldm, (int)(unsigned)((int64_t)N * T * ldm * 4));
   unsigned voff[8];
   {
     const int fq = lane & 7;
@@ -451,21 +431,19 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void heads_pairgrid_bf16_
       voff[i] = (unsigned)((((int64_t)trk * T + t) * ldm + (r < SBLK ? 0 : C) + 4 * q) * 4);
     }
   }
-  const __amdgpu_buffer_rsrc_t rsrc_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(Whp), 0, C * 32, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(Whp, C * 32);
   int y_soff = 0, w_soff = 0;
   auto stage = [&](int buf) {
     char* dst = smem + buf * ST + wave * 4 * HP_ROW;
 #pragma unroll
     for (int i = 0; i < 8; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_y, (__attribute__((address_space(3))) void*)(dst + i * 1024), 16,
-                                               (int)voff[i], y_soff, 0, 0);
+      bglds16(rsrc_y, voff[i], y_soff, dst + i * 1024);
     y_soff += HP_KC * 4;
     // head weights of the k-step, [4 kg][16 h][8 ch] bf16 = the packed layout itself; staged through
     // LDS as well so that no register-returning global load (whose wait the compiler would place at the
     // top of the loop, serialising the whole DMA queue with the compute) is left in the loop
     if (wave == 0) {
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_w, (__attribute__((address_space(3))) void*)(smem + buf * ST + ROWS * HP_ROW),
-                                               16, lane * 16, w_soff, 0, 0);
+      bglds16(rsrc_w, lane * 16, w_soff, smem + buf * ST + ROWS * HP_ROW);
       w_soff += 1024;
     }
   };

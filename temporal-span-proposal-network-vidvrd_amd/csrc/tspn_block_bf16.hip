@@ -32,14 +32,11 @@
 #include <algorithm>
 
 #include "tspn_common.h"
+#include "tspn_device.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+using namespace tspn_dev;
 
 constexpr int THREADS = 256;
 constexpr int TW = 30;                  // output pixels of a tile row
@@ -91,13 +88,10 @@ __global__ __launch_bounds__(THREADS, 2) void bottleneck_block_bf16_kernel(
   const unsigned woff = lane * 16;
 
   // one descriptor per tensor, based at this image: every offset below is a 32-bit byte offset inside the image
-  const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<__bf16*>(x) + (int64_t)img * Hin * Win * CIN, 0, (int)(unsigned)((int64_t)Hin * Win * CIN * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs_o = __builtin_amdgcn_make_buffer_rsrc(
-      out + (int64_t)img * H * W * C4, 0, (int)(unsigned)((int64_t)H * W * C4 * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_x = buffer_rsrc(x + (int64_t)img * Hin * Win * CIN, (int)(unsigned)((int64_t)Hin * Win * CIN * 2));
+  const __amdgpu_buffer_rsrc_t rs_o = buffer_rsrc(out + (int64_t)img * H * W * C4, (int)(unsigned)((int64_t)H * W * C4 * 2));
   // where the residual rows come from (32-bit offsets inside the image, like the output's)
-  const __amdgpu_buffer_rsrc_t rs_r = RES == 2 ? __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<__bf16*>(Wfs) + (int64_t)img * H * W * C4, 0, (int)(unsigned)((int64_t)H * W * C4 * 2), 0x00020000) : rs_x;
+  const __amdgpu_buffer_rsrc_t rs_r = RES == 2 ? buffer_rsrc(Wfs + (int64_t)img * H * W * C4, (int)(unsigned)((int64_t)H * W * C4 * 2)) : rs_x;
   // byte offset of the input pixel under output pixel (yy, xx): a 1x1 conv of stride ST reads pixel (ST yy, ST xx)
   auto xpix = [&](int yy, int xx) { return (unsigned)(((yy * ST) * Win + xx * ST) * CIN * 2); };
   constexpr unsigned OOB = 0x80000000u;             // beyond every descriptor: loads give zeros, stores are dropped
@@ -136,10 +130,10 @@ __global__ __launch_bounds__(THREADS, 2) void bottleneck_block_bf16_kernel(
 #pragma unroll
       for (int gg = 0; gg < 2; ++gg)
 #pragma unroll
-        for (int sq = 0; sq < 4; ++sq)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(
-              rs_x, (__attribute__((address_space(3))) void*)(Bs + buf * XST + ((2 * wave + gg) * SL1 + 64 * sq) * 16), 16,
-              (int)xv[sq], c * 128 + (2 * wave + gg) * 16, 0, 0);
+        for (int sq = 0; sq < 4; ++sq) {
+          char* l = Bs + buf * XST + ((2 * wave + gg) * SL1 + 64 * sq) * 16;
+          bglds16(rs_x, xv[sq], c * 128 + (2 * wave + gg) * 16, l);
+        }
     };
     const int64_t w1row = (int64_t)C1 * 4096;
     f32x4 a[2][4];                                   // W1 fragments of a chunk's four k-steps, this chunk's and the next's
@@ -338,7 +332,7 @@ __global__ __launch_bounds__(THREADS, 2) void bottleneck_block_bf16_kernel(
       const bool ok = li < TW && yy < H && xx < W;
       po[pj] = ok ? (unsigned)(((yy * W + xx) * C4 + 16 * kh) * 2) : OOB;
     }
-    u32x4_t keep[2] = {};                            // store data of the previous group (see the epilogue)
+    u32x4 keep[2] = {};                            // store data of the previous group (see the epilogue)
     // The wave's row blocks go in PAIRS (two 32-channel blocks = one 128-byte line of a pixel) and the tile's column blocks
     // in groups of two: the four 16-byte stores that complete a pixel's line are issued back to back.  (First form: one
     // row block per pass, the two halves of a line a whole pass apart -- L2 hands part-written lines to the fabric as
@@ -479,14 +473,14 @@ __global__ __launch_bounds__(THREADS, 2) void bottleneck_block_bf16_kernel(
               const float4 t = *reinterpret_cast<const float4*>(b3s + (mbA + ms) * 128 + 16 * i);
               bv[4 * i] = t.x; bv[4 * i + 1] = t.y; bv[4 * i + 2] = t.z; bv[4 * i + 3] = t.w;
             }
-            u32x4_t o2[2];
+            u32x4 o2[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
               bf16x8 o;
 #pragma unroll
               for (int j = 0; j < 8; ++j)
                 o[j] = (__bf16)fmaxf((acc[ms][pj][8 * h + j] + bv[8 * h + j]) + (float)res[PROJ ? 0 : (g & 1)][ms][pj][h][j], 0.f);
-              o2[h] = __builtin_bit_cast(u32x4_t, o);
+              o2[h] = __builtin_bit_cast(u32x4, o);
             }
             __builtin_amdgcn_raw_buffer_store_b128(o2[0], rs_o, (int)(pofs == OOB ? OOB : pofs), (mbA + ms) * 64, 0);
             __builtin_amdgcn_raw_buffer_store_b128(o2[1], rs_o, (int)(pofs == OOB ? OOB : pofs + 16), (mbA + ms) * 64, 0);

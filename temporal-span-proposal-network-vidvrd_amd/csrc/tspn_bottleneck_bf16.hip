@@ -32,14 +32,11 @@
 #include <type_traits>
 
 #include "tspn_common.h"
+#include "tspn_device.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+using namespace tspn_dev;
 
 constexpr int THREADS = 256;
 constexpr int BN = 128;                 // pixels per workgroup
@@ -47,14 +44,6 @@ constexpr int KC = 64;                  // channels per chunk
 constexpr int SLP = 132;                // padded pixel slots per channel group
 constexpr int B_ST = 8 * SLP * 16;      // bytes per x stage = per 64 channels of the h2 image
 
-template <int OFF>
-__device__ __forceinline__ void load_wfrag(f32x4& dst, unsigned lane_off, const char* base) {
-  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(lane_off), "s"(base), "n"(OFF) : "memory");
-}
-template <int VM>
-__device__ __forceinline__ void wait_w(f32x4& r0, f32x4& r1) {
-  asm volatile("s_waitcnt vmcnt(%2)" : "+v"(r0), "+v"(r1) : "n"(VM));
-}
 // NEXT (CM = 256, round 4): the kernel also computes conv1 of the FOLLOWING block on its own output tile,
 //     h1n = relu(W1n . out + b1n)        1x1, K = 4 CM = 1024 -> CM rows,
 // so that the 4 CM-channel map is read once per block (as the next block's residual) instead of twice.  Phase 3 then
@@ -130,10 +119,7 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
   // cheaper one to issue beside MFMAs (tools/probes/lds_dma_issue_probe.hip)
   constexpr unsigned OOB = 0x80000000u;
   const int64_t rbase = n0 - W - 1 > 0 ? n0 - W - 1 : 0;
-  const __amdgpu_buffer_rsrc_t rsrc_h1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(h1) + rbase * CM, 0, 0x7fffffff, 0x00020000);
-  auto bglds16 = [&](unsigned voff, int soff, char* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_h1, (__attribute__((address_space(3))) void*)l, 16, (int)voff, soff, 0, 0);
-  };
+  const __amdgpu_buffer_rsrc_t rsrc_h1 = buffer_rsrc_unbounded(h1 + rbase * CM);
 
   f32x16 acc[MI][NI];
 #pragma unroll
@@ -207,12 +193,12 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
       const unsigned voff = (q >= 0 && q < npix) ? (unsigned)((q - rbase) * CM * 2 + 16 * bg) : OOB;
       char* dst = Bs + buf * B_ST + (bg * SLP + 64 * (wave & 1)) * 16;
 #pragma unroll
-      for (int p = 0; p < 4; ++p) bglds16(voff + 32 * p, soff, dst + 2 * p * SLP * 16);
+      for (int p = 0; p < 4; ++p) bglds16(rsrc_h1, voff + 32 * p, soff, dst + 2 * p * SLP * 16);
       if (wave == 0 && lane < 16) {                          // slots 128, 129: [group][2]
         const int g = lane >> 1, e = lane & 1;
         const int64_t q2 = n0 + (int64_t)(ra - 1) * W - 1 + 128 + e;
         const unsigned voff2 = (q2 >= 0 && q2 < npix) ? (unsigned)((q2 - rbase) * CM * 2 + 16 * g) : OOB;
-        bglds16(voff2, soff, extra + buf * 256);             // the DMA adds lane * 16
+        bglds16(rsrc_h1, voff2, soff, extra + buf * 256);             // the DMA adds lane * 16
       }
     };
 #pragma unroll
@@ -390,13 +376,13 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
         const unsigned voff = (q >= 0 && q < npix) ? (unsigned)((q - rbase) * CM * 2 + 16 * bg) : OOB;
         char* dst = Bs + ra * B_ST + (bg * SLP + 64 * (wave & 1)) * 16;
 #pragma unroll
-        for (int p = 0; p < 4; ++p) bglds16(voff + 32 * p, half * KC * 2, dst + 2 * p * SLP * 16);
+        for (int p = 0; p < 4; ++p) bglds16(rsrc_h1, voff + 32 * p, half * KC * 2, dst + 2 * p * SLP * 16);
       }
       if (wave == 0 && lane < 48) {                          // slots 128, 129 of the three ranges: [range][group][2]
         const int ra = lane >> 4, g = (lane >> 1) & 7, e = lane & 1;
         const int64_t q = n0 + (int64_t)(ra - 1) * W - 1 + 128 + e;
         const unsigned voff = (q >= 0 && q < npix) ? (unsigned)((q - rbase) * CM * 2 + 16 * g) : OOB;
-        bglds16(voff, half * KC * 2, extra);                 // the DMA adds lane * 16
+        bglds16(rsrc_h1, voff, half * KC * 2, extra);                 // the DMA adds lane * 16
       }
 #pragma unroll
       for (int mi = 0; mi < MI; ++mi) wl[mi] = wbase[mi] + half * (9 * 4096);
@@ -483,7 +469,7 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
   // `global_load_dwordx4 v[..], v[a:a+1], off` in the ISA) in a phase whose instruction stream, not its bytes, is what
   // bounds it (profiles/r4/bottleneck_pipeline_study.md §8).  Pixels beyond the end get an out-of-range offset: their loads
   // return zeros, their stores are dropped -- no branch around the stores.
-  const __amdgpu_buffer_rsrc_t rsrc_w3 = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(Wf3), 0, C4 * CM * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_w3 = buffer_rsrc(Wf3, C4 * CM * 2);
   // (NEXT sits at 510 of 512 registers and spills with the descriptors: it keeps the pointer form)
   const char* const w3base = reinterpret_cast<const char*>(Wf3) + woff3;
   auto w3_load = [&](int sp, int k, int ms) {       // fragment of k-step k, row block ms of sub-pass sp
@@ -538,8 +524,8 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
   const unsigned voff_in = (unsigned)(li * C4 + 16 * kh) * 2;
   constexpr unsigned OOB3 = 0x80000000u;
   // descriptors based at the tile's first pixel; uniform byte offset of a group's rows inside the tile
-  const __amdgpu_buffer_rsrc_t rsrc_res = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(residual) + n0 * C4, 0, 0x7fffffff, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsrc_out = __builtin_amdgcn_make_buffer_rsrc(out + n0 * C4, 0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_res = buffer_rsrc_unbounded(residual + n0 * C4);
+  const __amdgpu_buffer_rsrc_t rsrc_out = buffer_rsrc_unbounded(out + n0 * C4);
   auto row_soff = [&](int sp, int grp) {
     const int ms = grp % MS, nj = grp / MS;
     return ((sub_nb(sp) + nj) * 32 * C4 + 32 * (sub_rb(sp) + ms)) * 2;
@@ -605,8 +591,8 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
         }
       } else {
         const int vo = (int)(okp ? voff_in : OOB3), so = row_soff(e, grp);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, ohold), rsrc_out, vo, so, 0);
-        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, o), rsrc_out, vo + 16, so, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, ohold), rsrc_out, vo, so, 0);
+        __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, o), rsrc_out, vo + 16, so, 0);
       }
       res_issue_ahead(e, std::integral_constant<int, grp>{});   // its ring slot is free now
     }

@@ -26,14 +26,12 @@
 #include <type_traits>
 
 #include "tspn_common.h"
+#include "tspn_device.h"
 #include "tspn_status.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+using namespace tspn_dev;
 
 constexpr int CM = 256;
 constexpr int THREADS = 512;
@@ -57,18 +55,6 @@ static_assert(SMEM <= 160 * 1024, "LDS budget");
 
 __device__ __bf16 g_zero_page_bp[128];  // source of padding taps (never written)
 
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-template <int OFF>
-__device__ __forceinline__ void load_wfrag(f32x4& dst, unsigned lane_off, const char* base) {
-  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(lane_off), "s"(base), "n"(OFF) : "memory");
-}
-template <int VM>
-__device__ __forceinline__ void wait_w(f32x4& r0, f32x4& r1) {
-  asm volatile("s_waitcnt vmcnt(%2)" : "+v"(r0), "+v"(r1) : "n"(VM));
-}
 // counters in LDS: one add per wave (lane 0), polled by every wave that waits
 __device__ __forceinline__ void lds_add1(char* Bs, int off, int lane) {
   if (lane == 0)

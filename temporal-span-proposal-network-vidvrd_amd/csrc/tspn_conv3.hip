@@ -26,10 +26,11 @@
 #include <type_traits>
 
 #include "tspn_common.h"
+#include "tspn_device.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
+using namespace tspn_dev;
 
 constexpr int BM = 128;
 constexpr int BN = 128;
@@ -303,7 +304,6 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_mfma_kernel(
   }
 }
 
-
 // ---------------------------------------------------------------------------------------------
 // Fast path: the same tiling with the operand tiles moved HBM/L2 -> LDS by LDS-DMA
 // (global_load_lds): no staging registers, no ds_write pass, a dozen VMEM instructions per wave
@@ -314,15 +314,6 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_mfma_kernel(
 // flight: out-of-range rows / columns read clamped addresses and are never stored, and the only
 // valid column they could leak into (the last one, through its +1 tap) is already masked as a
 // sequence end.
-__device__ __forceinline__ void glds16(const float* g, float* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-__device__ __forceinline__ void glds4(const float* g, float* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 4, 0, 0);
-}
-
 template <int KCD>
 __global__ __launch_bounds__(THREADS, (KCD == 8 ? 4 : 2)) void conv3_mfma_dma_kernel(
     const float* __restrict__ x, const float* __restrict__ Wp, const float* __restrict__ bias,
@@ -568,7 +559,6 @@ __global__ __launch_bounds__(THREADS, (KCD == 8 ? 4 : 2)) void conv3_mfma_dma_ke
   }
 }
 
-
 // ---------------------------------------------------------------------------------------------
 // Channels-last variant: x is [B, T, Cin] — the tracklet layout itself — so the fused path needs
 // no transpose pass, a column's channels are contiguous (16-B aligned DMA pieces: 9 per chunk and
@@ -787,7 +777,6 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_mfma_cl_kernel(
   }
 }
 
-
 }  // namespace
 
 extern "C" int tspn_pack_conv3_f32(const float* W, int64_t M, int64_t Cin, int64_t split,
@@ -835,7 +824,6 @@ extern "C" int tspn_conv3_f32(const float* x, int64_t B, int64_t Cin, int64_t T,
                      (int)tiles_m, (int)tiles_n, relu, (int)T);
   return tspn::check_launch("tspn_conv3_f32");
 }
-
 
 extern "C" int tspn_conv3_tc_f32(const float* x, int64_t B, int64_t T, int64_t Cin,
                                  const float* packed, int64_t M, const float* bias, int relu,

@@ -19,10 +19,11 @@
 #include <type_traits>
 
 #include "tspn_common.h"
+#include "tspn_device.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace tspn_dev;
 
 constexpr int NP = 4;       // pairs per wave
 constexpr int WAVES = 4;    // waves per workgroup
@@ -144,7 +145,6 @@ __global__ __launch_bounds__(WAVES * 64) void heads_kernel(
     }
   }
 }
-
 
 // ---------------------------------------------------------------------------------------------
 // Blocked pair stage for the canonical pair table (all ordered pairs (s,o), s != o, s-major, per
@@ -310,7 +310,6 @@ __global__ __launch_bounds__(256, 2) void heads_pairgrid_kernel(
   }
 }
 
-
 // ---------------------------------------------------------------------------------------------
 // Third structure of the blocked pair stage (same tiling: 8 subjects x 8 objects x 32 frames per
 // workgroup, 16-channel chunks).  Ablation of the kernel above (profiles/r1) put 0.55 ms of 2.55
@@ -320,11 +319,6 @@ __global__ __launch_bounds__(256, 2) void heads_pairgrid_kernel(
 //     (ldt) so a 16-byte piece never leaves its row; a piece = 8 channels x 32 frames of one row;
 //   * the activations of the NEXT (k-step, subject) phase are computed under the 16 MFMAs of the
 //     current one (explicit software pipeline, issue pattern 2 VALU : 1 MFMA).
-__device__ __forceinline__ void hglds16(const float* g, float* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
-
 __global__ __launch_bounds__(256, 2) void heads_pairgrid3_kernel(
     const float* __restrict__ y, int64_t ldt, int C, int T, int N, const float* __restrict__ Wh,
     const float* __restrict__ bh, int H, float* __restrict__ out, int ntb, int nob, int nsb,
@@ -366,7 +360,7 @@ __global__ __launch_bounds__(256, 2) void heads_pairgrid3_kernel(
   auto stage_piece = [&](int buf, auto p_tag) {  // piece p = 2*r + hh of this wave
     constexpr int p = decltype(p_tag)::value;
     constexpr int r = p >> 1, hh = p & 1;
-    hglds16(srow[r] + hh * half_step + loff, S + buf * PG_STAGE + ((4 * wave + r) * PG_CK + 8 * hh) * PG_T);
+    glds16(srow[r] + hh * half_step + loff, S + buf * PG_STAGE + ((4 * wave + r) * PG_CK + 8 * hh) * PG_T);
     if (hh == 1) srow[r] += chunk_step;
   };
   const int o_a = lane & 15;
@@ -540,7 +534,6 @@ __device__ __forceinline__ void swait6(f32x4& a, f32x4& b, f32x4& c, f32x4& d, f
 // (acc.x, acc.y) += w * (act.x, act.y): v_pk_fma_f32 with the weight broadcast from the low (even head) or the
 // high (odd head) dword of an SGPR pair.  A plain v_fma_f32 issues once per 4 cycles and SIMD like every VALU
 // instruction (measured: 4.3), i.e. at HALF the fp32 peak; only the packed form reaches 64 FLOP / clk / SIMD.
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void pkfma_lo(f32x2& acc, f32x2 w_sgpr, f32x2 act) {
   asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,0,0] op_sel_hi:[0,1,1]" : "+v"(acc) : "s"(w_sgpr), "v"(act));
 }
@@ -579,8 +572,7 @@ __global__ __launch_bounds__(256, CK == 8 ? 3 : 2) void heads_pairgrid4_kernel(
   // ---- DMA sources (as in heads_pairgrid3_kernel): wave w stages tile rows 4w..4w+3.  Buffer loads (round 4): one SGPR
   // descriptor of this video's projections (the launcher checks they stay below 2 GB), a 32-bit lane offset per row, the
   // channel chunk / half as the scalar offset -- cheaper to issue than global_load_lds (tools/probes/lds_dma_issue_probe.hip)
-  const __amdgpu_buffer_rsrc_t rsrc_y = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float*>(y) + b * N * rowlen, 0, (int)(unsigned)((int64_t)N * rowlen * 4), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_y = buffer_rsrc(y + b * N * rowlen, (int)(unsigned)((int64_t)N * rowlen * 4));
   unsigned voff[4];
   const unsigned loff = (unsigned)((lane >> 3) * ldt + min((int64_t)t0 + (lane & 7) * 4, ldt - 4));
 #pragma unroll
@@ -597,9 +589,7 @@ __global__ __launch_bounds__(256, CK == 8 ? 3 : 2) void heads_pairgrid4_kernel(
     for (int r = 0; r < 4; ++r) {
 #pragma unroll
       for (int hh = 0; hh < CK / 8; ++hh)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            rsrc_y, (__attribute__((address_space(3))) void*)(S + buf * STAGE + ((4 * wave + r) * CK + 8 * hh) * PG_T), 16,
-            (int)voff[r], y_soff + hh * half_bytes, 0, 0);
+        bglds16(rsrc_y, voff[r], y_soff + hh * half_bytes, S + buf * STAGE + ((4 * wave + r) * CK + 8 * hh) * PG_T);
     }
     y_soff += (CK / 8) * half_bytes;
   };
@@ -745,7 +735,6 @@ extern "C" int tspn_heads_f32(int mode, const float* a, const float* b, int64_t 
 #undef TSPN_HEADS_LAUNCH
   return tspn::check_launch("tspn_heads_f32");
 }
-
 
 extern "C" int tspn_heads_pairgrid_f32(const float* y, int64_t B, int64_t N, int64_t C, int64_t T,
                                        const float* Wh, const float* bh, int64_t H, float* out,

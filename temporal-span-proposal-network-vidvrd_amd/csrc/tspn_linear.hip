@@ -15,10 +15,11 @@
 #include <algorithm>
 
 #include "tspn_common.h"
+#include "tspn_device.h"
 
 namespace {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace tspn_dev;
 
 constexpr int TM = 64;         // rows (pairs) per workgroup tile
 constexpr int NBLK = 9;        // 16-wide column blocks per tile
@@ -309,7 +310,6 @@ int tspn::linear(const float* x, int64_t P, int64_t F, int64_t ldx, const float*
   return tspn::check_launch("tspn_predicate_head_f32(reduce)");
 }
 
-
 extern "C" size_t tspn_predicate_head_norm_workspace_bytes(int64_t P, int64_t F, int64_t K,
                                                            int64_t first, int64_t block,
                                                            int64_t nblocks) {
@@ -360,7 +360,6 @@ extern "C" int tspn_predicate_head_norm_f32(const float* x, int64_t P, int64_t F
   return tspn::check_launch("tspn_predicate_head_norm_f32(reduce)");
 }
 
-
 size_t tspn::pair_predicate_workspace_bytes(int64_t NT, int64_t D, int64_t K) {
   return tspn::align_up(tspn_predicate_head_workspace_bytes(NT, D, K), 256) +
          2 * tspn::align_up((size_t)NT * K * sizeof(float), 256);
@@ -387,7 +386,6 @@ int tspn::pair_predicate(const float* fbar, int64_t NT, int64_t D, const int64_t
                      P, K, cls_b, out);
   return tspn::check_launch("pair_predicate(combine)");
 }
-
 
 namespace {
 struct SpanLayout {

@@ -17,11 +17,11 @@
 #include <type_traits>
 
 #include "tspn_common.h"
+#include "tspn_device.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+using namespace tspn_dev;
 
 constexpr int THREADS = 256;
 constexpr int BM = 128, BN = 128;
@@ -32,11 +32,6 @@ template <int KC>
 constexpr size_t smem_bytes() { return sizeof(float) * 2 * (KC * BM + (KC / 4) * SLP * 4); }
 
 __device__ float g_zero_page[64];      // source of padding taps (never written)
-
-__device__ __forceinline__ void glds16(const float* g, float* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // w [Cout][Cin][KH][KW] (torch Conv2d layout) -> packed [KH*KW][Cin][Cout]
 __global__ void pack_conv2d_kernel(const float* __restrict__ w, int64_t Cout, int64_t Cin, int64_t KH,
@@ -233,14 +228,6 @@ __global__ __launch_bounds__(THREADS, 2) void conv2d_nhwc_kernel(
 // is two global_load_dwordx4 per lane and chunk (one 2-KiB line per wave), refilled for chunk i+1 as soon
 // as the MFMAs of chunk i have read them (rolling, counted vmcnt).  Only the x tile goes through LDS
 // (2 DMA pieces per wave and chunk, double-buffered, bare s_barrier per chunk).
-template <int OFF>
-__device__ __forceinline__ void load_wfrag(f32x4& dst, unsigned lane_off, const char* base) {
-  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(lane_off), "s"(base), "n"(OFF) : "memory");
-}
-template <int VM>
-__device__ __forceinline__ void wait_w(f32x4& r) {
-  asm volatile("s_waitcnt vmcnt(%1)" : "+v"(r) : "n"(VM));
-}
 
 // w [Cout][Cin][KH][KW] -> fragment-major [Cout/32][KH*KW][Cin/16][64][8]
 __global__ void pack_conv2d_frag_kernel(const float* __restrict__ w, int64_t Cout, int64_t Cin, int64_t ntaps,
@@ -453,8 +440,6 @@ __device__ __forceinline__ void bilinear_setup(float y, float x, int H, int W, i
   const float ly = y - (float)yl, lx = x - (float)xl, hy = 1.f - ly, hx = 1.f - lx;
   w1 = hy * hx; w2 = hy * lx; w3 = ly * hx; w4 = ly * lx;
 }
-
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 // four channels of a map pixel as fp32 (bf16 values are exact in fp32)
 template <bool BF16IN>

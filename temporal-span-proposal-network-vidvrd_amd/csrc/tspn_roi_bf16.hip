@@ -30,32 +30,17 @@
 #include <type_traits>
 
 #include "tspn_common.h"
+#include "tspn_device.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+using namespace tspn_dev;
 
 constexpr int THREADS = 256;
 constexpr int BN = 128;
 constexpr int KC = 64;                  // channels per chunk
 constexpr int SLP = 132;                // padded pixel slots per channel group
 constexpr int B_ST = 8 * SLP * 16;      // bytes per x stage: [8 groups][132 slots][8 bf16]
-
-template <int OFF>
-__device__ __forceinline__ void load_wfrag(f32x4& dst, unsigned lane_off, const char* base) {
-  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(lane_off), "s"(base), "n"(OFF) : "memory");
-}
-template <int VM>
-__device__ __forceinline__ void wait_w(f32x4& r) {
-  asm volatile("s_waitcnt vmcnt(%1)" : "+v"(r) : "n"(VM));
-}
-template <int VM>
-__device__ __forceinline__ void wait_w(f32x4& r0, f32x4& r1) {
-  asm volatile("s_waitcnt vmcnt(%2)" : "+v"(r0), "+v"(r1) : "n"(VM));
-}
 
 // w fp32 [Cout][Cin][KH][KW] -> bf16 fragment-major [Cout/32][Cin/64][taps][4][64][8]
 __global__ void pack_conv2d_frag_bf16_kernel(const float* __restrict__ w, int64_t Cout, int64_t Cin, int64_t ntaps,
@@ -139,7 +124,7 @@ __global__ __launch_bounds__(THREADS, (MI == 1 ? TSPN_ROI_BF16_MI1_WAVES : 2)) v
   };
   // base = the first pixel of the image the tile starts in: every valid tap of the tile lies at or behind it
   const int64_t base_pix = ((n0 < npix ? n0 : 0) / ((int64_t)OH * OW)) * H * W;
-  const __amdgpu_buffer_rsrc_t rsrc_x = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(x) + base_pix * Cin, 0, 0x7fffffff, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_x = buffer_rsrc_unbounded(x + base_pix * Cin);
   // tap chunks: piece instruction q = 4 wave + p covers pixels 8 q .. 8 q + 7 of the tile; lane l: pixel 8 q + (l >> 3),
   // LDS position l & 7 = piece ((l & 7) ^ f(pixel)), f = (l >> 3) ^ (q & 1)
   unsigned pboff[4];                               // byte offset of the lane's piece (first tap) from the base, per instruction
@@ -160,9 +145,6 @@ __global__ __launch_bounds__(THREADS, (MI == 1 ? TSPN_ROI_BF16_MI1_WAVES : 2)) v
       tapmask[p] = m;
     }
   }
-  auto bglds16 = [&](unsigned voff, int soff, char* l) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_x, (__attribute__((address_space(3))) void*)l, 16, (int)voff, soff, 0, 0);
-  };
   auto stage_x = [&](int buf, int i) {             // exactly four pieces per wave
     const int ntaps = KH * KW;
     const int c = i / ntaps, tap = i - c * ntaps;
@@ -173,7 +155,7 @@ __global__ __launch_bounds__(THREADS, (MI == 1 ? TSPN_ROI_BF16_MI1_WAVES : 2)) v
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
       const bool valid = (tapmask[p] >> tap) & 1ull;
-      bglds16(valid ? pboff[p] + tapoff : OOB, soff, dst + p * 1024);
+      bglds16(rsrc_x, valid ? pboff[p] + tapoff : OOB, soff, dst + p * 1024);
     }
   };
 
@@ -245,7 +227,7 @@ __global__ __launch_bounds__(THREADS, (MI == 1 ? TSPN_ROI_BF16_MI1_WAVES : 2)) v
     const int64_t npin = npix;                               // stride 1, pad 1: input pixels = output pixels
     // ranges: descriptor based at pixel max(n0 - W - 1, 0); a range pixel outside the tensor is an out-of-range offset
     const int64_t rbase = n0 - W - 1 > 0 ? n0 - W - 1 : 0;
-    const __amdgpu_buffer_rsrc_t rsrc_r = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(x) + rbase * Cin, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_r = buffer_rsrc_unbounded(x + rbase * Cin);
     auto stage_r = [&](int buf, int i) {                     // range i = 3 c + ra
       const int c = i / 3, ra = i - 3 * c;
       const int soff = c * KC * 2;
@@ -253,15 +235,16 @@ __global__ __launch_bounds__(THREADS, (MI == 1 ? TSPN_ROI_BF16_MI1_WAVES : 2)) v
       const unsigned voff = (q >= 0 && q < npin) ? (unsigned)((q - rbase) * Cin * 2 + 16 * bg) : OOB;
       char* dst = Bs + buf * B_ST + (bg * SLP + 64 * (wave & 1)) * 16;
 #pragma unroll
-      for (int p = 0; p < 4; ++p)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_r, (__attribute__((address_space(3))) void*)(dst + 2 * p * SLP * 16), 16,
-                                                 (int)(voff + 32 * p), soff, 0, 0);
+      for (int p = 0; p < 4; ++p) {
+        char* l = dst + 2 * p * SLP * 16;
+        bglds16(rsrc_r, voff + 32 * p, soff, l);
+      }
       if (wave == 0 && lane < 16) {                          // slots 128, 129: [group][2]
         const int g = lane >> 1, e = lane & 1;
         const int64_t q2 = n0 + (int64_t)(ra - 1) * W - 1 + 128 + e;
         const unsigned voff2 = (q2 >= 0 && q2 < npin) ? (unsigned)((q2 - rbase) * Cin * 2 + 16 * g) : OOB;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_r, (__attribute__((address_space(3))) void*)(extra + buf * 256), 16,
-                                                 (int)voff2, soff, 0, 0);      // the DMA adds lane * 16
+        char* l = extra + buf * 256;
+        bglds16(rsrc_r, voff2, soff, l);      // the DMA adds lane * 16
       }
     };
     auto read_r = [&](int buf, int tap, int rb, int ks, bf16x8 (&b)[4]) {

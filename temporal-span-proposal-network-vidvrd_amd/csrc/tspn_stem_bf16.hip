@@ -20,23 +20,16 @@
 #include <algorithm>
 
 #include "tspn_common.h"
+#include "tspn_device.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+using namespace tspn_dev;
 
 constexpr int KS = 7, KPAD = 3;           // the stem's kernel size and padding (stride 2)
 constexpr int TPX = 128;                  // output pixels per tile
 constexpr int SROW = 132;                 // staged s2d pixels per row (TPX + 3 used)
 constexpr int STAGE_BYTES = 4 * SROW * 32;
-
-__device__ __forceinline__ void glds16(const void* g, void* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, 0);
-}
 
 // x fp32 [NB][H][W][3] -> S bf16 [NB][SH][SW][16]; one thread = one s2d pixel (two 16-byte stores)
 __global__ __launch_bounds__(256) void stem_s2d_bf16_kernel(const float* __restrict__ x, int64_t NB, int H, int W,

@@ -31,15 +31,12 @@
 #include <type_traits>
 
 #include "tspn_common.h"
+#include "tspn_device.h"
 #include "tspn_status.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+using namespace tspn_dev;
 
 constexpr int THREADS = 512;
 constexpr int BN = 128;                 // pixels per workgroup
@@ -70,8 +67,6 @@ __device__ __forceinline__ void role_barrier() {
 // sub-pass counters in LDS: tspn_status.h (flag_set / flag_wait).  The wait is BOUNDED; a wave that gives up raises
 // TSPN_FAULT_HANDOVER through the device status block and ENDS -- it never reads or overwrites an exchange buffer it was
 // not handed (round 6; until then it fell through with wrong data and only a parity test would have noticed).
-using tspn_dev::flag_set;
-using tspn_dev::flag_wait;
 
 __global__ __launch_bounds__(THREADS, 1) void tail_io_bf16_kernel(
     const __bf16* __restrict__ h1, const __bf16* __restrict__ Wf2, const float* __restrict__ bias2,
@@ -108,7 +103,7 @@ __global__ __launch_bounds__(THREADS, 1) void tail_io_bf16_kernel(
     // stages the pixel (slot) 64 (w4 & 1) + lane, channel groups bg, bg + 2, bg + 4, bg + 6 (bg = w4 >> 1); slots 128, 129 go
     // to a side region (every io wave issues that piece -- same bytes, same place -- so that each has FIVE pieces per range)
     const int64_t rbase = n0 - W - 1 > 0 ? n0 - W - 1 : 0;
-    const __amdgpu_buffer_rsrc_t rsrc_h1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(h1) + rbase * CM, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_h1 = buffer_rsrc_unbounded(h1 + rbase * CM);
     const int slot = 64 * (w4 & 1) + lane, bg = w4 >> 1;
     auto stage_r = [&](int buf, int i) {
       const int c = i / 3, ra = i - 3 * c;
@@ -117,22 +112,22 @@ __global__ __launch_bounds__(THREADS, 1) void tail_io_bf16_kernel(
       const unsigned voff = (q >= 0 && q < npix) ? (unsigned)((q - rbase) * CM * 2 + 16 * bg) : OOB;
       char* dst = Bs + buf * B_ST + (bg * SLP + 64 * (w4 & 1)) * 16;
 #pragma unroll
-      for (int p = 0; p < 4; ++p)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_h1, (__attribute__((address_space(3))) void*)(dst + 2 * p * SLP * 16), 16,
-                                                 (int)(voff == OOB ? OOB : voff + 32 * p), soff, 0, 0);
+      for (int p = 0; p < 4; ++p) {
+        char* l = dst + 2 * p * SLP * 16;
+        bglds16(rsrc_h1, voff == OOB ? OOB : voff + 32 * p, soff, l);
+      }
       const int g = (lane >> 1) & 7, e = lane & 1;
       const int64_t q2 = n0 + (int64_t)(ra - 1) * W - 1 + 128 + e;
       const unsigned voff2 = (lane < 16 && q2 >= 0 && q2 < npix) ? (unsigned)((q2 - rbase) * CM * 2 + 16 * g) : OOB;
       if (lane < 16)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_h1, (__attribute__((address_space(3))) void*)(Bs + EXTRA_OFF + buf * 256), 16,
-                                                 (int)voff2, soff, 0, 0);
+        bglds16(rsrc_h1, voff2, soff, Bs + EXTRA_OFF + buf * 256);
     };
     // ---- phase 3 addresses: sub-pass e of wave pair w4 = channels 256 w4 + 32 e .. + 31 (half a 128-byte line) of all 128
     // pixels; item t of a lane = piece (lane & 3) (8 channels) of pixel 16 t + (lane >> 2): a quad of lanes = 64 contiguous
     // bytes.  The results of an even sub-pass wait in registers and are stored together with the odd one's: the two halves of a
     // line leave back to back (L2 hands part-written lines to the fabric as they are, profiles/r3)
-    const __amdgpu_buffer_rsrc_t rsrc_res = __builtin_amdgcn_make_buffer_rsrc(const_cast<__bf16*>(residual) + n0 * C4, 0, 0x7fffffff, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsrc_out = __builtin_amdgcn_make_buffer_rsrc(out + n0 * C4, 0, 0x7fffffff, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsrc_res = buffer_rsrc_unbounded(residual + n0 * C4);
+    const __amdgpu_buffer_rsrc_t rsrc_out = buffer_rsrc_unbounded(out + n0 * C4);
     // The quad -> pixel map is a permutation chosen for the LDS side (round 6): a ds_read_b128 is served in the lane
     // groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} (+ 32) and a quad covers 64 of a pixel row's 144 bytes in two
     // reads of alternate 16-byte slots, so with pp = lane >> 2 the quads of a group met on the same banks (two-way: 2 050
@@ -175,8 +170,8 @@ __global__ __launch_bounds__(THREADS, 1) void tail_io_bf16_kernel(
     role_barrier();                                          // [NRNG]: the last range has been read
     role_barrier();                                          // [1 + NRNG]: h2 complete (nothing of ours depends on it)
 
-    u32x4_t keep = {}, keep2 = {};
-    u32x4_t held[8];                                         // results of the even sub-pass of a pair
+    u32x4 keep = {}, keep2 = {};
+    u32x4 held[8];                                         // results of the even sub-pass of a pair
     static_assert(NSUB % RD == 0 && RD % 2 == 0, "the sub-pass loop is unrolled by the residual ring's depth; pairs inside");
     for (int e0 = 0; e0 < NSUB; e0 += RD) {
 #pragma unroll
@@ -203,7 +198,7 @@ __global__ __launch_bounds__(THREADS, 1) void tail_io_bf16_kernel(
           bf16x8 o;
 #pragma unroll
           for (int j = 0; j < 8; ++j) o[j] = (__bf16)fmaxf((sv[t][j >> 2][j & 3] + bv[j]) + (float)res[u][t][j], 0.f);
-          const u32x4_t o4 = __builtin_bit_cast(u32x4_t, o);
+          const u32x4 o4 = __builtin_bit_cast(u32x4, o);
           if ((u & 1) == 0) {
             held[t] = o4;
           } else {

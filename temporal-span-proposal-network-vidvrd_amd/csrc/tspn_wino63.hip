@@ -37,12 +37,11 @@
 #include <type_traits>
 
 #include "tspn_common.h"
+#include "tspn_device.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
+using namespace tspn_dev;
 
 constexpr int NW = 4;                     // waves per workgroup: one per SIMD, 512 registers each
 constexpr int THREADS = 64 * NW;
@@ -69,10 +68,6 @@ constexpr size_t SMEM_BYTES = sizeof(float) * NVB * VSS;
 #ifndef TSPN_WINO63_VAUX
 #define TSPN_WINO63_VAUX 0                // cache policy bits of the V bursts (2 = nt: 29.2 M KiB fetched but 27.6 ms)
 #endif
-__device__ __forceinline__ void glds16(const float* g, float* l) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)l, 16, 0, TSPN_WINO63_VAUX);
-}
 
 // nn.Conv1d weight W [M, Cin, 3] -> fragment-major transformed weights
 //   frag[m' / 32][chunk = ch / 8][j = 0..7][lane = 32 kh + li][e = 0..3] = U_j[8 chunk + 4 kh + e][32 (m'/32) + li]
@@ -109,6 +104,65 @@ __global__ void pack_wino63_frag_kernel(const float* __restrict__ W, int64_t M, 
   }
 }
 
+// ---- pieces of the F(6,3) input transform, shared by the fp32 form and the split-fp16 form below: the two must agree bit
+// for bit (the accuracy guard treats them as one algorithm).
+// The eight frames 6 q - 1 .. 6 q + 6 of sextet q of tracklet b, four channels from `channel_offset`.  Frames outside the
+// tracklet are zero (the conv's padding) and so is a sextet past the end of the launch (!ok); their addresses are clamped.
+__device__ __forceinline__ void wino63_load_sextet(const float* __restrict__ x, int64_t b, int q, int T, int Cin,
+                                                   int64_t ncols, bool ok, int channel_offset, f32x4 (&d)[8]) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int t = 6 * q + i - 1;
+    int64_t n = b * T + t;
+    n = n < 0 ? 0 : (n < ncols ? n : ncols - 1);
+    const f32x4 v = *reinterpret_cast<const f32x4*>(x + n * Cin + channel_offset);
+    d[i] = (ok && t >= 0 && t < T) ? v : f32x4{0.f, 0.f, 0.f, 0.f};
+  }
+}
+// V = B^T d
+__device__ __forceinline__ void wino63_bt(const f32x4 (&d)[8], f32x4 (&V)[8]) {
+  V[0] = d[0] - d[6] + 5.25f * (d[4] - d[2]);
+  V[7] = d[7] - d[1] + 5.25f * (d[3] - d[5]);
+  {
+    const f32x4 t1 = d[2] + d[6] - 4.25f * d[4], t2 = d[1] + d[5] - 4.25f * d[3];
+    V[1] = t1 + t2;
+    V[2] = t1 - t2;
+  }
+  {
+    const f32x4 t1 = d[6] + 0.25f * d[2] - 1.25f * d[4], t2 = 0.5f * d[1] - 2.5f * d[3] + 2.f * d[5];
+    V[3] = t1 + t2;
+    V[4] = t1 - t2;
+  }
+  {
+    const f32x4 t1 = d[6] + 4.f * (d[2] - 1.25f * d[4]), t2 = 2.f * d[1] - 2.5f * d[3] + 0.5f * d[5];
+    V[5] = t1 + t2;
+    V[6] = t1 - t2;
+  }
+}
+// m = max(m, |d[1..6]|) for the hot-sextet key.  NaN-propagating maxima (fmaxf drops NaN): a NaN input makes its sextet
+// hot, and |NaN| (sign cleared by fabsf) has larger bits than +Inf, so NaN ranks above Inf in the key.  Only the sextet's
+// OWN frames d[1..6] count: a value in the halo d[0] / d[7] enters one transformed column of the neighbour (one of its
+// outputs), while the sextet that holds it carries it into all six -- with the window counted, the equal keys of both went
+// to the later sextet.
+__device__ __forceinline__ void wino63_absmax_own_frames(const f32x4 (&d)[8], float& m) {
+#pragma unroll
+  for (int i = 1; i < 7; ++i)
+    m = __builtin_elementwise_maximum(
+        __builtin_elementwise_maximum(m, __builtin_elementwise_maximum(fabsf(d[i][0]), fabsf(d[i][1]))),
+        __builtin_elementwise_maximum(fabsf(d[i][2]), fabsf(d[i][3])));
+}
+// the wave's largest key into slot `slot` of `hot`: one 64-bit atomic max per wave, no return value
+__device__ __forceinline__ void wino63_hot_publish(unsigned long long* __restrict__ hot, unsigned long long key, unsigned slot) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(key, o, 64);
+    key = other > key ? other : key;
+  }
+  if ((threadIdx.x & 63) == 0)
+    __hip_atomic_fetch_max(hot + 32 * (slot & (TSPN_CONV_CHECK_HOT_SLOTS - 1)), key, __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Input transform V = B^T d.  A wave = 8 sextets x 8 channel groups (loads: whole 128-byte lines of x; stores:
 // 128-byte runs of Vg).  Frames outside the tracklet are zero (the conv's padding); sextets past the end of the
 // launch are zero too.
@@ -129,68 +183,18 @@ __global__ __launch_bounds__(256) void wino63_input_transform_kernel(
   const bool ok = S < nsext;
   const int64_t b = ok ? S / nq : 0;
   const int q = ok ? (int)(S - b * nq) : 0;
-  f32x4 d[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int t = 6 * q + i - 1;
-    int64_t n = b * T + t;
-    n = n < 0 ? 0 : (n < ncols ? n : ncols - 1);
-    const f32x4 v = *reinterpret_cast<const f32x4*>(x + n * Cin + 4 * cg);
-    d[i] = (ok && t >= 0 && t < T) ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-  }
+  f32x4 d[8], V[8];
+  wino63_load_sextet(x, b, q, T, Cin, ncols, ok, 4 * cg, d);
   if (hot) {                                                         // uniform
-    // NaN-propagating maxima (fmaxf drops NaN): a NaN input makes its sextet hot, and |NaN| (sign cleared by fabsf)
-    // has larger bits than +Inf, so NaN ranks above Inf in the key.  Only the sextet's OWN frames d[1..6] count: a value
-    // in the halo d[0] / d[7] enters one transformed column of the neighbour (one of its outputs), while the sextet that
-    // holds it carries it into all six -- with the window counted, the equal keys of both went to the later sextet.
     float m = 0.f;
-#pragma unroll
-    for (int i = 1; i < 7; ++i)
-      m = __builtin_elementwise_maximum(
-          __builtin_elementwise_maximum(m, __builtin_elementwise_maximum(fabsf(d[i][0]), fabsf(d[i][1]))),
-          __builtin_elementwise_maximum(fabsf(d[i][2]), fabsf(d[i][3])));
-    unsigned long long key = ((unsigned long long)__float_as_uint(m) << 32) | (unsigned)(S < nsext ? S : 0);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long other = __shfl_xor(key, o, 64);
-      key = other > key ? other : key;
-    }
-    if (lane == 0)
-      __hip_atomic_fetch_max(hot + 32 * ((blockIdx.x * 4 + wave + 7 * blockIdx.y) & (TSPN_CONV_CHECK_HOT_SLOTS - 1)), key,
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    wino63_absmax_own_frames(d, m);
+    wino63_hot_publish(hot, ((unsigned long long)__float_as_uint(m) << 32) | (unsigned)(S < nsext ? S : 0),
+                       blockIdx.x * 4 + wave + 7 * blockIdx.y);
   }
-  f32x4 V[8];
-  V[0] = d[0] - d[6] + 5.25f * (d[4] - d[2]);
-  V[7] = d[7] - d[1] + 5.25f * (d[3] - d[5]);
-  {
-    const f32x4 t1 = d[2] + d[6] - 4.25f * d[4], t2 = d[1] + d[5] - 4.25f * d[3];
-    V[1] = t1 + t2;
-    V[2] = t1 - t2;
-  }
-  {
-    const f32x4 t1 = d[6] + 0.25f * d[2] - 1.25f * d[4], t2 = 0.5f * d[1] - 2.5f * d[3] + 2.f * d[5];
-    V[3] = t1 + t2;
-    V[4] = t1 - t2;
-  }
-  {
-    const f32x4 t1 = d[6] + 4.f * (d[2] - 1.25f * d[4]), t2 = 2.f * d[1] - 2.5f * d[3] + 0.5f * d[5];
-    V[5] = t1 + t2;
-    V[6] = t1 - t2;
-  }
+  wino63_bt(d, V);
 #pragma unroll
   for (int j = 0; j < 8; ++j)
     *reinterpret_cast<f32x4*>(Vg + (((int64_t)cg * NJ + j) * nsp + S) * 4) = V[j];
-}
-
-// The weight loads are inline asm (the compiler does not see them as asynchronous), so every use of
-// their destination registers is preceded by one of these counted waits, tied to the registers by "+v".
-template <int VM>
-__device__ __forceinline__ void wait_a(f32x4& r0, f32x4& r1) {
-  asm volatile("s_waitcnt vmcnt(%2)" : "+v"(r0), "+v"(r1) : "n"(VM));
-}
-template <int OFF>
-__device__ __forceinline__ void load_frag(f32x4& dst, unsigned lane_off, const char* base) {
-  asm volatile("global_load_dwordx4 %0, %1, %2 offset:%3" : "=v"(dst) : "v"(lane_off), "s"(base), "n"(OFF) : "memory");
 }
 
 // BUFV: the V pieces are buffer loads (buffer_load_dwordx4 ... offen lds: one SGPR descriptor of the workspace, a fixed
@@ -247,15 +251,14 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
     if constexpr (BUFV) voff[k] = (unsigned)(e * 4); else vsrc[k] = Vg + e;
   }
   const int64_t super_step = (int64_t)8 * NJ * nsp * 4;
-  const __amdgpu_buffer_rsrc_t rsrc_v = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(Vg), 0, (int)0xffffffffu, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_v = buffer_rsrc(Vg, (int)0xffffffffu);
   const unsigned super_bytes = (unsigned)(super_step * 4);
   auto stage_piece = [&](int S, int k) {          // piece k of this wave, super-stage S -> ring buffer S & 1
     if constexpr (BUFV) {
       const int soff = (int)((unsigned)S * super_bytes);
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc_v, (__attribute__((address_space(3))) void*)(Vs + (S & 1) * VSS + (NPIECE * wave + k) * 256),
-                                               16, (int)voff[k], soff, 0, 0);
+      bglds16(rsrc_v, voff[k], soff, Vs + (S & 1) * VSS + (NPIECE * wave + k) * 256);
     } else {
-      glds16(vsrc[k], Vs + (S & 1) * VSS + (NPIECE * wave + k) * 256);
+      glds16<TSPN_WINO63_VAUX>(vsrc[k], Vs + (S & 1) * VSS + (NPIECE * wave + k) * 256);
     }
     if constexpr (!BUFV) vsrc[k] += super_step;
   };
@@ -276,10 +279,10 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
   };
   auto load_a_pair = [&](f32x4* ap, auto jp_tag, const char* base) {     // positions 2 jp, 2 jp + 1 of the chunk at base
     constexpr int JP = decltype(jp_tag)::value;
-    if (JP == 0) { load_frag<0>(ap[0], aoff, base); load_frag<1024>(ap[1], aoff, base); }
-    if (JP == 1) { load_frag<2048>(ap[2], aoff, base); load_frag<3072>(ap[3], aoff, base); }
-    if (JP == 2) { load_frag<0>(ap[4], aoff, base + 4096); load_frag<1024>(ap[5], aoff, base + 4096); }
-    if (JP == 3) { load_frag<2048>(ap[6], aoff, base + 4096); load_frag<3072>(ap[7], aoff, base + 4096); }
+    if (JP == 0) { load_wfrag<0>(ap[0], aoff, base); load_wfrag<1024>(ap[1], aoff, base); }
+    if (JP == 1) { load_wfrag<2048>(ap[2], aoff, base); load_wfrag<3072>(ap[3], aoff, base); }
+    if (JP == 2) { load_wfrag<0>(ap[4], aoff, base + 4096); load_wfrag<1024>(ap[5], aoff, base + 4096); }
+    if (JP == 3) { load_wfrag<2048>(ap[6], aoff, base + 4096); load_wfrag<3072>(ap[7], aoff, base + 4096); }
   };
   using P0 = std::integral_constant<int, 0>;
   using P1 = std::integral_constant<int, 1>;
@@ -335,22 +338,22 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
     const float* vn = CL == 3 ? vnext : vcur;
     constexpr int NCL = (CL + 1) & 3;
     f32x4* ap = a[PAR];
-    wait_a<3 * N2 + N1>(ap[0], ap[1]);
+    wait_w<3 * N2 + N1>(ap[0], ap[1]);
     mfma_pair(ap, 0, 1, S1, 0);
     if (HAS2) load_a_pair(ap, P0{}, abase);
     if (HAS1) { load_v(vn, NCL, 0); load_v(vn, NCL, 1); }
     __builtin_amdgcn_sched_barrier(0);
-    wait_a<2 * N2 + N1 + N0>(ap[2], ap[3]);
+    wait_w<2 * N2 + N1 + N0>(ap[2], ap[3]);
     mfma_pair(ap, 2, 3, S1, 1);
     if (HAS2) load_a_pair(ap, P1{}, abase);
     if (HAS1) { load_v(vn, NCL, 2); load_v(vn, NCL, 3); }
     __builtin_amdgcn_sched_barrier(0);
-    wait_a<N2 + N1 + 2 * N0>(ap[4], ap[5]);
+    wait_w<N2 + N1 + 2 * N0>(ap[4], ap[5]);
     mfma_pair(ap, 4, 5, S1, 2);
     if (HAS2) load_a_pair(ap, P2{}, abase);
     if (HAS1) { load_v(vn, NCL, 4); load_v(vn, NCL, 5); }
     __builtin_amdgcn_sched_barrier(0);
-    wait_a<N1 + 3 * N0>(ap[6], ap[7]);
+    wait_w<N1 + 3 * N0>(ap[6], ap[7]);
     mfma_pair(ap, 6, 7, S1, 3);
     if (HAS2) {
       load_a_pair(ap, P3{}, abase);
@@ -460,8 +463,6 @@ constexpr size_t F_SMEM = (size_t)F_NST * F_ST;
 constexpr size_t F_SMEM_ALL = F_SMEM + 2 * 256 * sizeof(int);   // + the exponent table of the unscale
 constexpr size_t F_PARK_PER_TILE = (size_t)7 * F_THREADS * 128 * sizeof(float);   // points 0..6 of a tile, fp32
 
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
 // power-of-two exponent e with max * 2^e in [2^14, 2^15); 0 for a zero or non-finite maximum (a non-finite value then
 // stays non-finite through the split, and so does every output it reaches)
 __device__ __forceinline__ int split_exponent(double mx) {
@@ -519,7 +520,7 @@ __global__ void pack_wino63_frag_kernel(const float* __restrict__ W, int64_t M, 
   *reinterpret_cast<int4*>(pj + (2 * ncg * Mp + m) * 8) = int4{e, 0, 0, 0};   // the whole slot: no undefined bytes
 }
 
-// Split input transform: V = B^T d exactly as the fp32 form computes it, then one scale per (sextet, point) column over
+// Split input transform: V = B^T d by the functions the fp32 form uses, then one scale per (sextet, point) column over
 // ALL Cin channels, so a workgroup owns whole columns: 8 sextets x all channels; thread = (sextet s = tid & 7, channel
 // group slot tid >> 3 of 32), 8 channels per group.  Pass 1 takes the column maxima (and the guard's hot-sextet key),
 // pass 2 recomputes V (the x lines are in L2 by then) and writes the hi / lo halves: for each (j, channel group) the
@@ -539,38 +540,9 @@ __global__ __launch_bounds__(256) void wino63_input_transform_kernel(
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       f32x4 d[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const int t = 6 * q + i - 1;
-        int64_t n = b * T + t;
-        n = n < 0 ? 0 : (n < ncols ? n : ncols - 1);
-        const f32x4 v = *reinterpret_cast<const f32x4*>(x + n * Cin + 8 * cg + 4 * h);
-        d[i] = (ok && t >= 0 && t < T) ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-      if (want_max) {
-#pragma unroll
-        for (int i = 1; i < 7; ++i)
-          xmax = __builtin_elementwise_maximum(
-              __builtin_elementwise_maximum(xmax, __builtin_elementwise_maximum(fabsf(d[i][0]), fabsf(d[i][1]))),
-              __builtin_elementwise_maximum(fabsf(d[i][2]), fabsf(d[i][3])));
-      }
-      V[h][0] = d[0] - d[6] + 5.25f * (d[4] - d[2]);
-      V[h][7] = d[7] - d[1] + 5.25f * (d[3] - d[5]);
-      {
-        const f32x4 t1 = d[2] + d[6] - 4.25f * d[4], t2 = d[1] + d[5] - 4.25f * d[3];
-        V[h][1] = t1 + t2;
-        V[h][2] = t1 - t2;
-      }
-      {
-        const f32x4 t1 = d[6] + 0.25f * d[2] - 1.25f * d[4], t2 = 0.5f * d[1] - 2.5f * d[3] + 2.f * d[5];
-        V[h][3] = t1 + t2;
-        V[h][4] = t1 - t2;
-      }
-      {
-        const f32x4 t1 = d[6] + 4.f * (d[2] - 1.25f * d[4]), t2 = 2.f * d[1] - 2.5f * d[3] + 0.5f * d[5];
-        V[h][5] = t1 + t2;
-        V[h][6] = t1 - t2;
-      }
+      wino63_load_sextet(x, b, q, T, Cin, ncols, ok, 8 * cg + 4 * h, d);
+      if (want_max) wino63_absmax_own_frames(d, xmax);
+      wino63_bt(d, V[h]);
     }
   };
   // ---- pass 1: column maxima (NaN-propagating), hot-sextet key
@@ -589,17 +561,9 @@ __global__ __launch_bounds__(256) void wino63_input_transform_kernel(
             __builtin_elementwise_maximum(cmax[j], __builtin_elementwise_maximum(fabsf(V[h][j][0]), fabsf(V[h][j][1]))),
             __builtin_elementwise_maximum(fabsf(V[h][j][2]), fabsf(V[h][j][3])));
   }
-  if (hot) {                                                       // uniform; as in the fp32 transform
-    unsigned long long key = ((unsigned long long)__float_as_uint(xm) << 32) | (unsigned)(ok ? S : 0);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long other = __shfl_xor(key, o, 64);
-      key = other > key ? other : key;
-    }
-    if (lane == 0)
-      __hip_atomic_fetch_max(hot + 32 * ((blockIdx.x * 4 + wave) & (TSPN_CONV_CHECK_HOT_SLOTS - 1)), key,
-                             __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
+  if (hot)                                                         // uniform
+    wino63_hot_publish(hot, ((unsigned long long)__float_as_uint(xm) << 32) | (unsigned)(ok ? S : 0),
+                       blockIdx.x * 4 + wave);
 #pragma unroll
   for (int j = 0; j < NJ; ++j) {
     float m = cmax[j];
@@ -638,11 +602,6 @@ __global__ __launch_bounds__(256) void wino63_input_transform_kernel(
       *reinterpret_cast<f16x8*>(dst + (int64_t)ncg * nsp2 * 8) = lo;
     }
   }
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vm() {
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
 }
 
 // Split contraction.  Workgroup = 256 rows x 256 sextets, ALL 8 points one after another: per point a GEMM over the
@@ -703,8 +662,7 @@ __global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
     char* dst = smem_raw + (g & 3) * F_ST + (4 * wave) * 1024;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src[i] + j * jstride[i] + k * kstride[i]),
-                                       (__attribute__((address_space(3))) void*)(dst + i * 1024), 16, 0, 0);
+      glds16(src[i] + j * jstride[i] + k * kstride[i], dst + i * 1024);
   };
 
   f32x16 acc[4][2];
@@ -743,7 +701,7 @@ __global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
   if (G > 1) issue(1);
   if (G > 2) issue(2);
   for (int g = 0; g < G; ++g) {
-    if (g + 2 < G) wait_vm<8>(); else if (g + 1 < G) wait_vm<4>(); else wait_vm<0>();
+    if (g + 2 < G) wait_vmcnt<8>(); else if (g + 1 < G) wait_vmcnt<4>(); else wait_vmcnt<0>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();                   // stage g landed for every wave; stage g - 1 is read out
     __builtin_amdgcn_sched_barrier(0);
@@ -798,7 +756,7 @@ __global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
 
   // ---- inverse transform + bias + store: acc holds M7; M0..M6 come back from the parking area (this lane's own
   // stores, complete before they are read)
-  wait_vm<0>();
+  wait_vmcnt<0>();
 #pragma unroll
   for (int ni = 0; ni < 2; ++ni) {
     const int64_t Sx = S0 + wn * 64 + ni * 32 + li;

@@ -22,6 +22,7 @@ __all__ = [
     "proposal_pair_filter", "gather_rows", "wino63_set_piece_form", "conv3_spot_check",
     "pack_conv2d", "pack_conv2d_frag", "conv2d_nhwc", "roi_align_nhwc", "pack_conv2d_frag_bf16", "conv2d_nhwc_bf16", "max_pool_nhwc", "pack_conv2d_frag_cin4", "conv2d_nhwc_cin4", "max_pool_nhwc_bf16", "pack_stem_bf16", "stem_conv_bf16", "stem_pool_bf16", "bottleneck_tail_bf16",
     "eval_traj_volume", "eval_viou", "eval_greedy_match",
+    "status_words", "status_fault", "status_clear", "status_selftest",
 ]
 
 
@@ -1072,6 +1073,21 @@ def roi_align_nhwc(feat, rois, output_size, spatial_scale, sampling_ratio=0, ali
     return out
 
 
+def _frag_shape_bf16(cout, cin, taps):
+    """Shape of pack_conv2d_frag_bf16's result for a [cout, cin, KH, KW] weight with KH * KW = taps."""
+    return (cout // 32, cin // 64, taps, 4, 64, 8)
+
+
+def _out_bf16(out, shape, device, who):
+    """`out` checked to be a bf16 device tensor of `shape`, or a new one when None."""
+    if out is None:
+        return torch.empty(shape, dtype=torch.bfloat16, device=device)
+    _dev(out, "out", torch.bfloat16)
+    if tuple(out.shape) != tuple(shape):
+        raise ValueError(f"{who}: out must be {tuple(shape)}, got {tuple(out.shape)}")
+    return out
+
+
 def pack_conv2d_frag_bf16(weight):
     """fp32 nn.Conv2d weight [Cout,Cin,KH,KW] -> bf16 fragment-major [Cout/32, KH*KW, Cin/64, 4, 64, 8]
     (tspn_pack_conv2d_frag_bf16; rounded once, to nearest even).  Needs Cout % 32 == 0, Cin % 64 == 0."""
@@ -1081,7 +1097,7 @@ def pack_conv2d_frag_bf16(weight):
     Cout, Cin, KH, KW = weight.shape
     if Cout % 32 or Cin % 64:
         raise ValueError(f"pack_conv2d_frag_bf16: needs Cout % 32 == 0 and Cin % 64 == 0 (Cout={Cout}, Cin={Cin})")
-    frag = torch.empty((Cout // 32, Cin // 64, KH * KW, 4, 64, 8), dtype=torch.bfloat16, device=weight.device)
+    frag = torch.empty(_frag_shape_bf16(Cout, Cin, KH * KW), dtype=torch.bfloat16, device=weight.device)
     _abi.check(_abi.lib().tspn_pack_conv2d_frag_bf16(_p(weight), Cout, Cin, KH, KW, _p(frag), _stream()))
     return frag
 
@@ -1093,7 +1109,7 @@ def conv2d_nhwc_bf16(x, frag, kernel_size, stride=1, padding=0, bias=None, resid
     _dev(x, "x", torch.bfloat16); _dev(frag, "frag", torch.bfloat16)
     NB, H, W, Cin = x.shape
     KH, KW = kernel_size
-    if frag.dim() != 6 or tuple(frag.shape[1:]) != (Cin // 64, KH * KW, 4, 64, 8) or Cin % 64:
+    if frag.dim() != 6 or tuple(frag.shape[1:]) != _frag_shape_bf16(32, Cin, KH * KW)[1:] or Cin % 64:
         raise ValueError(f"conv2d_nhwc_bf16: weights {tuple(frag.shape)} do not match taps={KH * KW}, Cin={Cin}")
     Cout = frag.shape[0] * 32
     OH, OW = (H + 2 * padding - KH) // stride + 1, (W + 2 * padding - KW) // stride + 1
@@ -1139,18 +1155,13 @@ def bottleneck_block_bf16(x, frag1, bias1, frag2, bias2, frag3, bias3, out=None)
     CM = C4 // 4
     if CM not in (64, 128) or C4 != 4 * CM:
         raise ValueError(f"bottleneck_block_bf16: needs 4 x 64 or 4 x 128 channels (got {C4})")
-    if (tuple(frag1.shape) != (CM // 32, C4 // 64, 1, 4, 64, 8) or tuple(frag2.shape) != (CM // 32, CM // 64, 9, 4, 64, 8)
-            or tuple(frag3.shape) != (CM // 8, CM // 64, 1, 4, 64, 8)):
+    if (tuple(frag1.shape) != _frag_shape_bf16(CM, C4, 1) or tuple(frag2.shape) != _frag_shape_bf16(CM, CM, 9)
+            or tuple(frag3.shape) != _frag_shape_bf16(C4, CM, 1)):
         raise ValueError("bottleneck_block_bf16: frag1 / frag2 / frag3 must be pack_conv2d_frag_bf16 of [CM,4CM,1,1] / "
                          "[CM,CM,3,3] / [4CM,CM,1,1]")
     if bias1.shape != (CM,) or bias2.shape != (CM,) or bias3.shape != (C4,):
         raise ValueError("bottleneck_block_bf16: bias shape mismatch")
-    if out is None:
-        out = torch.empty_like(x)
-    else:
-        _dev(out, "out", torch.bfloat16)
-        if tuple(out.shape) != tuple(x.shape):
-            raise ValueError(f"bottleneck_block_bf16: out must be {tuple(x.shape)}, got {tuple(out.shape)}")
+    out = _out_bf16(out, x.shape, x.device, "bottleneck_block_bf16")
     _abi.check(_abi.lib().tspn_bottleneck_block_bf16(_p(x), NB, H, W, CM, _p(frag1), _p(bias1), _p(frag2), _p(bias2),
                                                      _p(frag3), _p(bias3), _p(out), _stream()))
     return out
@@ -1170,18 +1181,13 @@ def bottleneck_block_proj_bf16(x, stride, frag1, bias1, frag2, bias2, frag3, bia
     CM = frag2.shape[0] * 32
     if (CIN, CM, int(stride)) != (64, 64, 1):
         raise ValueError(f"bottleneck_block_proj_bf16: built for (CIN, CM, stride) = (64, 64, 1), got {(CIN, CM, stride)}")
-    if (tuple(frag1.shape) != (CM // 32, CIN // 64, 1, 4, 64, 8) or tuple(frag2.shape) != (CM // 32, CM // 64, 9, 4, 64, 8)
-            or tuple(frag3.shape) != (CM // 8, CM // 64, 1, 4, 64, 8) or tuple(frags.shape) != (CM // 8, CIN // 64, 1, 4, 64, 8)):
+    if (tuple(frag1.shape) != _frag_shape_bf16(CM, CIN, 1) or tuple(frag2.shape) != _frag_shape_bf16(CM, CM, 9)
+            or tuple(frag3.shape) != _frag_shape_bf16(4 * CM, CM, 1) or tuple(frags.shape) != _frag_shape_bf16(4 * CM, CIN, 1)):
         raise ValueError("bottleneck_block_proj_bf16: fragment shapes do not match [CM,CIN,1,1] / [CM,CM,3,3] / [4CM,CM,1,1] / [4CM,CIN,1,1]")
     if bias1.shape != (CM,) or bias2.shape != (CM,) or bias3.shape != (4 * CM,) or biass.shape != (4 * CM,):
         raise ValueError("bottleneck_block_proj_bf16: bias shape mismatch")
     H, W = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
-    if out is None:
-        out = torch.empty((NB, H, W, 4 * CM), dtype=torch.bfloat16, device=x.device)
-    else:
-        _dev(out, "out", torch.bfloat16)
-        if tuple(out.shape) != (NB, H, W, 4 * CM):
-            raise ValueError(f"bottleneck_block_proj_bf16: out must be {(NB, H, W, 4 * CM)}, got {tuple(out.shape)}")
+    out = _out_bf16(out, (NB, H, W, 4 * CM), x.device, "bottleneck_block_proj_bf16")
     _abi.check(_abi.lib().tspn_bottleneck_block_proj_bf16(_p(x), NB, Hin, Win, CIN, int(stride), CM, _p(frag1), _p(bias1),
                                                           _p(frag2), _p(bias2), _p(frag3), _p(bias3), _p(frags), _p(biass),
                                                           _p(out), _stream()))
@@ -1201,18 +1207,13 @@ def bottleneck_block_res_bf16(x, stride, frag1, bias1, frag2, bias2, frag3, bias
     CM = frag2.shape[0] * 32
     if (CIN, CM, int(stride)) != (256, 128, 2):
         raise ValueError(f"bottleneck_block_res_bf16: built for (CIN, CM, stride) = (256, 128, 2), got {(CIN, CM, stride)}")
-    if (tuple(frag1.shape) != (CM // 32, CIN // 64, 1, 4, 64, 8) or tuple(frag2.shape) != (CM // 32, CM // 64, 9, 4, 64, 8)
-            or tuple(frag3.shape) != (CM // 8, CM // 64, 1, 4, 64, 8)):
+    if (tuple(frag1.shape) != _frag_shape_bf16(CM, CIN, 1) or tuple(frag2.shape) != _frag_shape_bf16(CM, CM, 9)
+            or tuple(frag3.shape) != _frag_shape_bf16(4 * CM, CM, 1)):
         raise ValueError("bottleneck_block_res_bf16: fragment shapes do not match [CM,CIN,1,1] / [CM,CM,3,3] / [4CM,CM,1,1]")
     H, W = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
     if bias1.shape != (CM,) or bias2.shape != (CM,) or bias3.shape != (4 * CM,) or tuple(residual.shape) != (NB, H, W, 4 * CM):
         raise ValueError("bottleneck_block_res_bf16: bias / residual shape mismatch")
-    if out is None:
-        out = torch.empty((NB, H, W, 4 * CM), dtype=torch.bfloat16, device=x.device)
-    else:
-        _dev(out, "out", torch.bfloat16)
-        if tuple(out.shape) != (NB, H, W, 4 * CM):
-            raise ValueError(f"bottleneck_block_res_bf16: out must be {(NB, H, W, 4 * CM)}, got {tuple(out.shape)}")
+    out = _out_bf16(out, (NB, H, W, 4 * CM), x.device, "bottleneck_block_res_bf16")
     _abi.check(_abi.lib().tspn_bottleneck_block_res_bf16(_p(x), NB, Hin, Win, CIN, int(stride), CM, _p(frag1), _p(bias1), _p(frag2),
                                                          _p(bias2), _p(frag3), _p(bias3), _p(residual), _p(out), _stream()))
     return out
@@ -1237,16 +1238,11 @@ def bottleneck_tail_bf16(h1, frag2, bias2, frag3, bias3, residual, out=None, nex
     NB, H, W, CM = h1.shape
     if CM not in (64, 128, 256):
         raise ValueError(f"bottleneck_tail_bf16: bottleneck channels must be 64, 128 or 256 (got {CM})")
-    if tuple(frag2.shape) != (CM // 32, CM // 64, 9, 4, 64, 8) or tuple(frag3.shape) != (CM // 8, CM // 64, 1, 4, 64, 8):
+    if tuple(frag2.shape) != _frag_shape_bf16(CM, CM, 9) or tuple(frag3.shape) != _frag_shape_bf16(4 * CM, CM, 1):
         raise ValueError("bottleneck_tail_bf16: frag2 / frag3 must be pack_conv2d_frag_bf16 of [CM,CM,3,3] / [4CM,CM,1,1]")
     if bias2.shape != (CM,) or bias3.shape != (4 * CM,) or tuple(residual.shape) != (NB, H, W, 4 * CM):
         raise ValueError("bottleneck_tail_bf16: bias / residual shape mismatch")
-    if out is None:
-        out = torch.empty((NB, H, W, 4 * CM), dtype=torch.bfloat16, device=h1.device)
-    else:
-        _dev(out, "out", torch.bfloat16)
-        if tuple(out.shape) != (NB, H, W, 4 * CM):
-            raise ValueError(f"bottleneck_tail_bf16: out must be {(NB, H, W, 4 * CM)}, got {tuple(out.shape)}")
+    out = _out_bf16(out, (NB, H, W, 4 * CM), h1.device, "bottleneck_tail_bf16")
     if io_waves:
         # (CM = 256) the role-split kernel: four MFMA waves + four waves that do all HBM traffic (tspn_bottleneck_tail_io_bf16)
         if CM != 256 or next_frag1 is not None or persistent:
@@ -1264,7 +1260,7 @@ def bottleneck_tail_bf16(h1, frag2, bias2, frag3, bias3, residual, out=None, nex
         _dev(next_frag1, "next_frag1", torch.bfloat16); _dev(next_bias1, "next_bias1")
         if CM != 256:
             raise ValueError(f"bottleneck_tail_bf16: the fused next conv1 needs 256 bottleneck channels (got {CM})")
-        if tuple(next_frag1.shape) != (CM // 32, 4 * CM // 64, 1, 4, 64, 8) or next_bias1.shape != (CM,):
+        if tuple(next_frag1.shape) != _frag_shape_bf16(CM, 4 * CM, 1) or next_bias1.shape != (CM,):
             raise ValueError("bottleneck_tail_bf16: next_frag1 must be pack_conv2d_frag_bf16 of [CM,4CM,1,1], next_bias1 [CM]")
         h1n = torch.empty((NB, H, W, CM), dtype=torch.bfloat16, device=h1.device)
         _abi.check(_abi.lib().tspn_bottleneck_tail_next_bf16(
@@ -1440,6 +1436,6 @@ def eval_greedy_match(ov, groups, n_pred, viou_threshold, max_group_gt, det_ws=N
 
 # every public operator runs with the device of its operands made current (see _on_tensor_device)
 for _name in __all__:
-    if _name not in ("pair_index", "fused_workspace_bytes"):
+    if _name not in ("pair_index", "fused_workspace_bytes") and not _name.startswith("status_"):
         globals()[_name] = _on_tensor_device(globals()[_name])
 del _name
