@@ -95,6 +95,25 @@ extern "C" int tspn_forward_fused_f32(const tspn_fused_desc* d, void* stream) {
   const int64_t NT = d->B * d->N, T = d->T, D = d->D, C = 2 * D, H = 3 * d->A;
   hipStream_t s = TSPN_STREAM(stream);
 
+  // The conv algorithm and its refusals, before anything is launched (a refused pass leaves both outputs untouched).
+  // The channels-last kernel consumes the tracklet layout [NT,T,D] directly; ragged shapes go
+  // through a transpose to channels-first [NT,D,T] and the general kernel.
+  const bool tc = (D % 16 == 0) && ((reinterpret_cast<uintptr_t>(d->feats) & 15) == 0) &&
+                  ((reinterpret_cast<uintptr_t>(d->conv_packed) & 15) == 0);
+  TSPN_REQUIRE(d->conv_algo == TSPN_CONV_DIRECT || d->conv_algo == TSPN_CONV_WINOGRAD63 ||
+                   d->conv_algo == TSPN_CONV_WINOGRAD63_F16X3,
+               TSPN_EINVAL,
+               "tspn_forward_fused: conv_algo must be TSPN_CONV_DIRECT (0), TSPN_CONV_WINOGRAD63 (1) or "
+               "TSPN_CONV_WINOGRAD63_F16X3 (2), got %d",
+               (int)d->conv_algo);
+  const bool f16x3 = d->conv_algo == TSPN_CONV_WINOGRAD63_F16X3;
+  const bool w63 = d->conv_algo == TSPN_CONV_WINOGRAD63 || f16x3;
+  TSPN_REQUIRE(!w63 || (tc && tspn::wino63_supported(D, 2 * C)), TSPN_EUNSUPPORTED,
+               "tspn_forward_fused: TSPN_CONV_WINOGRAD63 needs D %% 32 == 0 and 16-byte aligned operands "
+               "(pack the weights with tspn_pack_conv3_f32 and pass TSPN_CONV_DIRECT otherwise)");
+  TSPN_REQUIRE(!f16x3 || tspn::wino63_f16x3_supported(D, 2 * C), TSPN_EUNSUPPORTED,
+               "tspn_forward_fused: TSPN_CONV_WINOGRAD63_F16X3 needs D %% 64 == 0 (4D %% 256 == 0)");
+
   // bias of the encoder goes with the subject projection: bias2 = [conv_bias, 0]
   hipError_t e = hipMemsetAsync(bias2 + C, 0, C * sizeof(float), s);
   if (e == hipSuccess)
@@ -113,23 +132,6 @@ extern "C" int tspn_forward_fused_f32(const tspn_fused_desc* d, void* stream) {
   if (d->ev_logits_ready) (void)hipEventRecord(static_cast<hipEvent_t>(d->ev_logits_ready), s);
 
   // 1+2. per-tracklet projections  y[NT, 2C, T]: rows [0,C) = U (+bias), rows [C,2C) = V.
-  // The channels-last kernel consumes the tracklet layout [NT,T,D] directly; ragged shapes go
-  // through a transpose to channels-first [NT,D,T] and the general kernel.
-  const bool tc = (D % 16 == 0) && ((reinterpret_cast<uintptr_t>(d->feats) & 15) == 0) &&
-                  ((reinterpret_cast<uintptr_t>(d->conv_packed) & 15) == 0);
-  TSPN_REQUIRE(d->conv_algo == TSPN_CONV_DIRECT || d->conv_algo == TSPN_CONV_WINOGRAD63 ||
-                   d->conv_algo == TSPN_CONV_WINOGRAD63_F16X3,
-               TSPN_EINVAL,
-               "tspn_forward_fused: conv_algo must be TSPN_CONV_DIRECT (0), TSPN_CONV_WINOGRAD63 (1) or "
-               "TSPN_CONV_WINOGRAD63_F16X3 (2), got %d",
-               (int)d->conv_algo);
-  const bool f16x3 = d->conv_algo == TSPN_CONV_WINOGRAD63_F16X3;
-  const bool w63 = d->conv_algo == TSPN_CONV_WINOGRAD63 || f16x3;
-  TSPN_REQUIRE(!w63 || (tc && tspn::wino63_supported(D, 2 * C)), TSPN_EUNSUPPORTED,
-               "tspn_forward_fused: TSPN_CONV_WINOGRAD63 needs D %% 32 == 0 and 16-byte aligned operands "
-               "(pack the weights with tspn_pack_conv3_f32 and pass TSPN_CONV_DIRECT otherwise)");
-  TSPN_REQUIRE(!f16x3 || tspn::wino63_f16x3_supported(D, 2 * C), TSPN_EUNSUPPORTED,
-               "tspn_forward_fused: TSPN_CONV_WINOGRAD63_F16X3 needs D %% 64 == 0 (4D %% 256 == 0)");
   // On the fast path the rows of y are padded to ldy = ceil4(T) frames so that the blocked pair stage
   // can stage them with 16-byte LDS-DMA pieces that never leave a row (pad frames are never read out).
   // (needs what the DMA pair-stage kernel needs: even T, C % 16 == 0 — implied by tc)

@@ -1043,6 +1043,16 @@ int tspn::wino63_f16x3_contract(void* workspace, size_t workspace_bytes, int64_t
 extern "C" int tspn_conv3_tc_wino63_f16x3(const float* x, int64_t B, int64_t T, int64_t Cin, const int16_t* packed,
                                           int64_t M, const float* bias, int relu, float* y, void* workspace,
                                           size_t workspace_bytes, void* stream) {
+  // every refusal of the contraction before the transform is launched: a refused call launches nothing
+  const char* what = "tspn_conv3_tc_wino63_f16x3";
+  if (int rc = check_common(what, B, T, Cin, M, T)) return rc;
+  TSPN_REQUIRE(tspn::wino63_f16x3_supported(Cin, M), TSPN_EUNSUPPORTED,
+               "%s: needs Cin %% 32 == 0 and M %% 256 == 0 (Cin=%lld M=%lld)", what, (long long)Cin, (long long)M);
+  if (B > 0) {
+    TSPN_REQUIRE(workspace && packed && y, TSPN_EINVAL, "%s: null pointer", what);
+    TSPN_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0,
+                 TSPN_EUNSUPPORTED, "%s: packed weights must be 16-byte aligned", what);
+  }
   if (int rc = tspn::wino63_f16x3_input_transform(x, B, T, Cin, M, workspace, workspace_bytes, stream)) return rc;
   return tspn::wino63_f16x3_contract(workspace, workspace_bytes, B, T, Cin, packed, M, bias, relu, y, T, stream);
 }

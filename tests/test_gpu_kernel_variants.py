@@ -369,3 +369,220 @@ def test_conv2d_nhwc_bf16_mi2_without_ring(tspn, device, NB, H, W, Cin, Cout, k,
     got = y.cpu().double()
     tol = ref.abs() * 2.0 ** -8 + 3e-5
     assert bool(((got - ref).abs() <= tol).all()), float(((got - ref).abs() - tol).max())
+
+
+# ------------------------------------------------------------------- split-fp16 F(6,3) (tspn_wino63.hip overloads)
+# Against float64 conv1d at the split form's tolerances of tests/test_gpu_wino63_f16x3.py: 6e-5 absolute at these
+# magnitudes and 64 eps sum|x||w|.  The output is caller-held and pre-filled: no element may keep the sentinel, and
+# the 32 floats in front of and behind it must keep it.
+SENTINEL = np.float32(-3.0e33)
+F_BM = F_BN = 256     # contraction tile (rows x sextets), GM = 4 row tiles per group, 8 XCDs: tspn_wino63.hip
+F_GM = 4
+
+
+def conv_tc_ref64(x, w):
+    """x [B,T,Cin], w [M,Cin,3] -> (conv, sum |x||w|), float64 [B,M,T]."""
+    xt, wt = t(x).double().transpose(1, 2), t(w).double()
+    return (torch.nn.functional.conv1d(xt, wt, padding=1).numpy(),
+            torch.nn.functional.conv1d(xt.abs(), wt.abs(), padding=1).numpy())
+
+
+def held_output(shape, device, offset=0):
+    """(buffer, view): a sentinel-filled buffer and a contiguous view of `shape` 32 + offset floats into it."""
+    n = int(np.prod(shape))
+    buf = torch.full((n + 64 + offset,), float(SENTINEL), dtype=torch.float32, device=device)
+    v = buf[32 + offset:32 + offset + n].view(shape)
+    assert v.data_ptr() % 8 == (4 if offset % 2 else 0)
+    return buf, v
+
+
+def f16x3_raw(tspn, x, pk, bias, relu, y, ws=None, ws_bytes=None, M=None):
+    """tspn_conv3_tc_wino63_f16x3 on a caller-held y (and workspace); raises TspnError on a refusal."""
+    B, T, Cin = x.shape
+    M = tspn.ops.wino63_f16x3_dims(pk)[1] if M is None else M
+    l = tspn._abi.lib()
+    if ws is None:
+        ws = torch.empty(max(l.tspn_conv3_tc_wino63_f16x3_workspace_bytes(B, T, Cin, M), 256), dtype=torch.uint8,
+                         device=x.device)
+    tspn._abi.check(l.tspn_conv3_tc_wino63_f16x3(p(x), B, T, Cin, p(pk), M, p(bias), 1 if relu else 0, p(y), p(ws),
+                                                 ws.numel() if ws_bytes is None else ws_bytes, tspn.ops._stream()))
+    return y
+
+
+def check_f16x3(buf, y, ref, mag, what):
+    got = y.cpu().numpy()
+    n = y.numel()
+    edge = torch.cat([buf[:buf.numel() - n - 32], buf[buf.numel() - 32:]]).cpu().numpy()
+    assert (edge == SENTINEL).all(), f"{what}: wrote outside y"
+    assert not (got == SENTINEL).any(), f"{what}: {int((got == SENTINEL).sum())} outputs never written"
+    e = np.abs(got - ref)
+    assert e.max() <= 6e-5, f"{what}: max error {e.max():.3g}"
+    r = (e / (2.0 ** -24 * mag + 1e-300)).max()
+    assert r <= 64.0, f"{what}: {r:.3g} eps sum|x||w|"
+
+
+def run_f16x3_case(tspn, device, B, T, Cin, M, seed, offset=0, combos=((True, False), (False, True), (True, True), (False, False)),
+                   x=None, w=None):
+    x = tspn.hashrng.uniform(seed, "x", (B, T, Cin), -1, 1) if x is None else x
+    w = tspn.hashrng.normal(seed, "w", (M, Cin, 3), std=0.1) if w is None else w
+    b = tspn.hashrng.normal(seed, "b", (M,), std=0.1)
+    ref, mag = conv_tc_ref64(x, w)
+    xd, bd = t(x).to(device), t(b).to(device)
+    pk = tspn.ops.pack_conv3_wino63_f16x3(t(w).to(device))
+    outs = []
+    for with_bias, relu in combos:
+        r = ref + (b.astype(np.float64)[None, :, None] if with_bias else 0.0)
+        buf, y = held_output((B, M, T), device, offset)
+        f16x3_raw(tspn, xd, pk, bd if with_bias else None, relu, y)
+        check_f16x3(buf, y, np.maximum(r, 0.0) if relu else r, mag + (np.abs(b)[None, :, None] if with_bias else 0.0),
+                    f"B={B} T={T} Cin={Cin} M={M} offset={offset} bias={with_bias} relu={relu}")
+        outs.append(y)
+    return outs
+
+
+@pytest.mark.parametrize("M,B,T,nwg_mod8", [
+    (1280, 300, 7, 7),      # 5 row tiles (a group of 4 and a group of 1) x 3 sextet tiles = 15 workgroups, scalar tail
+    (1280, 520, 12, 1),     # x 5 sextet tiles = 25, vec2 stores
+    (1280, 800, 7, 3),      # x 7 = 35
+    (2304, 550, 12, 5),     # 9 row tiles (4 + 4 + 1) x 5 = 45
+])
+def test_wino63_f16x3_tile_grid_and_sextet_edges(tspn, device, M, B, T, nwg_mod8):
+    """Grids the workgroup remap has to get right: tiles_m % GM != 0 with tiles_m > GM, more than 8 workgroups with
+    every odd remainder against the 8 XCDs; every tile is written exactly once (sentinel, float64 reference)."""
+    tiles_m, tiles_n = M // F_BM, -(-(B * -(-T // 6)) // F_BN)
+    assert tiles_m % F_GM != 0 and tiles_m > F_GM and tiles_m * tiles_n > 8 and (tiles_m * tiles_n) % 8 == nwg_mod8
+    run_f16x3_case(tspn, device, B, T, 32, M, 430 + nwg_mod8)
+
+
+@pytest.mark.parametrize("B,T,nsext", [(85, 17, 255), (128, 12, 256), (64, 19, 256), (257, 5, 257), (128, 24, 512)])
+def test_wino63_f16x3_sextet_counts_at_the_tile_edge(tspn, device, B, T, nsext):
+    """Exactly 255, 256, 257 and 512 sextets: one padded column, a full tile, one column in a second tile, no padding."""
+    assert B * -(-T // 6) == nsext
+    run_f16x3_case(tspn, device, B, T, 32, 512, 440 + T)
+
+
+@pytest.mark.parametrize("T", [1, 5, 6, 7, 12, 31, 33, 34, 150])
+def test_wino63_f16x3_every_T_both_store_forms(tspn, device, T):
+    """Through the C entry ldy = T, so the 8-byte stores need T % 6 == 0 and an 8-byte aligned y; a y whose base is 4-byte
+    but not 8-byte aligned takes the scalar stores at the same shape and equals the aligned launch bit for bit."""
+    B, Cin, M = 5, 64, 256
+    aligned = run_f16x3_case(tspn, device, B, T, Cin, M, 450)
+    shifted = run_f16x3_case(tspn, device, B, T, Cin, M, 450, offset=1)
+    for a, s in zip(aligned, shifted):
+        assert torch.equal(a, s)
+
+
+@pytest.mark.parametrize("Cin,B,T,M", [(32, 50, 33, 512), (64, 50, 31, 512), (2048, 3, 33, 256)])
+def test_wino63_f16x3_contraction_depths(tspn, device, Cin, B, T, M):
+    """Cin = 32: two k-steps per point, the ring shorter than its prefetch depth, over several tiles; Cin = 2048: the
+    headline depth (benchmark distribution, whose outputs stay below 1)."""
+    if Cin == 2048:
+        run_f16x3_case(tspn, device, B, T, Cin, M, 460, x=tspn.hashrng.uniform(460, "x", (B, T, Cin)),
+                       w=tspn.hashrng.normal(460, "w", (M, Cin, 3), std=0.01))
+    else:
+        run_f16x3_case(tspn, device, B, T, Cin, M, 460)
+
+
+def test_wino63_f16x3_refusals_leave_the_output_untouched(tspn, device):
+    """Every refusal of the split entry points comes before any launch: y keeps its sentinel and the workspace its
+    fill (the input transform would have written it)."""
+    E = tspn._abi
+    B, T, Cin, M = 2, 9, 32, 256
+    x = t(tspn.hashrng.uniform(470, "x", (B, T, Cin), -1, 1)).to(device)
+    w = t(tspn.hashrng.normal(470, "w", (M, Cin, 3), std=0.1)).to(device)
+    pk = tspn.ops.pack_conv3_wino63_f16x3(w)
+    need = E.lib().tspn_conv3_tc_wino63_f16x3_workspace_bytes(B, T, Cin, M)
+    pk_buf = torch.zeros(pk.numel() + 8, dtype=torch.int16, device=device)
+    pk_off = pk_buf[2:2 + pk.numel()].view(pk.shape)
+    pk_off.copy_(pk)
+    assert pk_off.data_ptr() % 16 == 4
+
+    def refused(code, xx=x, pkk=pk, ws_off=0, ws_bytes=None, MM=None):
+        buf, y = held_output((B, MM or M, T), device)
+        ws_buf = torch.full((need + 512,), 0x5A, dtype=torch.uint8, device=device)
+        with pytest.raises(E.TspnError) as e:
+            f16x3_raw(tspn, xx, pkk, None, False, y, ws=ws_buf[ws_off:], ws_bytes=need if ws_bytes is None else ws_bytes, M=MM)
+        assert e.value.code == code, (e.value.code, str(e.value))
+        torch.cuda.synchronize(device)
+        assert bool((buf == float(SENTINEL)).all()) and bool((ws_buf == 0x5A).all())
+
+    refused(E.TSPN_EINVAL, xx=off4(x.cpu(), device))                   # x: 16-byte pieces
+    refused(E.TSPN_EUNSUPPORTED, pkk=pk_off)                           # packed: 16-byte LDS-DMA pieces
+    refused(E.TSPN_EINVAL, ws_off=16)                                  # workspace: 256-byte aligned
+    refused(E.TSPN_EWORKSPACE, ws_bytes=need - 256)                    # workspace: short
+    refused(E.TSPN_EUNSUPPORTED, MM=128)                               # M % 256 != 0
+    # the weight pack: M % 256, split with Cin != 2 split, packed at a 4-byte offset
+    out = torch.full((pk.numel() + 8,), 0x5A5A, dtype=torch.int16, device=device)
+    for (m, cin, split, o, code) in ((128, 32, 0, 0, E.TSPN_EUNSUPPORTED), (256, 96, 32, 0, E.TSPN_EINVAL),
+                                     (256, 32, 0, 2, E.TSPN_EINVAL)):
+        wt = torch.zeros((m, cin, 3), device=device)
+        with pytest.raises(E.TspnError) as e:
+            E.check(E.lib().tspn_pack_conv3_wino63_f16x3(p(wt), m, cin, split, p(out[o:]), tspn.ops._stream()))
+        assert e.value.code == code
+        torch.cuda.synchronize(device)
+        assert bool((out == 0x5A5A).all())
+    # a refused call is not sticky: the same operands, aligned, run
+    buf, y = held_output((B, M, T), device)
+    f16x3_raw(tspn, x, pk, None, False, y)
+    assert torch.equal(y, tspn.ops.conv3_tc_wino63_f16x3(x, pk))
+
+
+@pytest.mark.parametrize("canonical", [True, False])
+@pytest.mark.parametrize("T", [31, 33, 34])
+@pytest.mark.parametrize("D", [64, 192])
+def test_forward_fused_f16x3_against_dense_oracle(tspn, device, D, T, canonical):
+    """tspn_forward_fused_f32 with conv_algo = TSPN_CONV_WINOGRAD63_F16X3 at ops level (gate D % 64 == 0), 45 tracklets =
+    two contraction tiles: odd T keeps ldy = T (scalar stores), T = 34 with canonical pairs pads the rows of y to 36
+    frames and takes the 8-byte stores over two pad frames, which must never reach an output.  Against the dense
+    float64 oracle; the outputs are pre-filled and must all be written."""
+    B, N, A = 5, 9, 4
+    assert B * N * -(-T // 6) > F_BN
+    w = fused_weights(tspn, D, A)
+    vids = [tspn.synth.make_video(70 + b, N, T, D) for b in range(B)]
+    feats = torch.cat([t(v["tracklet_feats"]) for v in vids])
+    pairs = torch.cat([oracle.pair_index(N) + b * N for b in range(B)])
+    if not canonical:
+        pairs = pairs.flip(0).contiguous()
+    d = lambda v: v.to(device).contiguous()
+    packed = tspn.ops.pack_conv3_wino63_f16x3(d(w["conv_w"]), split=D)
+    hw = d(torch.cat([w["rel_w"][:, :, 0], w["dur_w"][:, :, 0]]))
+    hb = d(torch.cat([w["rel_b"], w["dur_b"]]))
+    P = pairs.shape[0]
+    out_h = torch.full((P, 3 * A, T), float(SENTINEL), device=device)
+    out_l = torch.full((P, w["cls_w"].shape[0]), float(SENTINEL), device=device)
+    need = tspn.ops.fused_workspace_bytes(B, N, T, D, A, w["cls_w"].shape[0], P, conv_algo=tspn._abi.CONV_WINOGRAD63_F16X3)
+    ws = torch.full((need,), 0x7F, dtype=torch.uint8, device=device)      # pad frames of y start as NaN bit patterns
+    heads, logits = tspn.ops.forward_fused(d(feats), d(pairs), B, N, packed, d(w["conv_b"]), hw, hb, d(w["cls_w"]),
+                                           d(w["cls_b"]), canonical_pairs=canonical, workspace=ws, out_heads=out_h,
+                                           out_logits=out_l)
+    assert not bool((heads == float(SENTINEL)).any()) and not bool((logits == float(SENTINEL)).any())
+    refs = [oracle.forward_dense(t(v["tracklet_feats"]).double(), t(v["tracklet_boxes"]).double(), oracle.pair_index(N),
+                                 {k: x.double() for k, x in w.items()}) for v in vids]
+    rel = torch.cat([r["relness"] for r in refs]).numpy()
+    dur = torch.cat([r["duration"] for r in refs]).numpy()
+    lg = torch.cat([r["rel_logits"] for r in refs]).numpy()
+    if not canonical:
+        rel, dur, lg = rel[::-1], dur[::-1], lg[::-1]
+    np.testing.assert_allclose(heads[:, :A].cpu().numpy(), rel, rtol=0, atol=6e-5)
+    np.testing.assert_allclose(heads[:, A:].cpu().numpy(), dur, rtol=0, atol=6e-5)
+    np.testing.assert_allclose(logits.cpu().numpy(), lg, rtol=0, atol=2e-5)
+
+
+def test_forward_fused_f16x3_refuses_d32_before_any_launch(tspn, device):
+    """D = 32 passes the fp32 F(6,3) gate but not the split form's (4D % 256): TSPN_EUNSUPPORTED, and neither the heads
+    nor the logits (computed first in a pass that runs) are touched."""
+    B, N, T, D, A = 1, 3, 12, 32, 4
+    w = fused_weights(tspn, D, A)
+    d = lambda v: v.to(device).contiguous()
+    pairs = oracle.pair_index(N)
+    fake = torch.zeros((8, 2 * (D // 8) + 1, 4 * D, 8), dtype=torch.int16, device=device)
+    assert tspn.ops.wino63_f16x3_dims(fake) == (D, 4 * D)
+    out_h = torch.full((pairs.shape[0], 3 * A, T), float(SENTINEL), device=device)
+    out_l = torch.full((pairs.shape[0], w["cls_w"].shape[0]), float(SENTINEL), device=device)
+    with pytest.raises(tspn._abi.TspnError) as e:
+        tspn.ops.forward_fused(d(torch.zeros(N, T, D)), d(pairs), B, N, fake, d(w["conv_b"]),
+                               d(torch.cat([w["rel_w"][:, :, 0], w["dur_w"][:, :, 0]])), d(torch.cat([w["rel_b"], w["dur_b"]])),
+                               d(w["cls_w"]), d(w["cls_b"]), canonical_pairs=True, out_heads=out_h, out_logits=out_l)
+    assert e.value.code == tspn._abi.TSPN_EUNSUPPORTED
+    torch.cuda.synchronize(device)
+    assert bool((out_h == float(SENTINEL)).all()) and bool((out_l == float(SENTINEL)).all())
