@@ -277,7 +277,11 @@ size_t tspn_conv3_tc_wino63_f16x3_workspace_bytes(int64_t B, int64_t T, int64_t 
 int tspn_conv3_tc_wino63_f16x3(const float* x, int64_t B, int64_t T, int64_t Cin, const int16_t* packed,
                                int64_t M, const float* bias, int relu, float* y,
                                void* workspace, size_t workspace_bytes, void* stream);
-
+/* The contraction runs one 256 x 256 tile per CU at a time.  1 (default): the tiles of the last round, when they fill
+ * at most half of the CUs, are cut into 2 or 4 tiles of 256 x 128 / 256 x 64 so that more CUs share that round; 0: whole
+ * tiles only.  The outputs are the same bit for bit (tests/test_gpu_wino63_f16x3_tail.py).  Process-wide (additive, no
+ * version bump); returns the previous value, TSPN_EINVAL for any other `on`. */
+int tspn_conv3_tc_wino63_f16x3_set_tail_split(int on);
 
 
 /* ---- a8/a10: relationness + span-regression heads -----------------------

@@ -461,6 +461,7 @@ constexpr int F_ST = 4 * 2 * 256 * 16;         // one k-step (16 channels) of Wh
 constexpr int F_NST = 4;                       // ring of stages, filled three k-steps ahead by LDS-DMA
 constexpr size_t F_SMEM = (size_t)F_NST * F_ST;
 constexpr size_t F_SMEM_ALL = F_SMEM + 2 * 256 * sizeof(int);   // + the exponent table of the unscale
+static_assert(TSPN_WINO63_GM > 0 && TSPN_WINO63_GM < 256, "the contraction's GM argument carries the tail split above bit 7");
 constexpr size_t F_PARK_PER_TILE = (size_t)7 * F_THREADS * 128 * sizeof(float);   // points 0..6 of a tile, fp32
 
 // power-of-two exponent e with max * 2^e in [2^14, 2^15); 0 for a zero or non-finite maximum (a non-finite value then
@@ -611,87 +612,106 @@ __global__ __launch_bounds__(256) void wino63_input_transform_kernel(
 // conv3_bf16_big_kernel).  At the end of a point the accumulator is unscaled and, for points 0..6, parked in the
 // workspace (each lane reads back exactly what it wrote: no synchronisation, deterministic); after point 7 the lane
 // reads its 7 parked tiles back, applies the inverse transform and the bias and writes y as the fp32 form does.
-__global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
-    const _Float16* __restrict__ Vh, const int* __restrict__ Ve, const int16_t* __restrict__ Wp,
+//
+// The tile body, for 256 rows x 64 WN sextets.  The 8 waves are 8 / WN over the rows x WN over the sextets, a wave tile
+// is 32 WN rows x 64 sextets (WN x 2 accumulators of 32 x 32):
+//   WN = 4  the full tile: 2 x 4 waves of 128 x 64
+//   WN = 2  half a tile (tail split by 2): 4 x 2 waves of 64 x 64
+//   WN = 1  a quarter (tail split by 4): 8 x 1 waves of 32 x 64
+// The LDS image of a stage and the A fragments are the same in all three; a narrower tile fills only the first 64 WN
+// sextets of each V row, so a stage is 16 + 4 WN DMA pieces of 1 KB.  An output element sees the same operands in the
+// same order whichever shape computes it (a 32x32x16 MFMA result depends on the element's own row and column only),
+// so y does not depend on how the launch was cut.  `sub` = which 64 WN sextets of the 256-sextet tile `tile`.
+template <int WN>
+__device__ __forceinline__ void wino63_f16x3_tile(
+    char* smem_raw, const _Float16* __restrict__ Vh, const int* __restrict__ Ve, const int16_t* __restrict__ Wp,
     const float* __restrict__ bias, float* __restrict__ y, float* __restrict__ park, int Cin, int T, int M, int nq,
-    int64_t nsext, int64_t nsp2, int tiles_m, int tiles_n, int relu, int ldy, int GM, int vec2) {
-  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
-
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int group_sz = GM * tiles_n;
-  const int group = wg / group_sz;
-  const int first_m = group * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int in_group = wg - group * group_sz;
-  const int tile_m = first_m + in_group % gm;
-  const int tile_n = in_group / gm;
+    int64_t nsext, int64_t nsp2, int tile_m, int tile_n, int tiles_n, int sub, int relu, int ldy, int vec2) {
+  constexpr int MI = WN;                       // 32-row blocks of a wave: 256 rows / (8 / WN waves) / 32
+  constexpr int BN = 64 * WN;                  // sextets of this tile
+  constexpr int NP = 16 + 4 * WN;              // DMA pieces per stage: 16 of W, 4 WN of V
+  constexpr int PW = (NP + 7) / 8;             // pieces per wave, at most
+  constexpr bool EVEN = NP % 8 == 0;           // every wave issues PW pieces (else PW or PW - 1, by wave)
   const int m0 = tile_m * F_BM;
-  const int64_t S0 = (int64_t)tile_n * F_BN;
+  const int64_t S0 = (int64_t)tile_n * F_BN + sub * BN;
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave >> 2, wn = wave & 3;
+  const int wm = wave / WN, wn = wave % WN;
   const int li = lane & 31, kh = lane >> 5;
   const int ncg = Cin >> 3, nk = Cin >> 4;
   const int G = NJ * nk;                             // k-steps of the whole workgroup (8 points)
 
-  // DMA pieces: piece p = 4 wave + i of a stage (1 KB each): region p >> 3 (Wh, Wl, Vh, Vl), channel group (p >> 2) & 1,
-  // rows / sextets 64 (p & 3) + lane.  Element offsets at k-step 0 of point 0, and the strides per k-step / point.
-  const int16_t* src[4];
-  int64_t kstride[4], jstride[4];
+  // DMA pieces of a stage (1 KB each), numbered p: p < 16 is W: region p >> 3 (Wh, Wl), channel group (p >> 2) & 1, rows
+  // 64 (p & 3) + lane; p >= 16 is V, v = p - 16: region 2 + v / (2 WN) (Vh, Vl), channel group (v / WN) & 1, sextets
+  // 64 (v % WN) + lane.  Wave w issues pieces [w NP / 8, (w + 1) NP / 8).  Element offsets at k-step 0 of point 0, and
+  // the strides per k-step / point.
+  const int p0 = wave * NP / 8;
+  const int npw = EVEN ? PW : (wave + 1) * NP / 8 - p0;      // wave-uniform
+  const int16_t* src[PW];
+  int64_t kstride[PW], jstride[PW];
+  int ldst[PW];                                              // byte offset of the piece in its stage
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const int p = 4 * wave + i;
-    const int region = p >> 3, cgi = (p >> 2) & 1, r = 64 * (p & 3) + lane;
-    if (region < 2) {
+  for (int i = 0; i < PW; ++i) {
+    const int p = min(p0 + i, NP - 1);
+    if (p < 16) {
+      const int region = p >> 3, cgi = (p >> 2) & 1, r = 64 * (p & 3) + lane;
       src[i] = Wp + (((int64_t)region * ncg + cgi) * M + m0 + r) * 8;
       kstride[i] = (int64_t)2 * M * 8;
       jstride[i] = (int64_t)(2 * ncg + 1) * M * 8;
+      ldst[i] = p * 1024;
     } else {
-      src[i] = reinterpret_cast<const int16_t*>(Vh) + (((int64_t)(region - 2) * ncg + cgi) * nsp2 + S0 + r) * 8;
+      const int v = p - 16;
+      const int region = v / (2 * WN), cgi = (v / WN) & 1, r = 64 * (v % WN) + lane;
+      src[i] = reinterpret_cast<const int16_t*>(Vh) + (((int64_t)region * ncg + cgi) * nsp2 + S0 + r) * 8;
       kstride[i] = (int64_t)2 * nsp2 * 8;
       jstride[i] = (int64_t)2 * ncg * nsp2 * 8;
+      ldst[i] = (2 + region) * 8192 + cgi * 4096 + (v % WN) * 1024;
     }
   }
   auto issue = [&](int g) {                          // k-step g (point g / nk) into ring stage g & 3
     const int j = g / nk, k = g - j * nk;
-    char* dst = smem_raw + (g & 3) * F_ST + (4 * wave) * 1024;
+    char* dst = smem_raw + (g & 3) * F_ST;
 #pragma unroll
-    for (int i = 0; i < 4; ++i)
-      glds16(src[i] + j * jstride[i] + k * kstride[i], dst + i * 1024);
+    for (int i = 0; i < PW; ++i)
+      if (EVEN || i < npw) glds16(src[i] + j * jstride[i] + k * kstride[i], dst + ldst[i]);
+  };
+  // all but the youngest `ahead` stages of this wave have landed (a wave's VMEM returns in order)
+  auto wait_stages = [&](auto ahead_tag) {
+    constexpr int AHEAD = decltype(ahead_tag)::value;
+    if (EVEN || npw == PW) wait_vmcnt<AHEAD * PW>(); else wait_vmcnt<AHEAD * (PW - 1)>();
   };
 
-  f32x16 acc[4][2];
+  f32x16 acc[MI][2];
 #pragma unroll
-  for (int mi = 0; mi < 4; ++mi)
+  for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[mi][ni][e] = 0.f;
 
-  // this lane's parking slots: [tile][point 0..6][32 f32x4 registers][512 lanes] (one 1 KB store per wave and register)
-  float* my_park = park + (int64_t)(tile_m * tiles_n + tile_n) * (F_PARK_PER_TILE / sizeof(float)) + tid * 4;
-  // unscale the accumulator of point j: 2^-(e_row + e_col), exact.  The tile's 256 row and 256 column exponents go
+  // this lane's parking slots: [tile][point 0..6][32 f32x4 registers][512 lanes] (one 1 KB store per wave and register);
+  // a narrower tile has 8 WN registers per point and takes the slots 8 WN sub .. of its 256-sextet tile
+  float* my_park = park + (int64_t)(tile_m * tiles_n + tile_n) * (F_PARK_PER_TILE / sizeof(float)) +
+                   (int64_t)sub * (8 * MI) * F_THREADS * 4 + tid * 4;
+  // unscale the accumulator of point j: 2^-(e_row + e_col), exact.  The tile's 256 row and 64 WN column exponents go
   // through LDS behind the ring (one load per thread instead of 64 per lane).
   int* etab = reinterpret_cast<int*>(smem_raw + F_SMEM);        // [256 rows][256 columns]
   auto unscale = [&](int j) {
     if (tid < F_BM)
       etab[tid] = reinterpret_cast<const int*>(Wp + (int64_t)j * (2 * ncg + 1) * M * 8 + (int64_t)2 * ncg * M * 8)[(int64_t)(m0 + tid) * 4];
-    else
+    else if (tid - F_BM < BN)
       etab[tid] = Ve[(int64_t)j * nsp2 + S0 + tid - F_BM];
     __syncthreads();
     int ec[2];
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) ec[ni] = etab[F_BM + wn * 64 + ni * 32 + li];
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
+    for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int r = etab[wm * 128 + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh];
+        const int r = etab[wm * (32 * MI) + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh];
 #pragma unroll
         for (int ni = 0; ni < 2; ++ni) acc[mi][ni][e] = ldexpf(acc[mi][ni][e], -(r + ec[ni]));
       }
@@ -701,17 +721,19 @@ __global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
   if (G > 1) issue(1);
   if (G > 2) issue(2);
   for (int g = 0; g < G; ++g) {
-    if (g + 2 < G) wait_vmcnt<8>(); else if (g + 1 < G) wait_vmcnt<4>(); else wait_vmcnt<0>();
+    if (g + 2 < G) wait_stages(std::integral_constant<int, 2>{});
+    else if (g + 1 < G) wait_stages(std::integral_constant<int, 1>{});
+    else wait_vmcnt<0>();
     __builtin_amdgcn_sched_barrier(0);
     __builtin_amdgcn_s_barrier();                   // stage g landed for every wave; stage g - 1 is read out
     __builtin_amdgcn_sched_barrier(0);
     if (g + 3 < G) issue(g + 3);
     __builtin_amdgcn_sched_barrier(0);
     const char* st = smem_raw + (g & 3) * F_ST;
-    f16x8 ah[4], al[4], bh[2], bl[2];
+    f16x8 ah[MI], al[MI], bh[2], bl[2];
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-      const int off = (kh * 256 + wm * 128 + mi * 32 + li) * 16;
+    for (int mi = 0; mi < MI; ++mi) {
+      const int off = (kh * 256 + wm * (32 * MI) + mi * 32 + li) * 16;
       ah[mi] = *reinterpret_cast<const f16x8*>(st + off);
       al[mi] = *reinterpret_cast<const f16x8*>(st + 8192 + off);
     }
@@ -724,22 +746,23 @@ __global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mi], bh[ni], acc[mi][ni], 0, 0, 0);
+      for (int mi = 0; mi < MI; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mi], bh[ni], acc[mi][ni], 0, 0, 0);
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
+      for (int mi = 0; mi < MI; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
-      for (int mi = 0; mi < 4; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
+      for (int mi = 0; mi < MI; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
     if (g % nk == nk - 1) {
       const int j = g / nk;
       unscale(j);
       if (j < NJ - 1) {
+        // (these stores are younger than every DMA piece in flight, so the counted waits above only get stricter)
 #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
+        for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
           for (int ni = 0; ni < 2; ++ni)
 #pragma unroll
@@ -766,7 +789,7 @@ __global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
     const int t = 6 * q;
     float* ycol = y + (b * M) * (int64_t)ldy + t;
 #pragma unroll
-    for (int mi = 0; mi < 4; ++mi)
+    for (int mi = 0; mi < MI; ++mi)
 #pragma unroll
       for (int eq = 0; eq < 4; ++eq) {
         f32x4 P[NJ - 1];
@@ -777,7 +800,7 @@ __global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
 #pragma unroll
         for (int e4 = 0; e4 < 4; ++e4) {
           const int e = 4 * eq + e4;
-          const int m = m0 + wm * 128 + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
+          const int m = m0 + wm * (32 * MI) + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * kh;
           const float p12 = P[1][e4] + P[2][e4], m12 = P[1][e4] - P[2][e4];
           const float p34 = P[3][e4] + P[4][e4], m34 = P[3][e4] - P[4][e4];
           const float p56 = P[5][e4] + P[6][e4], m56 = P[5][e4] - P[6][e4];
@@ -810,6 +833,59 @@ __global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
         }
       }
   }
+}
+
+// bijective XCD remap of `n` workgroups: the hardware deals consecutive block ids round the 8 XCDs, this gives XCD x a
+// contiguous range of the logical ids (which therefore share its L2)
+__device__ __forceinline__ int xcd_remap(int id, int n) {
+  const int q8 = n >> 3, r8 = n & 7, xcd = id & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
+}
+
+// The launch.  tiles_m x tiles_n tiles of 256 x 256, numbered in groups of GM row tiles x all sextet tiles.
+// `GM`: bits 0..7 the row tiles per group; bits 8..15 the tail split f (0 or 1: none).  With f = 2 or 4 the LAST
+// R = (gridDim.x - tiles) / (f - 1) tiles of that numbering are each cut into f tiles of 256 x 256 / f (sub-tiles), so
+// that the last, partly filled round of the launch keeps f times as many CUs busy:
+//   blocks [0, tiles - R)       one full tile each, XCD remap over these blocks
+//   blocks [tiles - R, grid)    R f sub-tiles, after every full tile in block order (the dispatcher hands them to CUs as
+//                               they come free); XCD remap over these blocks, f consecutive logical ids = one tile, so
+//                               the sub-tiles of a tile share an XCD (its W rows in L2) wherever the XCD's range of
+//                               ids is a multiple of f -- always at R % 8 == 0 -- and at most 7 tiles straddle two
+// Both remaps are bijections, so every tile and sub-tile is computed exactly once.  A sub-tile parks into its own
+// share of its tile's parking area; all other arguments mean what they meant without the split.
+__global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
+    const _Float16* __restrict__ Vh, const int* __restrict__ Ve, const int16_t* __restrict__ Wp,
+    const float* __restrict__ bias, float* __restrict__ y, float* __restrict__ park, int Cin, int T, int M, int nq,
+    int64_t nsext, int64_t nsp2, int tiles_m, int tiles_n, int relu, int ldy, int GM, int vec2) {
+  extern __shared__ __attribute__((aligned(16))) char smem_raw[];
+
+  const int f = max((GM >> 8) & 0xff, 1);
+  GM &= 0xff;
+  const int tiles = tiles_m * tiles_n;
+  const int nsplit = f > 1 ? ((int)gridDim.x - tiles) / (f - 1) : 0;     // R
+  const int nfull = tiles - nsplit;
+  const int bid = blockIdx.x;
+  int wg, sub = 0;
+  if (bid < nfull) {
+    wg = xcd_remap(bid, nfull);
+  } else {
+    const int s = xcd_remap(bid - nfull, nsplit * f);
+    wg = nfull + s / f;
+    sub = s - (s / f) * f;
+  }
+  const int group_sz = GM * tiles_n;
+  const int group = wg / group_sz;
+  const int first_m = group * GM;
+  const int gm = min(GM, tiles_m - first_m);
+  const int in_group = wg - group * group_sz;
+  const int tile_m = first_m + in_group % gm;
+  const int tile_n = in_group / gm;
+  if (bid < nfull)
+    wino63_f16x3_tile<4>(smem_raw, Vh, Ve, Wp, bias, y, park, Cin, T, M, nq, nsext, nsp2, tile_m, tile_n, tiles_n, 0, relu, ldy, vec2);
+  else if (f == 2)
+    wino63_f16x3_tile<2>(smem_raw, Vh, Ve, Wp, bias, y, park, Cin, T, M, nq, nsext, nsp2, tile_m, tile_n, tiles_n, sub, relu, ldy, vec2);
+  else
+    wino63_f16x3_tile<1>(smem_raw, Vh, Ve, Wp, bias, y, park, Cin, T, M, nq, nsext, nsp2, tile_m, tile_n, tiles_n, sub, relu, ldy, vec2);
 }
 
 int64_t padded_sextets(int64_t B, int64_t T) { return tspn::ceil_div(B * tspn::ceil_div(T, 6), SWG) * SWG; }
@@ -1008,6 +1084,40 @@ int tspn::wino63_f16x3_input_transform(const float* x, int64_t B, int64_t T, int
   return tspn::check_launch(what);
 }
 
+// 1 = cut the tiles of the last, partly filled round of the split contraction into sub-tiles (default), 0 = whole tiles only
+static std::atomic<int> g_tail_split{1};
+
+extern "C" int tspn_conv3_tc_wino63_f16x3_set_tail_split(int on) {
+  TSPN_REQUIRE(on == 0 || on == 1, TSPN_EINVAL, "tspn_conv3_tc_wino63_f16x3_set_tail_split: on must be 0 or 1");
+  return g_tail_split.exchange(on, std::memory_order_relaxed);
+}
+
+// CUs of the current device (0 if unknown), asked once per device ordinal
+static int device_cus() {
+  constexpr int kMaxDevices = 64;
+  static std::atomic<int> cached[kMaxDevices] = {};
+  int dev = -1, cus = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return 0;
+  const bool tracked = dev >= 0 && dev < kMaxDevices;
+  if (tracked && (cus = cached[dev].load(std::memory_order_relaxed)) > 0) return cus;
+  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 0;
+  if (tracked) cached[dev].store(cus, std::memory_order_relaxed);
+  return cus;
+}
+
+// The tail split of a launch of `tiles` workgroups (one per CU at a time): R = tiles % CUs tiles are left for the last
+// round; when they fill at most half of the CUs, each is cut into f = min(4, CUs / R) sub-tiles.  Returns f (1: no split).
+static int tail_split_factor(int64_t tiles, int cus, int64_t* R) {
+  *R = 0;
+  if (cus <= 0 || g_tail_split.load(std::memory_order_relaxed) == 0) return 1;
+  const int64_t r = tiles % cus;
+  if (r == 0) return 1;
+  const int64_t f = std::min<int64_t>(4, cus / r);
+  if (f < 2) return 1;
+  *R = r;
+  return f == 3 ? 2 : (int)f;     // the kernel has the shapes 256 / 2 and 256 / 4
+}
+
 // step 2 of the split form: the f16 MFMA contraction + inverse transform
 int tspn::wino63_f16x3_contract(void* workspace, size_t workspace_bytes, int64_t B, int64_t T, int64_t Cin,
                                 const int16_t* packed, int64_t M, const float* bias, int relu, float* y, int64_t ldy,
@@ -1026,17 +1136,21 @@ int tspn::wino63_f16x3_contract(void* workspace, size_t workspace_bytes, int64_t
   const int64_t nq = tspn::ceil_div(T, 6);
   const int64_t nsext = B * nq, nsp2 = padded_sextets_f16x3(B, T);
   const int64_t tiles_m = M / F_BM, tiles_n = nsp2 / F_BN;
-  TSPN_REQUIRE(tiles_m * tiles_n < (1LL << 31), TSPN_EUNSUPPORTED, "%s: grid too large", what);
+  TSPN_REQUIRE(tiles_m * tiles_n < (1LL << 29), TSPN_EUNSUPPORTED, "%s: grid too large", what);
   const int vec2 = (ldy % 2 == 0) && (ldy >= 6 * nq) && ((reinterpret_cast<uintptr_t>(y) & 7) == 0);
+  // the last round: R tiles as R f sub-tiles behind the full ones (see the kernel)
+  int64_t R = 0;
+  const int f = tail_split_factor(tiles_m * tiles_n, device_cus(), &R);
+  const int64_t grid = tiles_m * tiles_n + R * (f - 1);
   char* ws = static_cast<char*>(workspace);
   static tspn::LdsLimit lds;     // 128 KB of dynamic LDS
   void (*kern)(const _Float16*, const int*, const int16_t*, const float*, float*, float*, int, int, int, int, int64_t,
                int64_t, int, int, int, int, int, int) = conv3_wino63_kernel;
   if (int rc = lds.ensure(reinterpret_cast<const void*>(kern), F_SMEM_ALL, what)) return rc;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(F_THREADS), F_SMEM_ALL, TSPN_STREAM(stream),
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(F_THREADS), F_SMEM_ALL, TSPN_STREAM(stream),
                      reinterpret_cast<const _Float16*>(ws + L.v), reinterpret_cast<const int*>(ws + L.e), packed, bias, y,
                      reinterpret_cast<float*>(ws + L.park), (int)Cin, (int)T, (int)M, (int)nq, nsext, nsp2, (int)tiles_m,
-                     (int)tiles_n, relu, (int)ldy, TSPN_WINO63_GM, vec2);
+                     (int)tiles_n, relu, (int)ldy, TSPN_WINO63_GM | (f << 8), vec2);
   return tspn::check_launch(what);
 }
 

@@ -19,7 +19,7 @@ __all__ = [
     "cast_bf16", "pack_conv3_bf16", "pack_heads_bf16", "conv3_tc_bf16", "heads_pairgrid_bf16",
     "transpose_cast_bf16", "temporal_encoder_heads_bf16",
     "temporal_mean_bf16", "forward_fused_bf16", "span_predicate", "bottleneck_block_bf16", "bottleneck_block_proj_bf16", "bottleneck_block_res_bf16",
-    "proposal_pair_filter", "gather_rows", "wino63_set_piece_form", "conv3_spot_check",
+    "proposal_pair_filter", "gather_rows", "wino63_set_piece_form", "wino63_f16x3_set_tail_split", "conv3_spot_check",
     "pack_conv2d", "pack_conv2d_frag", "conv2d_nhwc", "roi_align_nhwc", "pack_conv2d_frag_bf16", "conv2d_nhwc_bf16", "max_pool_nhwc", "pack_conv2d_frag_cin4", "conv2d_nhwc_cin4", "max_pool_nhwc_bf16", "pack_stem_bf16", "stem_conv_bf16", "stem_pool_bf16", "bottleneck_tail_bf16",
     "eval_traj_volume", "eval_viou", "eval_greedy_match",
     "status_words", "status_fault", "status_clear", "status_selftest",
@@ -514,6 +514,15 @@ def wino63_set_piece_form(form):
     """0 = buffer-load pieces where the workspace is below 4 GB (default), 1 = 64-bit pointer pieces everywhere
     (tspn_conv3_tc_wino63_set_piece_form).  Returns the previous setting."""
     prev = _abi.lib().tspn_conv3_tc_wino63_set_piece_form(int(form))
+    if prev < 0:
+        _abi.check(prev)
+    return prev
+
+
+def wino63_f16x3_set_tail_split(on):
+    """1 = the split-fp16 contraction cuts the tiles of its last, partly filled round into sub-tiles (default), 0 = whole
+    tiles only (tspn_conv3_tc_wino63_f16x3_set_tail_split); same outputs bit for bit.  Returns the previous setting."""
+    prev = _abi.lib().tspn_conv3_tc_wino63_f16x3_set_tail_split(int(on))
     if prev < 0:
         _abi.check(prev)
     return prev
