@@ -432,7 +432,10 @@ int tspn_conv3_spot_check_f32(const float* x, int64_t B, int64_t T, int64_t Cin,
  * the pair's own span [start, end) of frames before RelationPredictor (model.py:85-88):
  *   out[p] = sigmoid(cls_w . mean_{t in [start_p, end_p)} cat(f[s_p, t], f[o_p, t]) + cls_b).
  * feats [NT, T, D]; pairs [P,2] global tracklet ids; spans int64 [P,2], e.g. the top span of
- * tspn_decode_spans_f32 (a negative start selects the whole segment).                               */
+ * tspn_decode_spans_f32.  A row that is not 0 <= start < end <= T is rewritten: start and end
+ * are clipped into the segment, an empty or reversed span pools its first frame, and one with a negative
+ * start -- the (-1, -1) of a pair without a proposal -- pools the whole segment.  A NaN / Inf feature reaches
+ * exactly the outputs of the spans that contain its frame.                                           */
 size_t tspn_span_predicate_workspace_bytes(int64_t NT, int64_t T, int64_t D, int64_t K);
 int tspn_span_predicate_f32(const float* feats, int64_t NT, int64_t T, int64_t D, const int64_t* pairs,
                             const int64_t* spans, int64_t P, const float* cls_w, const float* cls_b,

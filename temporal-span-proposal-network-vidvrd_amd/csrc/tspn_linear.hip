@@ -219,6 +219,8 @@ __global__ void pair_combine_kernel(const float* __restrict__ rs, const float* _
 // features over each pair's span it is applied to every (tracklet, frame) row first -- G = f W'^T with
 // W' = cls_w [K,2D] read as [2K, D] (column 2k: subject half, 2k+1: object half) -- prefix-summed over
 // time in float64, and a pair's logit is a difference of two prefix rows per half divided by the span length.
+// A NaN / Inf frame makes every later prefix value of its (tracklet, column) non-finite; the combine kernel then sums
+// the span's own frames of G instead, so a non-finite value reaches exactly the spans that contain it.
 __global__ void span_prefix_kernel(const float* __restrict__ G, int64_t NT, int T, int K2,
                                    double* __restrict__ PS) {
   const int64_t total = NT * K2;
@@ -236,9 +238,19 @@ __global__ void span_prefix_kernel(const float* __restrict__ G, int64_t NT, int 
   }
 }
 
-__global__ void span_combine_kernel(const double* __restrict__ PS, const int64_t* __restrict__ pairs,
-                                    const int64_t* __restrict__ spans, int64_t P, int T, int K,
-                                    const float* __restrict__ b, float* __restrict__ out) {
+// Sum of G over the frames [a, e) of one (tracklet, column) in float64, in frame order: what PS[e] - PS[a] is when
+// both are finite.  span_combine_kernel takes it when the running sum of span_prefix_kernel has met a NaN / Inf in an
+// EARLIER or inner frame: every later prefix value is non-finite then, although the span's own frames may all be finite.
+__device__ inline double span_sum_frames(const float* __restrict__ g, int64_t K2, int64_t a, int64_t e) {
+  double acc = 0.0;
+  for (int64_t t = a; t < e; ++t) acc += (double)g[t * K2];
+  return acc;
+}
+
+__global__ void span_combine_kernel(const double* __restrict__ PS, const float* __restrict__ G,
+                                    const int64_t* __restrict__ pairs, const int64_t* __restrict__ spans,
+                                    int64_t P, int T, int K, const float* __restrict__ b,
+                                    float* __restrict__ out) {
   const int64_t total = P * K;
   const int64_t K2 = 2 * (int64_t)K;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
@@ -247,9 +259,16 @@ __global__ void span_combine_kernel(const double* __restrict__ PS, const int64_t
     int64_t a = spans[2 * p], e = spans[2 * p + 1];
     a = a < 0 ? 0 : (a > T - 1 ? T - 1 : a);       // out-of-range / unused (-1) spans fall back to
     e = e < a + 1 ? (spans[2 * p] < 0 ? T : a + 1) : (e > T ? T : e);  // the whole segment / one frame
-    const double* ps = PS + (pairs[2 * p] * (T + 1)) * K2 + 2 * k;
-    const double* po = PS + (pairs[2 * p + 1] * (T + 1)) * K2 + 2 * k + 1;
-    double v = ((ps[e * K2] - ps[a * K2]) + (po[e * K2] - po[a * K2])) / (double)(e - a);
+    const int64_t s = pairs[2 * p], o = pairs[2 * p + 1];
+    const double* ps = PS + (s * (T + 1)) * K2 + 2 * k;
+    const double* po = PS + (o * (T + 1)) * K2 + 2 * k + 1;
+    // a prefix value is non-finite from the first NaN / Inf frame on (PS[a] non-finite implies PS[e] non-finite), so
+    // PS[e] alone tells whether the difference is usable; finite prefixes keep the difference and its bits
+    double ds = ps[e * K2] - ps[a * K2];
+    double dob = po[e * K2] - po[a * K2];
+    if (!isfinite(ps[e * K2])) ds = span_sum_frames(G + (s * T) * K2 + 2 * k, K2, a, e);
+    if (!isfinite(po[e * K2])) dob = span_sum_frames(G + (o * T) * K2 + 2 * k + 1, K2, a, e);
+    double v = (ds + dob) / (double)(e - a);
     if (b != nullptr) v += (double)b[k];
     out[i] = (float)(1.0 / (1.0 + exp(-v)));
   }
@@ -429,7 +448,7 @@ extern "C" int tspn_span_predicate_f32(const float* feats, int64_t NT, int64_t T
   hipLaunchKernelGGL(span_prefix_kernel, dim3(b1), dim3(256), 0, s, G, NT, (int)T, (int)(2 * K), PS);
   if ((rc = tspn::check_launch("tspn_span_predicate_f32(prefix)"))) return rc;
   const int b2 = (int)std::min<int64_t>(tspn::ceil_div(P * K, 256), 8192);
-  hipLaunchKernelGGL(span_combine_kernel, dim3(b2), dim3(256), 0, s, PS, pairs, spans, P, (int)T, (int)K,
-                     cls_b, out);
+  hipLaunchKernelGGL(span_combine_kernel, dim3(b2), dim3(256), 0, s, PS, G, pairs, spans, P, (int)T,
+                     (int)K, cls_b, out);
   return tspn::check_launch("tspn_span_predicate_f32(combine)");
 }

@@ -182,7 +182,16 @@ def _nt(a, b, bias=None, sigmoid=False):
 
 def _tr(a):
     """[M,N] -> [N,M] contiguous (tspn_transpose_td_f32)."""
+    if a.numel() == 0:
+        return a.new_zeros((a.shape[1], a.shape[0]))      # an empty batch: the C entry refuses zero-length axes
     return ops.transpose_td(a.contiguous().unsqueeze(0))[0]
+
+
+def _col_sums(g):
+    """Column sums of g [M,N], rows added in order (tspn_temporal_sum_f32): the bias gradients; zero for an empty batch."""
+    if g.shape[0] == 0:
+        return g.new_zeros((g.shape[1],))
+    return ops.temporal_sum(g.contiguous().unsqueeze(0))[0]
 
 
 class _LinearFn(torch.autograd.Function):
@@ -200,7 +209,7 @@ class _LinearFn(torch.autograd.Function):
         g = g.contiguous()
         gx = _nt(g, _tr(w)) if ctx.needs_input_grad[0] else None
         gw = _nt(_tr(g), _tr(x)) if ctx.needs_input_grad[1] else None
-        gb = ops.temporal_sum(g.unsqueeze(0))[0] if ctx.needs_input_grad[2] else None
+        gb = _col_sums(g) if ctx.needs_input_grad[2] else None
         return gx, gw, gb
 
 
@@ -236,7 +245,7 @@ class _PredicateHeadFn(torch.autograd.Function):
         gz = (g * out * (1.0 - out)).contiguous()
         gx = _nt(gz, _tr(w)) if ctx.needs_input_grad[0] else None
         gw = _nt(_tr(gz), _tr(x)) if ctx.needs_input_grad[1] else None
-        gb = ops.temporal_sum(gz.unsqueeze(0))[0] if ctx.needs_input_grad[2] else None
+        gb = _col_sums(gz) if ctx.needs_input_grad[2] else None
         return gx, gw, gb
 
 
@@ -289,6 +298,18 @@ class _TemporalHeadsDenseFn(torch.autograd.Function):
         return dx, _conv3_weight_grad(x, dz), dz.sum((0, 2)), d_head_w, g.sum((0, 2))
 
 
+def _tracklet_projections(feats, conv_w, conv_b):
+    """U‖V [NT, 2C, T] of tracklet features [NT, T, D] on the split-packed conv weight: the channels-last
+    kernel when D % 16 == 0, else what the fused eval pass does for such a D -- HIP transpose + the direct kernel -- so
+    that every model that scores can also be trained."""
+    d = feats.shape[2]
+    packed = ops.pack_conv3(conv_w, split=d)
+    bias2 = torch.cat([conv_b, torch.zeros_like(conv_b)])
+    if d % 16 == 0:
+        return ops.conv3_tc(feats, packed, bias2)
+    return ops.conv3(ops.transpose_td(feats), packed, bias2)
+
+
 class _TemporalHeadsTrackletFn(torch.autograd.Function):
     """Factorised pair encoder + heads on tracklet tensors for training.  Forward: the HIP
     projections U‖V (tspn_conv3_tc_f32 on the split-packed weight) and the indexed pair stage
@@ -300,10 +321,8 @@ class _TemporalHeadsTrackletFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feats, pairs, conv_w, conv_b, head_w, head_b):
-        d = feats.shape[2]
-        c = 2 * d
-        bias2 = torch.cat([conv_b, torch.zeros_like(conv_b)])
-        y = ops.conv3_tc(feats, ops.pack_conv3(conv_w, split=d), bias2)          # [NT, 2C, T]
+        c = 2 * feats.shape[2]
+        y = _tracklet_projections(feats, conv_w, conv_b)                          # [NT, 2C, T]
         s, o = pairs[:, 0].contiguous(), pairs[:, 1].contiguous()
         heads = ops.heads(y[:, :c].contiguous(), head_w, head_b, b=y[:, c:].contiguous(), ia=s, ib=o)
         ctx.save_for_backward(feats, pairs, conv_w, conv_b, head_w)
@@ -313,10 +332,8 @@ class _TemporalHeadsTrackletFn(torch.autograd.Function):
     def backward(ctx, g):
         feats, pairs, conv_w, conv_b, head_w = ctx.saved_tensors
         g = g.contiguous()
-        d = feats.shape[2]
-        c = 2 * d
-        bias2 = torch.cat([conv_b, torch.zeros_like(conv_b)])
-        y = ops.conv3_tc(feats, ops.pack_conv3(conv_w, split=d), bias2)
+        c = 2 * feats.shape[2]
+        y = _tracklet_projections(feats, conv_w, conv_b)
         u, v = y[:, :c], y[:, c:]
         du, dv = torch.zeros_like(u), torch.zeros_like(v)
         d_head_w = torch.zeros_like(head_w)

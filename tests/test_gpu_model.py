@@ -6,6 +6,7 @@ import torch
 
 import cases
 import oracle
+from train_reference import oracle_weights, train_reference as _oracle_train_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -117,13 +118,6 @@ def test_use_ppn_eval_and_train(tspn, device):
 def temporal_cfg(D, use_ppn=True):
     return cases.baseline_cfg(**{"RELPN.USE_PPN": use_ppn, "RELPN.USE_DPN": True,
                                  "RELPN.DPN.IN_CHANNELS": 2 * D, "PREDICT.FEATURE_DIM": 2 * D})
-
-
-def oracle_weights(sd):
-    return {"conv_w": t(sd[DPN_PRE + "conv.weight"]), "conv_b": t(sd[DPN_PRE + "conv.bias"]),
-            "dur_w": t(sd[DPN_PRE + "duration_pred.weight"]), "dur_b": t(sd[DPN_PRE + "duration_pred.bias"]),
-            "rel_w": t(sd[DPN_PRE + "relness_pred.weight"]), "rel_b": t(sd[DPN_PRE + "relness_pred.bias"]),
-            "cls_w": t(sd["classifier.rel_predictor.weight"]), "cls_b": t(sd["classifier.rel_predictor.bias"])}
 
 
 def test_temporal_forward_tracklets_fused(tspn, device):
@@ -440,22 +434,6 @@ def test_predict_loop_like_predict_py(tspn, device):
         np.testing.assert_array_equal(np.stack([p[1] for p in preds]), trip.numpy())
         np.testing.assert_array_equal(np.stack([p[2] for p in preds]), tids.numpy())
         assert preds[0][0].shape == () and preds[0][1].shape == (3,) and preds[0][2].shape == (2,)
-
-
-def _oracle_train_reference(v, pairs, sd, gt_dur, gt_rel, targets):
-    """The reference's intended DPN training step in plain torch autograd (CPU, float64): materialised
-    pair features -> oracle.dpn_head (relpn/dpn.py:69-73) -> BCEWithLogits (dpn.py:44); RelOIPool over the
-    segment -> RelationPredictor -> BCE (model.py:59-64).  Returns losses and parameter gradients."""
-    w = {k: x.double().requires_grad_(True) for k, x in oracle_weights(sd).items()}
-    pf, _ = oracle.pair_gather(t(v["tracklet_feats"]), t(v["tracklet_boxes"]), pairs)
-    rel, dur, _ = oracle.dpn_head(pf.double(), w["conv_w"], w["conv_b"], w["dur_w"], w["dur_b"], w["rel_w"], w["rel_b"])
-    losses = {"loss_duration": torch.nn.functional.binary_cross_entropy_with_logits(dur, gt_dur.double())}
-    if gt_rel is not None:
-        losses["loss_relationness"] = torch.nn.functional.binary_cross_entropy_with_logits(rel, gt_rel.double())
-    logit = oracle.predicate_head(pf.double().mean(dim=2), w["cls_w"], w["cls_b"])
-    losses["loss_rel"] = torch.nn.functional.binary_cross_entropy(logit, targets.double())
-    sum(losses.values()).backward()
-    return {k: float(x) for k, x in losses.items()}, {k: x.grad for k, x in w.items()}
 
 
 def test_dense_temporal_heads_input_gradient(tspn, device):

@@ -210,6 +210,33 @@ def test_rel_oi_pool_spans():
     assert oracle.rel_oi_pool(torch.ones(4, 7)).shape == (4, 7)
 
 
+def test_span_frames_rules_on_hand_written_rows():
+    """The frames an out-of-range / empty / unused span row pools over, written out by hand for T = 12:
+    every row selects at least one frame, none outside the segment; a valid row is taken as it is."""
+    T = 12
+    rows = [((-1, -1), (0, T)),            # "no span" (decode_spans' unused row): the whole segment
+            ((-3, 0), (0, T)),             # negative start, empty: the whole segment
+            ((-1, 10), (0, 10)),           # negative start, usable end: start clipped
+            ((5, 5), (5, 6)),              # empty: its first frame
+            ((7, 3), (7, 8)),              # reversed: its first frame
+            ((T - 1, T), (T - 1, T)),      # the last frame
+            ((T, T + 4), (T - 1, T)),      # starts one past the end: the last frame
+            ((T + 5, T + 9), (T - 1, T)),  # wholly beyond the end: the last frame
+            ((0, T + 1), (0, T)),          # end clipped
+            ((0, T), (0, T))]              # the whole segment, valid
+    for (s, e), want in rows:
+        assert oracle.span_frames(s, e, T) == want, (s, e)
+    assert oracle.span_frames(-1, -1, 1) == (0, 1) and oracle.span_frames(0, 0, 1) == (0, 1)
+    for s in range(T):                     # every valid row is unchanged
+        for e in range(s + 1, T + 1):
+            assert oracle.span_frames(s, e, T) == (s, e)
+    # rel_oi_pool applies it: the mean over the rewritten frames
+    x = torch.arange(len(rows) * 2 * T, dtype=torch.float64).reshape(len(rows), 2, T) ** 2
+    out = oracle.rel_oi_pool(x, torch.tensor([r[0] for r in rows]))
+    for p, (_, (a, e)) in enumerate(rows):
+        np.testing.assert_array_equal(out[p].numpy(), x[p, :, a:e].mean(1).numpy())
+
+
 def test_g8_bf16_semantics_pinned_by_reference_bf16_modules():
     """The bf16 restatement (operands bf16, exact products, wide sums, encoder activation rounded
     once) against the reference's DPNHead / RelationPredictor cast with .bfloat16() (torch CPU
