@@ -441,6 +441,32 @@ int tspn_span_predicate_f32(const float* feats, int64_t NT, int64_t T, int64_t D
                             const int64_t* spans, int64_t P, const float* cls_w, const float* cls_b,
                             int64_t K, float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- relations decoded with their temporal spans (csrc/relations/) ---------
+ * Build-defined (the reference decodes whole-segment relations only).  For S equal-shape segments of N
+ * tracklets and P pairs each, with the J = spans_per_pair proposals per pair that tspn_decode_spans_f32(top_k = J)
+ * wrote for the S*P pairs:
+ *   feats [S*N, T, D]; pairs int64 [S, P, 2] segment-local tracklet ids in [0, N); spans int64 [S*P, J, 2] frames
+ *   [start, end); span_scores fp32 [S*P, J] (already a sigmoid); span_counts int64 [S*P]; cls_w [K, 2D], cls_b [K] or
+ *   NULL; cls_logits [S, N, NO] per-tracklet class logits.
+ * A candidate (p, j, k), j < span_counts[p], scores  q * span_scores[p, j]  (one fp32 product) with q the value
+ * tspn_span_predicate_f32 returns for (pair p, spans[p, j]), bit for bit.  Per (p, j) the R = min(topk_per_span, K)
+ * best k by q, over the segment the best min(topk_per_seg, candidates) by the product; order of torch's stable
+ * descending sort (NaN above +Inf, lower flat index ((p*J + j)*R + r) on ties).
+ * Outputs, Mc = min(topk_per_seg, P*J*R) slots per segment: out_score [S, Mc], out_triplet int64 [S, Mc, 3] (subject
+ * class, predicate, object class; class = first argmax of the tracklet's cls_logits row), out_pair_tid int64
+ * [S, Mc, 2], out_span int64 [S, Mc, 2] (the spans row as given), out_span_rank int64 [S, Mc] (j), out_valid int64 [S]:
+ * the slots written; the rest are left untouched.
+ * TSPN_EUNSUPPORTED: K > 256, topk_per_seg > 1024, J > 16, P*J*R >= 2^31.                                        */
+size_t tspn_decode_span_relations_workspace_bytes(int64_t S, int64_t N, int64_t T, int64_t D, int64_t P, int64_t J,
+                                                  int64_t K, int64_t topk_per_span);
+int tspn_decode_span_relations_f32(const float* feats, int64_t S, int64_t N, int64_t T, int64_t D,
+                                   const int64_t* pairs, int64_t P, const int64_t* spans, const float* span_scores,
+                                   const int64_t* span_counts, int64_t J, const float* cls_w, const float* cls_b,
+                                   int64_t K, const float* cls_logits, int64_t NO, int64_t topk_per_span,
+                                   int64_t topk_per_seg, float* out_score, int64_t* out_triplet,
+                                   int64_t* out_pair_tid, int64_t* out_span, int64_t* out_span_rank,
+                                   int64_t* out_valid, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- bf16-operand path (BASELINE config 3: N=64, T=900, D=1024, bf16) ----
  * Semantics (build-defined; pinned by tests/golden/g8 against the reference's own DPNHead /
  * RelationPredictor modules cast with .bfloat16(), lib/modeling/relpn/dpn.py:55-73, model.py:76-88):

@@ -156,6 +156,9 @@ PROTOTYPES = {
     "tspn_conv3_tc_wino63_f16x3_set_tail_split": (_int, [_int]),
     "tspn_span_predicate_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "tspn_span_predicate_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "tspn_decode_span_relations_workspace_bytes": (_sz, [_i64] * 8),
+    "tspn_decode_span_relations_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64,
+                                              _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tspn_cast_bf16": (_int, [_vp, _i64, _vp, _vp]),
     "tspn_pack_conv3_bf16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),
     "tspn_transpose_cast_bf16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),

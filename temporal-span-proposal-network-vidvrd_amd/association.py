@@ -186,6 +186,22 @@ def load_trajectories(vid, fstart, fend, root="./vidvrd-baseline-output"):
         return [Track(**t) for t in json.load(fin)]
 
 
+def _span_cut(track, fstart, span):
+    """A fresh Track holding the frames span = [a, e) (segment-local) of a segment's tracklet: a span-bounded prediction
+    owns its trajectories, so a merge into one relation is never seen through another (unlike whole-segment
+    predictions, which share the segment's Track objects as in the reference)."""
+    a, e = (int(v) for v in np.asarray(span).tolist())
+    if not 0 <= a < e <= track.rois.shape[0]:
+        raise ValueError(f"span [{a}, {e}) does not lie inside a tracklet of {track.rois.shape[0]} frames")
+    return Track(fstart + a, fstart + e, track.rois[a:e], score=track.score, category=track.category,
+                 classeme=track.classeme, vsig=track.vsig, gt_trackid=track.gt_trackid)
+
+
+def _span_follows(prev, cur):
+    """`cur` starts inside `prev` and ends no earlier: what `_merge_trajs(prev, cur)` needs."""
+    return prev.pstart <= cur.pstart < prev.pend <= cur.pend
+
+
 def _as_tracks(trajs, fstart, fend):
     out = []
     for t in trajs:
@@ -295,6 +311,14 @@ def greedy_relational_association(dataset, short_term_relations, max_traj_num_in
     default = the reference's on-disk proposals (`load_trajectories`).
     `device`: a HIP device ("cuda", "cuda:0", torch.device): the trajectory IoUs of a segment come from one
     batched launch (module docstring) instead of one numpy evaluation per (prediction, candidate); same results.
+    Span-bounded predictions (build-defined; `predict_short_term_relations(spans_per_pair > 0)`): a 4-tuple
+    (score, triplet, (s_idx, o_idx), (a, e)) lasts the frames [fstart + a, fstart + e) only.  Its two trajectories are
+    fresh copies of the segment's tracklets cut to rois[a:e], not shared with any other prediction; it can extend a
+    relation `r` of the previous segment only if its trajectories start inside r's and end no earlier
+    (r.straj.pstart <= pstart < r.straj.pend <= pend, the same for the object) - so a span that stops before its
+    segment's end is not continued - and otherwise opens a new relation; the IoU test and everything else are as for
+    3-tuples, which take the reference's path unchanged.  `device=` cannot serve 4-tuples (ValueError): its IoU table
+    holds one row per whole tracklet of the segment, not per prediction's cut.
     `stats`: optional dict, receives counters (`iou_launches`, `iou_lookups`, `iou_host_rows`, `segments`).
     Returns the list of serialised video relations (`dataset` supplies the names; None keeps ids)."""
     if trajectories is None:
@@ -303,6 +327,9 @@ def greedy_relational_association(dataset, short_term_relations, max_traj_num_in
         provider = trajectories
     else:
         provider = lambda vid, fs, fe: trajectories[(vid, fs, fe)]  # noqa: E731
+    if device is not None and any(len(p) == 4 for _, prediction in short_term_relations for p in prediction[0]):
+        raise ValueError("greedy_relational_association: span-bounded predictions (4-tuples) need device=None: the batched "
+                         "IoU table is per whole tracklet")
     short_term_relations.sort(key=lambda x: int(x[0][1]))   # in place, like the reference
     video_relation_list = []
     last_modify_rel_list = []
@@ -336,6 +363,9 @@ def greedy_relational_association(dataset, short_term_relations, max_traj_num_in
             s_cid, pid, o_cid = pred[1]
             s_idx, o_idx = pred[2]
             straj, otraj = trajs[int(s_idx)], trajs[int(o_idx)]
+            spanned = len(pred) == 4
+            if spanned:
+                straj, otraj = _span_cut(straj, fstart, pred[3]), _span_cut(otraj, fstart, pred[3])
             if i == 0:
                 r = VideoRelation(vid, s_cid, pid, o_cid, straj, otraj, confs=conf_score)
                 video_relation_list.append(r)
@@ -345,6 +375,8 @@ def greedy_relational_association(dataset, short_term_relations, max_traj_num_in
             candidates = by_triplet.get(_triplet_key(pred[1]), ())
             for r in candidates:
                 if straj.pstart < r.fend and otraj.pstart < r.fend:
+                    if spanned and not (_span_follows(r.straj, straj) and _span_follows(r.otraj, otraj)):
+                        continue
                     lookups += 1
                     if r.both_overlap(straj, otraj, table=table, s_idx=s_idx, o_idx=o_idx):
                         r.extend(straj, otraj, conf_score)
@@ -378,19 +410,26 @@ def _triplet_key(triplet):
 # ~2 000 launches per video: measured 489 ms per video against 385 without it (profiles/r6/cfg5_associate.md).  Videos are
 # independent, so it runs in a worker PROCESS: the driver hands over a video's short-term relations (a few MB, pickled)
 # and carries on.
-def short_term_relations_from_arrays(segments, scores, triplets, pairs, boxes=None):
+def short_term_relations_from_arrays(segments, scores, triplets, pairs, boxes=None, spans=None):
     """The decoded top-k of a video's segments as arrays -> the structures `greedy_relational_association` takes.
     segments: [(vid, fstart, fend)] x S; scores [S][K]; triplets [S][K,3]; pairs [S][K,2] (tracklet ids inside the segment),
     as `BaseModel.decode` / predict.py:106-116 produce them per segment; boxes (optional) [S][N,L,4] -> the trajectories
-    dict.  Arrays keep their dtypes (a relation's score is the mean of the scores it absorbed).  Returns
-    (short_term_relations, trajectories | None)."""
+    dict.  spans (optional) [S][K,2]: frames [start, end) inside the segment per prediction, as
+    `BaseModel.decode_span_relations` produces them -> span-bounded 4-tuple predictions.  Arrays keep their dtypes (a
+    relation's score is the mean of the scores it absorbed).  Returns (short_term_relations, trajectories | None)."""
     rels, trajs = [], ({} if boxes is not None else None)
     for s, index in enumerate(segments):
         index = (index[0], int(index[1]), int(index[2]))
         sc, tr, pr = np.asarray(scores[s]), np.asarray(triplets[s]), np.asarray(pairs[s])
         if tr.shape != (sc.shape[0], 3) or pr.shape != (sc.shape[0], 2):
             raise ValueError(f"segment {index}: scores {sc.shape}, triplets {tr.shape}, pairs {pr.shape} do not belong together")
-        rels.append((index, (list(zip(sc, tr, pr)), None, None)))
+        if spans is None:
+            rels.append((index, (list(zip(sc, tr, pr)), None, None)))
+        else:
+            sp = np.asarray(spans[s])
+            if sp.shape != (sc.shape[0], 2):
+                raise ValueError(f"segment {index}: spans {sp.shape} for {sc.shape[0]} predictions")
+            rels.append((index, (list(zip(sc, tr, pr, sp)), None, None)))
         if boxes is not None:
             trajs[index] = np.asarray(boxes[s], dtype=np.float64)
     return rels, trajs
@@ -482,12 +521,14 @@ class AssociationWorker:
         self._conn.send((key, short_term_relations, trajectories, out_path, bool(return_relations)))
         self._inflight += 1
 
-    def submit_arrays(self, key, segments, scores, triplets, pairs, boxes, out_path=None, return_relations=True):
+    def submit_arrays(self, key, segments, scores, triplets, pairs, boxes, out_path=None, return_relations=True, spans=None):
         """`submit` with the video's decoded results as arrays (`short_term_relations_from_arrays` runs in the worker):
         pickling a VidOR-scale video's 12 000 predictions as tuples of small arrays costs the driving process ~80 ms
         and the worker as much again; as five arrays it is under a millisecond."""
-        self._conn.send((key, {"segments": list(segments), "scores": scores, "triplets": triplets, "pairs": pairs,
-                               "boxes": boxes}, None, out_path, bool(return_relations)))
+        arrays = {"segments": list(segments), "scores": scores, "triplets": triplets, "pairs": pairs, "boxes": boxes}
+        if spans is not None:                                    # span-bounded predictions: a worker with device=None only
+            arrays["spans"] = spans
+        self._conn.send((key, arrays, None, out_path, bool(return_relations)))
         self._inflight += 1
 
     def result(self):

@@ -17,6 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 CSRC_EVAL = os.path.join(CSRC, "eval")   # evaluation kernels (their variant table: tests/eval_kernel_variants.py)
+CSRC_REL = os.path.join(CSRC, "relations")   # span relation decode (its variant table: tests/relations_kernel_variants.py)
 LIB_NAME = "libtspn_mi355x.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 ARCH = "gfx950"
@@ -43,11 +44,13 @@ NO_SPILL_KERNELS = ("conv3_wino63_kernel", "heads_pairgrid4_kernel", "heads_pair
 
 
 def sources():
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC_EVAL, "*.hip")))
+    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC_EVAL, "*.hip")) +
+                  glob.glob(os.path.join(CSRC_REL, "*.hip")))
 
 
 def _headers():
     return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC_EVAL, "*.h")) + \
+        glob.glob(os.path.join(CSRC_REL, "*.h")) + \
         glob.glob(os.path.join(ROOT, "include", "*.h")) + \
         [os.path.abspath(__file__)]
 

@@ -1,0 +1,212 @@
+// f5: relations decoded WITH their temporal spans (gfx950).
+//
+// tspn_decode_topk_f32 decodes relations that last their whole segment and score as the predicate sigmoid alone.  Here
+// every pair brings the J span proposals of tspn_decode_spans_f32; a candidate is (pair p, span j, predicate k), its
+// score the fp32 product  q[p,j,k] * score[p,j]  of the span-pooled predicate sigmoid (the very value
+// tspn_span_predicate_f32 returns for that row: tspn::span_logit) and the span's relationness.  Per (p, j) row the R
+// best k by q, over the segment the M best candidates by the product, both in torch's stable descending order
+// (tspn::order_key: NaN above +Inf, lower index on ties).  Build-defined, DESIGN.md 2: the reference has no counterpart
+// (its RelNMS is a stub and predict.py never reads the duration proposals).
+//
+//   stage a  G = f W'^T and its float64 prefix sums over time (tspn::span_prefix_stage, shared with span pooling)
+//   kernel b one wave per (pair, span) row: the K <= 256 values q formed in registers from the prefix differences,
+//            R rounds of wave arg-max; writes R x (key of the product, product, k).  A row j >= count[p] writes key 0,
+//            below every real key: [rows, K] never reaches HBM
+//   kernel c one workgroup per segment: tspn::select_topk_sorted over the P*J*R keys, then the gathers (pair ids,
+//            predicate, class argmax, span, span rank)
+#include <algorithm>
+
+#include "tspn_common.h"
+#include "tspn_span_pool.h"
+#include "tspn_topk_select.h"
+
+namespace {
+
+constexpr int VPT = 4;        // values per lane in kernel b -> K <= 256
+constexpr int MAX_J = 16;
+
+using tspn::key_before;
+using tspn::order_key;
+
+__global__ __launch_bounds__(256) void span_row_topk_kernel(
+    const double* __restrict__ PS, const float* __restrict__ G, const int64_t* __restrict__ pairs,
+    const int64_t* __restrict__ spans, const float* __restrict__ span_scores,
+    const int64_t* __restrict__ span_counts, const float* __restrict__ b, int64_t rows, int N, int P, int J, int T,
+    int K, int R, unsigned* __restrict__ key, float* __restrict__ sc, int* __restrict__ ix) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const int64_t pr = row / J;                  // pair over all segments
+  const int j = (int)(row - pr * J);
+  if ((int64_t)j >= span_counts[pr]) {         // not a proposal: nothing the segment stage can select
+    for (int r = lane; r < R; r += 64) {
+      key[row * R + r] = 0u;
+      sc[row * R + r] = 0.f;
+      ix[row * R + r] = -1;
+    }
+    return;
+  }
+  const int64_t seg = pr / P;
+  const int64_t s = seg * N + pairs[2 * pr], o = seg * N + pairs[2 * pr + 1];
+  const int64_t a0 = spans[2 * row], e0 = spans[2 * row + 1];
+  const float w = span_scores[row];
+  const int64_t K2 = 2 * (int64_t)K;
+  float v[VPT];
+  unsigned kv[VPT];
+#pragma unroll
+  for (int i = 0; i < VPT; ++i) {
+    const int k = lane + 64 * i;
+    v[i] = k < K ? tspn::span_logit(PS, G, s, o, a0, e0, T, K2, k, b) : 0.f;
+    kv[i] = order_key(v[i]);
+  }
+  unsigned used = 0;
+  // R <= K and every real value has a key > 0: each round selects an unused k < K
+  for (int r = 0; r < R; ++r) {
+    unsigned bk = 0;
+    int bi = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < VPT; ++i) {
+      const int k = lane + 64 * i;
+      if (k < K && !((used >> i) & 1u) && key_before(kv[i], k, bk, bi)) {
+        bk = kv[i];
+        bi = k;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned ok = __shfl_xor(bk, off);
+      const int oi = __shfl_xor(bi, off);
+      if (key_before(ok, oi, bk, bi)) {
+        bk = ok;
+        bi = oi;
+      }
+    }
+    if ((bi & 63) == lane && bi < K) {           // the owner of the winner writes the candidate
+      float bv = v[0];
+#pragma unroll
+      for (int i = 1; i < VPT; ++i)
+        if ((bi >> 6) == i) bv = v[i];
+      used |= 1u << (bi >> 6);
+      const float prod = bv * w;                 // one rounding (-ffp-contract=off)
+      key[row * R + r] = order_key(prod);
+      sc[row * R + r] = prod;
+      ix[row * R + r] = bi;
+    }
+  }
+}
+
+__global__ __launch_bounds__(tspn::kSelectThreads) void segment_span_topk_kernel(
+    const unsigned* __restrict__ key, const float* __restrict__ sc, const int* __restrict__ ix,
+    const int64_t* __restrict__ pairs, const int64_t* __restrict__ spans, const int64_t* __restrict__ span_counts,
+    const float* __restrict__ cls, int N, int NO, int P, int J, int R, int mcap, int topk_seg,
+    float* __restrict__ out_score, int64_t* __restrict__ out_trip, int64_t* __restrict__ out_tid,
+    int64_t* __restrict__ out_span, int64_t* __restrict__ out_rank, int64_t* __restrict__ out_valid) {
+  __shared__ tspn::SelectLds L;
+  __shared__ unsigned s_rows;
+
+  const int tid = threadIdx.x;
+  const int64_t seg = blockIdx.x;
+  const int Q = P * J * R;
+  // ---- the segment's real candidates: R per row j < count[p], exactly the rows kernel b gave real keys
+  if (tid == 0) s_rows = 0;
+  __syncthreads();
+  unsigned mine = 0;
+  for (int p = tid; p < P; p += tspn::kSelectThreads) {
+    const int64_t c = span_counts[seg * P + p];
+    mine += (unsigned)(c < 0 ? 0 : (c > J ? J : c));
+  }
+  if (mine) atomicAdd(&s_rows, mine);
+  __syncthreads();
+  const int64_t valid = (int64_t)s_rows * R;
+  const int M = (int)(valid < topk_seg ? valid : topk_seg);
+  if (tid == 0) out_valid[seg] = M;
+  if (M == 0) return;                            // the same for every thread
+
+  const unsigned* kseg = key + seg * Q;
+  tspn::select_topk_sorted(L, [kseg](int i) { return kseg[i]; }, Q, M);
+
+  // ---- gathers: score, pair ids, predicate id, class labels, span and its rank
+  for (int r = tid; r < M; r += tspn::kSelectThreads) {
+    const int flat = L.ki[r];
+    const int row = flat / R;
+    const int p = row / J, j = row - p * J;
+    const int64_t pr = seg * P + p;
+    const int64_t ts = pairs[2 * pr], to = pairs[2 * pr + 1];
+    const int64_t o = seg * mcap + r;
+    out_score[o] = sc[seg * Q + flat];
+    out_tid[2 * o] = ts;
+    out_tid[2 * o + 1] = to;
+    out_trip[3 * o] = tspn::argmax_first(cls + (seg * N + ts) * NO, NO);
+    out_trip[3 * o + 1] = ix[seg * Q + flat];
+    out_trip[3 * o + 2] = tspn::argmax_first(cls + (seg * N + to) * NO, NO);
+    out_span[2 * o] = spans[2 * (pr * J + j)];
+    out_span[2 * o + 1] = spans[2 * (pr * J + j) + 1];
+    out_rank[o] = j;
+  }
+}
+
+size_t cand_bytes(int64_t S, int64_t P, int64_t J, int64_t R) {
+  return tspn::align_up((size_t)S * P * J * R * sizeof(float), 256);   // one of the three arrays (key, product, k)
+}
+
+}  // namespace
+
+extern "C" size_t tspn_decode_span_relations_workspace_bytes(int64_t S, int64_t N, int64_t T, int64_t D, int64_t P,
+                                                             int64_t J, int64_t K, int64_t topk_per_span) {
+  if (S <= 0 || N <= 0 || T <= 0 || D <= 0 || P <= 0 || J <= 0 || K <= 0 || topk_per_span <= 0) return 0;
+  const int64_t R = std::min<int64_t>(topk_per_span, K);
+  return tspn::align_up(tspn::span_prefix_workspace_bytes(S * N, T, D, K), 256) + 3 * cand_bytes(S, P, J, R);
+}
+
+extern "C" int tspn_decode_span_relations_f32(const float* feats, int64_t S, int64_t N, int64_t T, int64_t D,
+                                              const int64_t* pairs, int64_t P, const int64_t* spans,
+                                              const float* span_scores, const int64_t* span_counts, int64_t J,
+                                              const float* cls_w, const float* cls_b, int64_t K,
+                                              const float* cls_logits, int64_t NO, int64_t topk_per_span,
+                                              int64_t topk_per_seg, float* out_score, int64_t* out_triplet,
+                                              int64_t* out_pair_tid, int64_t* out_span, int64_t* out_span_rank,
+                                              int64_t* out_valid, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+  const char* who = "tspn_decode_span_relations_f32";
+  TSPN_REQUIRE(S >= 0 && N >= 0 && P >= 0 && T > 0 && D > 0 && J > 0 && K > 0 && NO > 0 && topk_per_span > 0 &&
+                   topk_per_seg > 0 && T < (1 << 30) && N < (1LL << 31) && P < (1LL << 31) && S < (1LL << 31),
+               TSPN_EINVAL, "%s: bad sizes S=%lld N=%lld T=%lld D=%lld P=%lld J=%lld K=%lld NO=%lld", who,
+               (long long)S, (long long)N, (long long)T, (long long)D, (long long)P, (long long)J, (long long)K,
+               (long long)NO);
+  TSPN_REQUIRE(K <= 64 * VPT, TSPN_EUNSUPPORTED, "%s: K=%lld > %d", who, (long long)K, 64 * VPT);
+  TSPN_REQUIRE(topk_per_seg <= tspn::kSelectMaxM, TSPN_EUNSUPPORTED, "%s: topk_per_seg=%lld > %d", who,
+               (long long)topk_per_seg, tspn::kSelectMaxM);
+  TSPN_REQUIRE(J <= MAX_J, TSPN_EUNSUPPORTED, "%s: spans_per_pair J=%lld > %d", who, (long long)J, MAX_J);
+  const int64_t R = std::min<int64_t>(topk_per_span, K);
+  TSPN_REQUIRE(P * J * R < (1LL << 31), TSPN_EUNSUPPORTED, "%s: P*J*topk_per_span = %lld candidates per segment", who,
+               (long long)(P * J * R));
+  if (S == 0 || P == 0) return TSPN_OK;
+  TSPN_REQUIRE(N > 0, TSPN_EINVAL, "%s: pairs without tracklets", who);
+  TSPN_REQUIRE(feats && pairs && spans && span_scores && span_counts && cls_w && cls_logits && out_score &&
+                   out_triplet && out_pair_tid && out_span && out_span_rank && out_valid,
+               TSPN_EINVAL, "%s: null pointer", who);
+  const size_t pre = tspn::align_up(tspn::span_prefix_workspace_bytes(S * N, T, D, K), 256);
+  const size_t cb = cand_bytes(S, P, J, R);
+  TSPN_REQUIRE(workspace && workspace_bytes >= pre + 3 * cb, TSPN_EWORKSPACE, "%s: workspace %zu < %zu bytes", who,
+               workspace_bytes, pre + 3 * cb);
+  const int64_t rows = S * P * J;
+  const int64_t nb = tspn::ceil_div(rows, 4);
+  TSPN_REQUIRE(nb < (1LL << 31), TSPN_EUNSUPPORTED, "%s: grid too large", who);
+  const float* G = nullptr;
+  const double* PS = nullptr;
+  int rc = tspn::span_prefix_stage(feats, S * N, T, D, cls_w, K, workspace, pre, stream, &G, &PS, who);
+  if (rc) return rc;
+  char* ws = static_cast<char*>(workspace) + pre;
+  unsigned* key = reinterpret_cast<unsigned*>(ws);
+  float* sc = reinterpret_cast<float*>(ws + cb);
+  int* ix = reinterpret_cast<int*>(ws + 2 * cb);
+  hipStream_t s = TSPN_STREAM(stream);
+  hipLaunchKernelGGL(span_row_topk_kernel, dim3((unsigned)nb), dim3(256), 0, s, PS, G, pairs, spans, span_scores,
+                     span_counts, cls_b, rows, (int)N, (int)P, (int)J, (int)T, (int)K, (int)R, key, sc, ix);
+  if ((rc = tspn::check_launch("tspn_decode_span_relations_f32(rows)"))) return rc;
+  const int64_t mcap = std::min<int64_t>(topk_per_seg, P * J * R);
+  hipLaunchKernelGGL(segment_span_topk_kernel, dim3((unsigned)S), dim3(tspn::kSelectThreads), 0, s, key, sc, ix, pairs,
+                     spans, span_counts, cls_logits, (int)N, (int)NO, (int)P, (int)J, (int)R, (int)mcap,
+                     (int)topk_per_seg, out_score, out_triplet, out_pair_tid, out_span, out_span_rank, out_valid);
+  return tspn::check_launch("tspn_decode_span_relations_f32(segment)");
+}

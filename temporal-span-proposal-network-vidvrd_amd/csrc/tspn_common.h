@@ -109,6 +109,13 @@ size_t pair_predicate_workspace_bytes(int64_t NT, int64_t D, int64_t K);
 int pair_predicate(const float* fbar, int64_t NT, int64_t D, const int64_t* pairs, int64_t P,
                    const float* cls_w, const float* cls_b, int64_t K, float* out, void* workspace,
                    size_t workspace_bytes, void* stream);
+// First stage of span pooling (tspn_linear.hip), shared by tspn_span_predicate_f32 and tspn_decode_span_relations_f32:
+// G [NT*T, 2K] = feats . cls_w read as [2K, D], and PS [NT, T+1, 2K], its float64 prefix sums over time.  Both live in
+// the first span_prefix_workspace_bytes() of `workspace`; `who` names the entry point in the workspace error.
+size_t span_prefix_workspace_bytes(int64_t NT, int64_t T, int64_t D, int64_t K);
+int span_prefix_stage(const float* feats, int64_t NT, int64_t T, int64_t D, const float* cls_w, int64_t K,
+                      void* workspace, size_t workspace_bytes, void* stream, const float** G_out,
+                      const double** PS_out, const char* who);
 
 }  // namespace tspn
 

@@ -24,13 +24,15 @@
 #include <cmath>
 
 #include "tspn_common.h"
+#include "tspn_topk_select.h"
 
 namespace {
 
 constexpr int VPT = 4;        // values per lane in kernel 1 -> K <= 256
-constexpr int SEG_THREADS = 1024;
-constexpr int MAX_M = 1024;
+constexpr int SEG_THREADS = tspn::kSelectThreads;
+constexpr int MAX_M = tspn::kSelectMaxM;
 
+using tspn::argmax_first;
 using tspn::key_before;
 using tspn::order_key;
 
@@ -84,139 +86,19 @@ __global__ __launch_bounds__(256) void pair_topk_kernel(const float* __restrict_
   }
 }
 
-__device__ int argmax_first(const float* p, int n) {   // torch.argmax: the first NaN, else the first maximum
-  unsigned bk = order_key(p[0]);
-  int bi = 0;
-  for (int i = 1; i < n; ++i) {
-    const unsigned k = order_key(p[i]);
-    if (k > bk) {
-      bk = k;
-      bi = i;
-    }
-  }
-  return bi;
-}
-
 __global__ __launch_bounds__(SEG_THREADS) void segment_topk_kernel(
     const float* __restrict__ sc, const int* __restrict__ ix, const int64_t* __restrict__ pairs,
     const float* __restrict__ cls_sub, const float* __restrict__ cls_obj, int64_t ld, int64_t seg_rows,
     int64_t row_mul, int P, int R, int NO, int M, float* __restrict__ out_score,
     int64_t* __restrict__ out_trip, int64_t* __restrict__ out_tid) {
-  __shared__ unsigned hist[256];
-  __shared__ unsigned s_prefix, s_need, s_count;
-  __shared__ unsigned kk[MAX_M];
-  __shared__ int ki[MAX_M];
+  __shared__ tspn::SelectLds L;
 
   const int tid = threadIdx.x;
   const int64_t seg = blockIdx.x;
   const int Q = P * R;
   const float* cand = sc + seg * Q;
-
-  // ---- exact M-th largest key by 4 radix passes (most significant byte first)
-  if (tid == 0) {
-    s_prefix = 0;
-    s_need = (unsigned)M;
-  }
-  __syncthreads();
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 24 - 8 * pass;
-    if (tid < 256) hist[tid] = 0;
-    __syncthreads();
-    const unsigned prefix = s_prefix;
-    const unsigned himask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
-    for (int i = tid; i < Q; i += SEG_THREADS) {
-      const unsigned k = order_key(cand[i]);
-      if ((k & himask) == prefix) atomicAdd(&hist[(k >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      unsigned need = s_need, acc = 0;
-      int b = 255;
-      for (; b >= 0; --b) {
-        if (acc + hist[b] >= need) break;
-        acc += hist[b];
-      }
-      s_prefix = prefix | ((unsigned)b << shift);
-      s_need = need - acc;  // how many we still need inside bucket b
-    }
-    __syncthreads();
-  }
-  const unsigned kth = s_prefix;     // key of the M-th largest candidate
-  const unsigned ties_needed = s_need;  // of the candidates equal to it, the lowest indices win
-  __syncthreads();  // everyone has read s_prefix / s_need before they are reused below
-  // ---- among ties: the `ties_needed`-th smallest flat index (4 byte-wide passes, lowest first)
-  if (tid == 0) {
-    s_prefix = 0;
-    s_need = ties_needed;
-  }
-  __syncthreads();
-  for (int pass = 0; pass < 4; ++pass) {
-    const int shift = 24 - 8 * pass;
-    if (tid < 256) hist[tid] = 0;
-    __syncthreads();
-    const unsigned prefix = s_prefix;
-    const unsigned himask = pass == 0 ? 0u : (0xffffffffu << (shift + 8));
-    for (int i = tid; i < Q; i += SEG_THREADS) {
-      if (order_key(cand[i]) == kth && (((unsigned)i) & himask) == prefix)
-        atomicAdd(&hist[(((unsigned)i) >> shift) & 255u], 1u);
-    }
-    __syncthreads();
-    if (tid == 0) {
-      unsigned need = s_need, acc = 0;
-      int b = 0;
-      for (; b < 256; ++b) {
-        if (acc + hist[b] >= need) break;
-        acc += hist[b];
-      }
-      s_prefix = prefix | ((unsigned)b << shift);
-      s_need = need - acc;
-    }
-    __syncthreads();
-  }
-  const unsigned last_tie_idx = s_prefix;  // ties with index <= this are selected
-
-  // ---- compaction of the M winners into LDS (unordered), then bitonic sort
-  if (tid == 0) s_count = 0;
-  __syncthreads();
-  for (int i = tid; i < Q; i += SEG_THREADS) {
-    const unsigned k = order_key(cand[i]);
-    if (k > kth || (k == kth && (unsigned)i <= last_tie_idx)) {
-      const unsigned slot = atomicAdd(&s_count, 1u);
-      if (slot < (unsigned)MAX_M) {
-        kk[slot] = k;
-        ki[slot] = i;
-      }
-    }
-  }
-  __syncthreads();
-  int m2 = 1;
-  while (m2 < M) m2 <<= 1;
-  for (int i = tid; i < m2; i += SEG_THREADS)
-    if (i >= M) {
-      kk[i] = 0u;                                  // below every real key
-      ki[i] = 0x7fffffff;
-    }
-  __syncthreads();
-  for (int k = 2; k <= m2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < m2; i += SEG_THREADS) {
-        const int l = i ^ j;
-        if (l > i) {
-          const unsigned vi = kk[i], vl = kk[l];
-          const int ii = ki[i], il = ki[l];
-          const bool fwd = (i & k) == 0;
-          const bool swap = fwd ? key_before(vl, il, vi, ii) : key_before(vi, ii, vl, il);
-          if (swap) {
-            kk[i] = vl;
-            kk[l] = vi;
-            ki[i] = il;
-            ki[l] = ii;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  tspn::select_topk_sorted(L, [cand](int i) { return order_key(cand[i]); }, Q, M);
+  const int* ki = L.ki;
 
   // ---- gathers: pair ids, predicate id, class labels
   for (int r = tid; r < M; r += SEG_THREADS) {

@@ -15,6 +15,7 @@
 #include <algorithm>
 
 #include "tspn_common.h"
+#include "tspn_span_pool.h"
 #include "tspn_device.h"
 
 namespace {
@@ -238,15 +239,6 @@ __global__ void span_prefix_kernel(const float* __restrict__ G, int64_t NT, int 
   }
 }
 
-// Sum of G over the frames [a, e) of one (tracklet, column) in float64, in frame order: what PS[e] - PS[a] is when
-// both are finite.  span_combine_kernel takes it when the running sum of span_prefix_kernel has met a NaN / Inf in an
-// EARLIER or inner frame: every later prefix value is non-finite then, although the span's own frames may all be finite.
-__device__ inline double span_sum_frames(const float* __restrict__ g, int64_t K2, int64_t a, int64_t e) {
-  double acc = 0.0;
-  for (int64_t t = a; t < e; ++t) acc += (double)g[t * K2];
-  return acc;
-}
-
 __global__ void span_combine_kernel(const double* __restrict__ PS, const float* __restrict__ G,
                                     const int64_t* __restrict__ pairs, const int64_t* __restrict__ spans,
                                     int64_t P, int T, int K, const float* __restrict__ b,
@@ -256,21 +248,7 @@ __global__ void span_combine_kernel(const double* __restrict__ PS, const float* 
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < total;
        i += (int64_t)gridDim.x * blockDim.x) {
     const int64_t p = i / K, k = i - p * K;
-    int64_t a = spans[2 * p], e = spans[2 * p + 1];
-    a = a < 0 ? 0 : (a > T - 1 ? T - 1 : a);       // out-of-range / unused (-1) spans fall back to
-    e = e < a + 1 ? (spans[2 * p] < 0 ? T : a + 1) : (e > T ? T : e);  // the whole segment / one frame
-    const int64_t s = pairs[2 * p], o = pairs[2 * p + 1];
-    const double* ps = PS + (s * (T + 1)) * K2 + 2 * k;
-    const double* po = PS + (o * (T + 1)) * K2 + 2 * k + 1;
-    // a prefix value is non-finite from the first NaN / Inf frame on (PS[a] non-finite implies PS[e] non-finite), so
-    // PS[e] alone tells whether the difference is usable; finite prefixes keep the difference and its bits
-    double ds = ps[e * K2] - ps[a * K2];
-    double dob = po[e * K2] - po[a * K2];
-    if (!isfinite(ps[e * K2])) ds = span_sum_frames(G + (s * T) * K2 + 2 * k, K2, a, e);
-    if (!isfinite(po[e * K2])) dob = span_sum_frames(G + (o * T) * K2 + 2 * k + 1, K2, a, e);
-    double v = (ds + dob) / (double)(e - a);
-    if (b != nullptr) v += (double)b[k];
-    out[i] = (float)(1.0 / (1.0 + exp(-v)));
+    out[i] = tspn::span_logit(PS, G, pairs[2 * p], pairs[2 * p + 1], spans[2 * p], spans[2 * p + 1], T, K2, k, b);
   }
 }
 
@@ -420,9 +398,34 @@ SpanLayout span_layout(int64_t NT, int64_t T, int64_t D, int64_t K) {
 }
 }  // namespace
 
-extern "C" size_t tspn_span_predicate_workspace_bytes(int64_t NT, int64_t T, int64_t D, int64_t K) {
+size_t tspn::span_prefix_workspace_bytes(int64_t NT, int64_t T, int64_t D, int64_t K) {
   if (NT <= 0 || T <= 0 || D <= 0 || K <= 0) return 0;
   return span_layout(NT, T, D, K).total;
+}
+
+// G[(trk, t), 2k + half] = f[trk, t, :] . cls_w[k, half*D : (half+1)*D] and its float64 prefix sums over time, both in
+// the first span_prefix_workspace_bytes of `workspace`
+int tspn::span_prefix_stage(const float* feats, int64_t NT, int64_t T, int64_t D, const float* cls_w, int64_t K,
+                            void* workspace, size_t workspace_bytes, void* stream, const float** G_out,
+                            const double** PS_out, const char* who) {
+  const SpanLayout L = span_layout(NT, T, D, K);
+  TSPN_REQUIRE(workspace && workspace_bytes >= L.total, TSPN_EWORKSPACE, "%s: workspace %zu < %zu bytes", who,
+               workspace_bytes, L.total);
+  char* ws = static_cast<char*>(workspace);
+  float* G = reinterpret_cast<float*>(ws + L.lin);
+  double* PS = reinterpret_cast<double*>(ws + L.lin + L.g);
+  int rc = tspn::linear(feats, NT * T, D, D, cls_w, D, nullptr, 2 * K, G, 0, ws, L.lin, stream);
+  if (rc) return rc;
+  const int b1 = (int)std::min<int64_t>(tspn::ceil_div(NT * 2 * K, 256), 8192);
+  hipLaunchKernelGGL(span_prefix_kernel, dim3(b1), dim3(256), 0, TSPN_STREAM(stream), G, NT, (int)T, (int)(2 * K), PS);
+  if ((rc = tspn::check_launch("tspn_span_predicate_f32(prefix)"))) return rc;
+  *G_out = G;
+  *PS_out = PS;
+  return TSPN_OK;
+}
+
+extern "C" size_t tspn_span_predicate_workspace_bytes(int64_t NT, int64_t T, int64_t D, int64_t K) {
+  return tspn::span_prefix_workspace_bytes(NT, T, D, K);
 }
 
 extern "C" int tspn_span_predicate_f32(const float* feats, int64_t NT, int64_t T, int64_t D,
@@ -434,19 +437,12 @@ extern "C" int tspn_span_predicate_f32(const float* feats, int64_t NT, int64_t T
                (long long)T, (long long)D, (long long)K, (long long)P);
   if (P == 0 || NT == 0) return TSPN_OK;
   TSPN_REQUIRE(feats && pairs && spans && cls_w && out, TSPN_EINVAL, "tspn_span_predicate_f32: null pointer");
-  const SpanLayout L = span_layout(NT, T, D, K);
-  TSPN_REQUIRE(workspace && workspace_bytes >= L.total, TSPN_EWORKSPACE,
-               "tspn_span_predicate_f32: workspace %zu < %zu bytes", workspace_bytes, L.total);
-  char* ws = static_cast<char*>(workspace);
-  float* G = reinterpret_cast<float*>(ws + L.lin);
-  double* PS = reinterpret_cast<double*>(ws + L.lin + L.g);
-  // G[(trk, t), 2k + half] = f[trk, t, :] . cls_w[k, half*D : (half+1)*D]
-  int rc = tspn::linear(feats, NT * T, D, D, cls_w, D, nullptr, 2 * K, G, 0, ws, L.lin, stream);
+  const float* G = nullptr;
+  const double* PS = nullptr;
+  int rc = tspn::span_prefix_stage(feats, NT, T, D, cls_w, K, workspace, workspace_bytes, stream, &G, &PS,
+                                   "tspn_span_predicate_f32");
   if (rc) return rc;
   hipStream_t s = TSPN_STREAM(stream);
-  const int b1 = (int)std::min<int64_t>(tspn::ceil_div(NT * 2 * K, 256), 8192);
-  hipLaunchKernelGGL(span_prefix_kernel, dim3(b1), dim3(256), 0, s, G, NT, (int)T, (int)(2 * K), PS);
-  if ((rc = tspn::check_launch("tspn_span_predicate_f32(prefix)"))) return rc;
   const int b2 = (int)std::min<int64_t>(tspn::ceil_div(P * K, 256), 8192);
   hipLaunchKernelGGL(span_combine_kernel, dim3(b2), dim3(256), 0, s, PS, G, pairs, spans, P, (int)T,
                      (int)K, cls_b, out);

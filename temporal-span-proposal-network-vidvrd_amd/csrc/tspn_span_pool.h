@@ -1,0 +1,41 @@
+// Span pooling, the per-(row, predicate) expression: shared by span_combine_kernel (tspn_linear.hip) and
+// span_row_topk_kernel (relations/tspn_span_relations.hip), which must return the same fp32 bits.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+namespace tspn {
+
+// Sum of G over the frames [a, e) of one (tracklet, column) in float64, in frame order: what PS[e] - PS[a] is when
+// both are finite.  span_logit takes it when the running sum of span_prefix_kernel has met a NaN / Inf in an
+// EARLIER or inner frame: every later prefix value is non-finite then, although the span's own frames may all be finite.
+__device__ inline double span_sum_frames(const float* __restrict__ g, int64_t K2, int64_t a, int64_t e) {
+  double acc = 0.0;
+  for (int64_t t = a; t < e; ++t) acc += (double)g[t * K2];
+  return acc;
+}
+
+// sigmoid(mean over the frames of span (a0, e0) of G[s, :, 2k] + G[o, :, 2k+1], + b[k]) of global tracklets (s, o):
+// PS [NT, T+1, 2K] float64 prefix sums of G [NT, T, 2K] over time.
+__device__ inline float span_logit(const double* __restrict__ PS, const float* __restrict__ G, int64_t s, int64_t o,
+                                   int64_t a0, int64_t e0, int T, int64_t K2, int64_t k,
+                                   const float* __restrict__ b) {
+  int64_t a = a0, e = e0;
+  a = a < 0 ? 0 : (a > T - 1 ? T - 1 : a);       // out-of-range / unused (-1) spans fall back to
+  e = e < a + 1 ? (a0 < 0 ? T : a + 1) : (e > T ? T : e);  // the whole segment / one frame
+  const double* ps = PS + (s * (T + 1)) * K2 + 2 * k;
+  const double* po = PS + (o * (T + 1)) * K2 + 2 * k + 1;
+  // a prefix value is non-finite from the first NaN / Inf frame on (PS[a] non-finite implies PS[e] non-finite), so
+  // PS[e] alone tells whether the difference is usable; finite prefixes keep the difference and its bits
+  double ds = ps[e * K2] - ps[a * K2];
+  double dob = po[e * K2] - po[a * K2];
+  if (!isfinite(ps[e * K2])) ds = span_sum_frames(G + (s * T) * K2 + 2 * k, K2, a, e);
+  if (!isfinite(po[e * K2])) dob = span_sum_frames(G + (o * T) * K2 + 2 * k + 1, K2, a, e);
+  double v = (ds + dob) / (double)(e - a);
+  if (b != nullptr) v += (double)b[k];
+  return (float)(1.0 / (1.0 + exp(-v)));
+}
+
+}  // namespace tspn

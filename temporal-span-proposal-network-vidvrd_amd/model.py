@@ -1430,6 +1430,61 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                 out.append(ops.span_predicate(_f32(f, dev), p.contiguous(), sp.contiguous(), cw, cb).to(f.device))
         return out
 
+    def decode_span_relations(self, pair_list, duration_proposals, spans_per_pair=4, topk_per_span=20, topk_per_seg=200,
+                              num_obj=35, sizes=None, nms_threshold=0.5):
+        """Relations WITH their temporal spans from `forward`'s duration_proposals (build-defined): per
+        pair the `spans_per_pair` best span proposals (`decode_spans`), per span the `topk_per_span` best predicates of
+        the predicate head pooled over that span, scored predicate sigmoid x span relationness, and per segment the
+        `topk_per_seg` best of those.  Per segment returns (scores [M], triplets int64 [M,3] = (subject class,
+        predicate, object class), pair_tids int64 [M,2], spans int64 [M,2] frames [start, end) inside the segment), in
+        descending score order, on the device of the segment's 'tracklet_feats'.  Needs the tracklet fields
+        ('tracklet_feats' [N,T,D], 'track_cls_logits' [N,num_obj]); honours 'tracklet_pairs'.  Segments with fewer than
+        2 tracklets or no pair yield empty results.  Equal-shape segments share one launch; everything runs on the
+        caller's stream."""
+        cls = self.classifier.rel_predictor
+        out = [None] * len(pair_list)
+        groups = {}
+        with torch.no_grad():
+            for i, (plist, dp) in enumerate(zip(pair_list, duration_proposals)):
+                if not self._is_tracklet_sample(plist):
+                    raise ValueError(f"decode_span_relations: segment {i} has no 'tracklet_feats': spans need temporal features")
+                f = plist.get_field("tracklet_feats")
+                n = int(f.shape[0])
+                heads = dp.heads
+                if n <= 1 or heads.shape[0] == 0:
+                    tgt = f.device
+                    out[i] = (torch.empty(0, device=tgt), torch.empty((0, 3), dtype=torch.int64, device=tgt),
+                              torch.empty((0, 2), dtype=torch.int64, device=tgt), torch.empty((0, 2), dtype=torch.int64, device=tgt))
+                    continue
+                c = plist.get_field("track_cls_logits")
+                if tuple(c.shape) != (n, num_obj):
+                    raise ValueError(f"decode_span_relations: segment {i}: 'track_cls_logits' must be [{n},{num_obj}], got {tuple(c.shape)}")
+                groups.setdefault((tuple(f.shape), tuple(heads.shape)), []).append(i)
+            for (fshape, hshape), members in groups.items():
+                n, nm = fshape[0], len(members)
+                dev = _compute_device(*[pair_list[i].get_field("tracklet_feats") for i in members], cls.weight)
+                cw, cb = self.classifier._cache.get("cls", (cls.weight, cls.bias), dev, lambda ts: ts)
+                pairs = []
+                for i in members:
+                    p = _segment_pairs(pair_list[i], n, dev)
+                    if p.shape[0] != hshape[0]:
+                        raise ValueError(f"decode_span_relations: segment {i}: {p.shape[0]} pairs but duration_proposals "
+                                         f"has {hshape[0]} rows")
+                    pairs.append(p)
+                pairs = torch.stack(pairs).contiguous()
+                heads = _batch_rows([duration_proposals[i].heads for i in members], dev)
+                sz = sizes if sizes is not None else self.anchor_sizes(hshape[2])
+                sp = ops.decode_spans(heads, sz, top_k=spans_per_pair, nms_threshold=nms_threshold)
+                feats = _batch_rows([pair_list[i].get_field("tracklet_feats") for i in members], dev)
+                clog = _batch_rows([pair_list[i].get_field("track_cls_logits") for i in members], dev).view(nm, n, num_obj)
+                res = ops.decode_span_relations(feats, pairs, sp["span"], sp["score"], sp["count"], cw, cb, clog,
+                                                topk_per_span=topk_per_span, topk_per_seg=topk_per_seg, check_pairs=False)
+                valid = res[5].tolist()
+                for k, i in enumerate(members):
+                    tgt = pair_list[i].get_field("tracklet_feats").device
+                    out[i] = tuple(r[k, :valid[k]].to(tgt) for r in res[:4])
+        return out
+
     def pair_geometry(self, pair_list):
         """Relative box geometry [P,8,T] per segment from 'tracklet_boxes' (pair builder side output)."""
         out = []

@@ -15,7 +15,7 @@ from . import _abi
 __all__ = [
     "predicate_head", "feature_preprocess_", "ppn_pair_matrix_topk", "traj_iou", "traj_iou_tail", "pair_index",
     "pair_gather", "pack_conv3", "conv3", "conv3_tc", "pack_conv3_wino63", "conv3_tc_wino63", "pack_conv3_wino63_f16x3", "conv3_tc_wino63_f16x3", "heads", "heads_pairgrid", "temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
-    "forward_fused", "temporal_encoder_heads", "fused_workspace_bytes", "fused_bf16_workspace_bytes", "decode_topk", "decode_spans",
+    "forward_fused", "temporal_encoder_heads", "fused_workspace_bytes", "fused_bf16_workspace_bytes", "decode_topk", "decode_spans", "decode_span_relations",
     "cast_bf16", "pack_conv3_bf16", "pack_heads_bf16", "conv3_tc_bf16", "heads_pairgrid_bf16",
     "transpose_cast_bf16", "temporal_encoder_heads_bf16",
     "temporal_mean_bf16", "forward_fused_bf16", "span_predicate", "bottleneck_block_bf16", "bottleneck_block_proj_bf16", "bottleneck_block_res_bf16",
@@ -994,6 +994,68 @@ def span_predicate(feats, pairs, spans, cls_w, cls_b):
     _abi.check(l.tspn_span_predicate_f32(_p(feats), NT, T, D, _p(pairs), _p(spans), P, _p(cls_w), _p(cls_b), K,
                                          _p(out), _p(ws), ws.numel(), _stream()))
     return out
+
+
+def decode_span_relations(feats, pairs, spans, span_scores, span_counts, cls_w, cls_b, cls_logits, topk_per_span=20,
+                          topk_per_seg=200, check_pairs=True, out=None):
+    """Relations with their temporal spans for S equal-shape segments (tspn_decode_span_relations_f32).
+
+    feats [S,N,T,D] (or [S*N,T,D]); pairs int64 [S,P,2] segment-local tracklet ids; spans int64 [S*P,J,2],
+    span_scores [S*P,J], span_counts int64 [S*P]: `decode_spans(top_k=J)` of the S*P pairs (leading dims [S,P] are taken
+    too); cls_w [K,2D], cls_b [K] or None; cls_logits [S,N,num_obj].  A candidate (pair, span j < count, predicate k)
+    scores span_predicate(pair, span)[k] * span_score: per span the `topk_per_span` best k, per segment the
+    `topk_per_seg` best candidates.
+    Returns (scores [S,Mc], triplets int64 [S,Mc,3], pair_tids int64 [S,Mc,2], spans int64 [S,Mc,2], span_rank int64
+    [S,Mc], valid int64 [S]) with Mc = min(topk_per_seg, P*J*min(topk_per_span, K)); segment s has valid[s] <= Mc real
+    rows, the rest are not written.  `out`: those six tensors, preallocated."""
+    _dev(feats, "feats"); _dev(pairs, "pairs", torch.int64); _dev(spans, "spans", torch.int64)
+    _dev(span_scores, "span_scores"); _dev(span_counts, "span_counts", torch.int64)
+    _dev(cls_w, "cls_w"); _dev(cls_logits, "cls_logits")
+    if cls_b is not None:
+        _dev(cls_b, "cls_b")
+    if pairs.dim() != 3 or pairs.shape[2] != 2 or cls_logits.dim() != 3 or cls_logits.shape[0] != pairs.shape[0]:
+        raise ValueError("decode_span_relations: pairs must be [S,P,2] and cls_logits [S,N,num_obj]")
+    S, P, _ = pairs.shape
+    N, NO = cls_logits.shape[1], cls_logits.shape[2]
+    if feats.dim() == 4:
+        feats = feats.view(-1, feats.shape[2], feats.shape[3])
+    if feats.dim() != 3 or feats.shape[0] != S * N:
+        raise ValueError(f"decode_span_relations: feats must hold S*N = {S * N} tracklets [S*N,T,D], got {tuple(feats.shape)}")
+    T, D = feats.shape[1], feats.shape[2]
+    K = cls_w.shape[0]
+    if spans.dim() < 3 or spans.shape[-1] != 2:
+        raise ValueError("decode_span_relations: spans must be [S*P,J,2]")
+    J = spans.shape[-2]
+    if spans.numel() != S * P * J * 2 or span_scores.numel() != S * P * J or span_counts.numel() != S * P \
+            or (span_scores.numel() and span_scores.shape[-1] != J):
+        raise ValueError(f"decode_span_relations: spans [S*P,J,2], span_scores [S*P,J] and span_counts [S*P] expected for "
+                         f"S*P = {S * P}, J = {J}")
+    if tuple(cls_w.shape) != (K, 2 * D) or (cls_b is not None and tuple(cls_b.shape) != (K,)):
+        raise ValueError("decode_span_relations: cls_w must be [K,2D] and cls_b [K]")
+    if check_pairs and S * P and (int(pairs.min()) < 0 or int(pairs.max()) >= N):
+        raise IndexError("decode_span_relations: tracklet id outside the segment")
+    R = min(int(topk_per_span), K)
+    Mc = min(int(topk_per_seg), P * J * R)
+    dev = feats.device
+    shapes = (((S, Mc), torch.float32), ((S, Mc, 3), torch.int64), ((S, Mc, 2), torch.int64), ((S, Mc, 2), torch.int64),
+              ((S, Mc), torch.int64), ((S,), torch.int64))
+    if out is None:
+        out = tuple(torch.empty(sh, dtype=dt, device=dev) for sh, dt in shapes)
+        if S * P == 0:
+            out[5].zero_()                       # nothing is launched
+    else:
+        if len(out) != 6:
+            raise ValueError("decode_span_relations: out must be the six result tensors")
+        for t, (sh, dt), name in zip(out, shapes, ("scores", "triplets", "pair_tids", "spans", "span_rank", "valid")):
+            if tuple(_dev(t, "out." + name, dt).shape) != sh:
+                raise ValueError(f"decode_span_relations: out.{name} must be {sh}")
+    l = _abi.lib()
+    ws = _ws(l.tspn_decode_span_relations_workspace_bytes(S, N, T, D, P, J, K, int(topk_per_span)), dev)
+    _abi.check(l.tspn_decode_span_relations_f32(_p(feats), S, N, T, D, _p(pairs), P, _p(spans), _p(span_scores),
+                                                _p(span_counts), J, _p(cls_w), _p(cls_b), K, _p(cls_logits), NO,
+                                                int(topk_per_span), int(topk_per_seg), *[_p(t) for t in out],
+                                                _p(ws), ws.numel(), _stream()))
+    return tuple(out)
 
 
 # --------------------------------------------------------------------------- #
