@@ -168,7 +168,12 @@ int tspn_gather_rows_f32(const float* src, int64_t ld, int64_t F, const int64_t*
  *            ties broken lower-index-first                   [B,topk] int64
  * MLP = Linear(Cin,H)+ReLU+Linear(H,Cout); weights as in the state_dict
  * (sub_emb.0.weight [H,Cin], sub_emb.2.weight [Cout,H], ...).
- * Limits: N <= 128, Cin,H,Cout <= 256, topk <= N*N.                         */
+ * Limits: N <= 128, Cin,H,Cout <= 256, topk <= N*N, and one workgroup's LDS:
+ * 4*N*(Cin+H+2*Cout) + 8*n2p bytes <= 160 KiB, n2p = N*N rounded up to a power
+ * of two.  At the model's widths (Cin 35, H 64, Cout 35) that is N <= 90
+ * (126 376 B); N = 91 ... 128 (n2p = 16 384) need 192 588 B and more and are
+ * refused with TSPN_EUNSUPPORTED.  N = 128 fits only with narrow embeddings,
+ * e.g. H = Cout = 8 (161 280 B).                                            */
 int tspn_ppn_pair_matrix_topk_f32(const float* cls, int64_t B, int64_t N, int64_t Cin,
                                   int64_t H, int64_t Cout,
                                   const float* ws1, const float* bs1,
@@ -182,7 +187,9 @@ int tspn_ppn_pair_matrix_topk_f32(const float* cls, int64_t B, int64_t N, int64_
  * Replaces cubic_iou/_intersect/_union (lib/modeling/trajectory.py:85-141):
  *   out[B,N1,N2] float32, boxes [B,N,T,4] (l,t,r,b), +1 pixel-inclusive,
  *   intersection accumulated over t in fp32 in frame order.
- * boxes2 == NULL means boxes2 = boxes1 (N2 = N1).                            */
+ * boxes2 == NULL means boxes2 = boxes1 (N2 = N1), whatever N2 says: a caller
+ * with an empty second operand (N2 = 0) has nothing to compute and must not
+ * call with its null data pointer.                                          */
 int tspn_traj_iou_f32(const float* boxes1, int64_t N1, const float* boxes2, int64_t N2,
                       int64_t B, int64_t T, float* out, void* stream);
 

@@ -258,6 +258,10 @@ def ppn_pair_matrix_topk(cls_logits, w, topk):
 
     cls_logits [B,N,Cin] or [N,Cin]; `w` = dict with keys sub_emb.0.weight ... obj_emb.2.bias.
     Returns (pair_matrix [B,N,N], idx int64 [B,min(topk,N*N)]) (batch dim dropped for 2-D input).
+
+    Capacity: one workgroup holds a segment in LDS, 4*N*(Cin+H+2*Cout) + 8*n2p bytes (n2p = N*N rounded up to a power
+    of two) against 160 KiB.  At the model's widths (35, 64, 35) the largest N is 90; N = 91 ... 128 raise
+    TSPN_EUNSUPPORTED (the message names LDS).  N = 128 runs only with narrow embeddings, e.g. H = Cout = 8.
     """
     squeeze = cls_logits.dim() == 2
     c = cls_logits.unsqueeze(0) if squeeze else cls_logits
@@ -294,6 +298,8 @@ def traj_iou(boxes1, boxes2=None):
             raise ValueError("traj_iou: boxes2 shape mismatch")
         N2 = b2.shape[1]
     out = torch.empty((B, N1, N2), dtype=torch.float32, device=b1.device)
+    if out.numel() == 0:      # an empty boxes2 has a null data pointer, which the C entry reads as "self-IoU"
+        return out[0] if squeeze else out
     _abi.check(_abi.lib().tspn_traj_iou_f32(_p(b1), N1, _p(b2), N2, B, T, _p(out), _stream()))
     return out[0] if squeeze else out
 
