@@ -9,9 +9,9 @@
 // (its RelNMS is a stub and predict.py never reads the duration proposals).
 //
 //   stage a  G = f W'^T and its float64 prefix sums over time (tspn::span_prefix_stage, shared with span pooling)
-//   kernel b one wave per (pair, span) row: the K <= 256 values q formed in registers from the prefix differences,
-//            R rounds of wave arg-max; writes R x (key of the product, product, k).  A row j >= count[p] writes key 0,
-//            below every real key: [rows, K] never reaches HBM
+//   kernel b one wave per (pair, span) row: the K <= 256 values q formed in registers from the prefix differences, then
+//            tspn::wave_row_topk (tspn_topk_select.h); writes R x (key of the product, product, k).  A row
+//            j >= count[p] writes tspn::kPadKey, below every real key: [rows, K] never reaches HBM
 //   kernel c one workgroup per segment: tspn::select_topk_sorted over the P*J*R keys, then the gathers (pair ids,
 //            predicate, class argmax, span, span rank)
 #include <algorithm>
@@ -22,10 +22,8 @@
 
 namespace {
 
-constexpr int VPT = 4;        // values per lane in kernel b -> K <= 256
 constexpr int MAX_J = 16;
 
-using tspn::key_before;
 using tspn::order_key;
 
 __global__ __launch_bounds__(256) void span_row_topk_kernel(
@@ -40,7 +38,7 @@ __global__ __launch_bounds__(256) void span_row_topk_kernel(
   const int j = (int)(row - pr * J);
   if ((int64_t)j >= span_counts[pr]) {         // not a proposal: nothing the segment stage can select
     for (int r = lane; r < R; r += 64) {
-      key[row * R + r] = 0u;
+      key[row * R + r] = tspn::kPadKey;
       sc[row * R + r] = 0.f;
       ix[row * R + r] = -1;
     }
@@ -51,48 +49,18 @@ __global__ __launch_bounds__(256) void span_row_topk_kernel(
   const int64_t a0 = spans[2 * row], e0 = spans[2 * row + 1];
   const float w = span_scores[row];
   const int64_t K2 = 2 * (int64_t)K;
-  float v[VPT];
-  unsigned kv[VPT];
+  float v[tspn::kRowTopkVPT];
 #pragma unroll
-  for (int i = 0; i < VPT; ++i) {
+  for (int i = 0; i < tspn::kRowTopkVPT; ++i) {
     const int k = lane + 64 * i;
     v[i] = k < K ? tspn::span_logit(PS, G, s, o, a0, e0, T, K2, k, b) : 0.f;
-    kv[i] = order_key(v[i]);
   }
-  unsigned used = 0;
-  // R <= K and every real value has a key > 0: each round selects an unused k < K
-  for (int r = 0; r < R; ++r) {
-    unsigned bk = 0;
-    int bi = 0x7fffffff;
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-      const int k = lane + 64 * i;
-      if (k < K && !((used >> i) & 1u) && key_before(kv[i], k, bk, bi)) {
-        bk = kv[i];
-        bi = k;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned ok = __shfl_xor(bk, off);
-      const int oi = __shfl_xor(bi, off);
-      if (key_before(ok, oi, bk, bi)) {
-        bk = ok;
-        bi = oi;
-      }
-    }
-    if ((bi & 63) == lane && bi < K) {           // the owner of the winner writes the candidate
-      float bv = v[0];
-#pragma unroll
-      for (int i = 1; i < VPT; ++i)
-        if ((bi >> 6) == i) bv = v[i];
-      used |= 1u << (bi >> 6);
-      const float prod = bv * w;                 // one rounding (-ffp-contract=off)
-      key[row * R + r] = order_key(prod);
-      sc[row * R + r] = prod;
-      ix[row * R + r] = bi;
-    }
-  }
+  tspn::wave_row_topk(v, K, R, lane, [=](int r, float value, int k) {
+    const float prod = value * w;                // one rounding (-ffp-contract=off)
+    key[row * R + r] = order_key(prod);
+    sc[row * R + r] = prod;
+    ix[row * R + r] = k;
+  });
 }
 
 __global__ __launch_bounds__(tspn::kSelectThreads) void segment_span_topk_kernel(
@@ -173,7 +141,7 @@ extern "C" int tspn_decode_span_relations_f32(const float* feats, int64_t S, int
                TSPN_EINVAL, "%s: bad sizes S=%lld N=%lld T=%lld D=%lld P=%lld J=%lld K=%lld NO=%lld", who,
                (long long)S, (long long)N, (long long)T, (long long)D, (long long)P, (long long)J, (long long)K,
                (long long)NO);
-  TSPN_REQUIRE(K <= 64 * VPT, TSPN_EUNSUPPORTED, "%s: K=%lld > %d", who, (long long)K, 64 * VPT);
+  TSPN_REQUIRE(K <= tspn::kRowTopkMaxK, TSPN_EUNSUPPORTED, "%s: K=%lld > %d", who, (long long)K, tspn::kRowTopkMaxK);
   TSPN_REQUIRE(topk_per_seg <= tspn::kSelectMaxM, TSPN_EUNSUPPORTED, "%s: topk_per_seg=%lld > %d", who,
                (long long)topk_per_seg, tspn::kSelectMaxM);
   TSPN_REQUIRE(J <= MAX_J, TSPN_EUNSUPPORTED, "%s: spans_per_pair J=%lld > %d", who, (long long)J, MAX_J);

@@ -35,6 +35,12 @@ inline int check_launch(const char* what) {
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// the smallest power of two >= n (1 for n <= 1)
+__host__ __device__ inline int64_t next_pow2(int64_t n) {
+  int64_t p = 1;
+  while (p < n) p <<= 1;
+  return p;
+}
 
 // ---- non-finite contract
 // ReLU as torch's F.relu: NaN in -> NaN out (fmaxf(v, 0) would return 0).  One v_maximum3_f32 on gfx950.
@@ -51,6 +57,16 @@ __device__ __forceinline__ unsigned order_key(float v) {
 // (key, index) order of a stable descending sort: larger key first, lower index first on ties
 __device__ __forceinline__ bool key_before(unsigned ka, int ia, unsigned kb, int ib) {
   return ka > kb || (ka == kb && ia < ib);
+}
+
+// the largest v over the wave, in every lane
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long other = __shfl_xor(v, o, 64);
+    v = other > v ? other : v;
+  }
+  return v;
 }
 
 // hipFuncAttributeMaxDynamicSharedMemorySize is a PER-DEVICE attribute of a kernel.  One static

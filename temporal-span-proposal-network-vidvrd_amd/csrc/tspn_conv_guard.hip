@@ -53,12 +53,7 @@ __global__ __launch_bounds__(THREADS) void conv3_spot_check_kernel(
   unsigned long long hotkey = 0;
   {
     const unsigned long long* slots = scratch + TSPN_CONV_CHECK_HOT_OFFSET / 8;
-    unsigned long long k = lane < TSPN_CONV_CHECK_HOT_SLOTS ? slots[32 * lane] : 0ull;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned long long other = __shfl_xor(k, o, 64);
-      k = other > k ? other : k;
-    }
+    const unsigned long long k = tspn::wave_max_u64(lane < TSPN_CONV_CHECK_HOT_SLOTS ? slots[32 * lane] : 0ull);
     hotkey = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(k >> 32)) << 32) |
              (unsigned)__builtin_amdgcn_readfirstlane((int)k);
   }

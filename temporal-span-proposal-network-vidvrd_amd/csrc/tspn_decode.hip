@@ -16,10 +16,9 @@
 // compares run on tspn::order_key, so every emitted index is in range whatever the scores hold.
 // Integer / compare work only: bit-exact against the oracle.
 //
-//   kernel 1  one wave per pair: R rounds of wave arg-max over the K scores held in registers
-//   kernel 2  one workgroup per segment: exact radix-select of the M-th largest candidate
-//             (4 x 8-bit histograms over order-preserving keys), index-select among ties,
-//             compaction into LDS, bitonic sort of the <= 1024 winners, label gathers.
+//   kernel 1  one wave per pair: tspn::wave_row_topk over the K scores held in registers
+//   kernel 2  one workgroup per segment: tspn::select_topk_sorted over the P*R candidates, label gathers
+// (both bodies: tspn_topk_select.h)
 #include <algorithm>
 #include <cmath>
 
@@ -28,12 +27,10 @@
 
 namespace {
 
-constexpr int VPT = 4;        // values per lane in kernel 1 -> K <= 256
 constexpr int SEG_THREADS = tspn::kSelectThreads;
 constexpr int MAX_M = tspn::kSelectMaxM;
 
 using tspn::argmax_first;
-using tspn::key_before;
 using tspn::order_key;
 
 __global__ __launch_bounds__(256) void pair_topk_kernel(const float* __restrict__ logits,
@@ -44,46 +41,16 @@ __global__ __launch_bounds__(256) void pair_topk_kernel(const float* __restrict_
   const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= rows) return;
   const float* src = logits + row * K;
-  float v[VPT];
-  unsigned kv[VPT];
+  float v[tspn::kRowTopkVPT];
 #pragma unroll
-  for (int i = 0; i < VPT; ++i) {
+  for (int i = 0; i < tspn::kRowTopkVPT; ++i) {
     const int k = lane + 64 * i;
     v[i] = k < K ? src[k] : 0.f;
-    kv[i] = order_key(v[i]);
   }
-  unsigned used = 0;
-  // R <= K and every real score has a key > 0: each round selects an unused k < K
-  for (int r = 0; r < R; ++r) {
-    unsigned bk = 0;
-    int bi = 0x7fffffff;
-#pragma unroll
-    for (int i = 0; i < VPT; ++i) {
-      const int k = lane + 64 * i;
-      if (k < K && !((used >> i) & 1u) && key_before(kv[i], k, bk, bi)) {
-        bk = kv[i];
-        bi = k;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      const unsigned ok = __shfl_xor(bk, off);
-      const int oi = __shfl_xor(bi, off);
-      if (key_before(ok, oi, bk, bi)) {
-        bk = ok;
-        bi = oi;
-      }
-    }
-    if ((bi & 63) == lane && bi < K) {           // the owner of the winner writes its value (NaN payloads kept)
-      float bv = v[0];
-#pragma unroll
-      for (int i = 1; i < VPT; ++i)
-        if ((bi >> 6) == i) bv = v[i];
-      used |= 1u << (bi >> 6);
-      sc[row * R + r] = bv;
-      ix[row * R + r] = bi;
-    }
-  }
+  tspn::wave_row_topk(v, K, R, lane, [=](int r, float value, int k) {
+    sc[row * R + r] = value;
+    ix[row * R + r] = k;
+  });
 }
 
 __global__ __launch_bounds__(SEG_THREADS) void segment_topk_kernel(
@@ -131,8 +98,8 @@ extern "C" int tspn_decode_topk_f32(const float* rel_logit, const int64_t* pairs
   TSPN_REQUIRE(S >= 0 && P >= 0 && K > 0 && NO > 0 && topk_pair > 0 && topk_seg > 0 && ld >= NO &&
                    seg_rows > 0 && row_mul >= 0,
                TSPN_EINVAL, "tspn_decode_topk_f32: bad sizes");
-  TSPN_REQUIRE(K <= 64 * VPT, TSPN_EUNSUPPORTED, "tspn_decode_topk_f32: K=%lld > %d", (long long)K,
-               64 * VPT);
+  TSPN_REQUIRE(K <= tspn::kRowTopkMaxK, TSPN_EUNSUPPORTED, "tspn_decode_topk_f32: K=%lld > %d", (long long)K,
+               tspn::kRowTopkMaxK);
   const int64_t R = std::min<int64_t>(topk_pair, K);
   const int64_t M = std::min<int64_t>(topk_seg, P * R);
   TSPN_REQUIRE(M <= MAX_M, TSPN_EUNSUPPORTED, "tspn_decode_topk_f32: topk_seg=%lld > %d",

@@ -6,16 +6,16 @@
 // `torch.sort(pair_matrix.view(-1), descending=True)[:num_pair_proposals]` of
 // PPN._forward_test (ppn.py:84-85).  In the reference this is ~10 launch-bound
 // torch ops per segment; here the whole thing runs in one workgroup per segment
-// with every intermediate in LDS.  The sort is a bitonic network over
-// (value, flat index) with the total order "larger value first, lower index
-// first on ties" (= a stable descending sort; the reference's unstable sort
-// leaves tie order unspecified — SURVEY.md §7 hard part 3).  The keys are tspn::order_key, torch's order: a NaN
+// with every intermediate in LDS.  The sort is tspn::bitonic_sort_desc (tspn_topk_select.h) over (order key, flat
+// index): larger value first, lower index first on ties (= a stable descending sort; the reference's unstable sort
+// leaves tie order unspecified -- SURVEY.md §7 hard part 3).  The keys are tspn::order_key, torch's order: a NaN
 // entry (a tracklet with NaN class logits) ranks above +Inf and leaves the order of the finite ones intact.
 // Indices are into the N x N matrix including the diagonal (s*N + o).
 #include <algorithm>
 #include <cmath>
 
 #include "tspn_common.h"
+#include "tspn_topk_select.h"
 
 namespace {
 
@@ -75,32 +75,13 @@ __global__ __launch_bounds__(PPN_THREADS) void ppn_kernel(
       s_key[i] = tspn::order_key(v);
       s_idx[i] = i;
     } else {
-      s_key[i] = 0u;                                  // below every real key
-      s_idx[i] = 0x7fffffff;
+      s_key[i] = tspn::kPadKey;
+      s_idx[i] = tspn::kPadIdx;
     }
   }
   __syncthreads();
 
-  for (int k = 2; k <= n2p; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < n2p; i += PPN_THREADS) {
-        const int l = i ^ j;
-        if (l > i) {
-          const unsigned ki = s_key[i], kl = s_key[l];
-          const int ii = s_idx[i], il = s_idx[l];
-          const bool fwd = (i & k) == 0;
-          const bool swap = fwd ? tspn::key_before(kl, il, ki, ii) : tspn::key_before(ki, ii, kl, il);
-          if (swap) {
-            s_key[i] = kl;
-            s_key[l] = ki;
-            s_idx[i] = il;
-            s_idx[l] = ii;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  tspn::bitonic_sort_desc<PPN_THREADS>(s_key, s_idx, n2p);
   for (int i = tid; i < topk; i += PPN_THREADS) out_idx[b * topk + i] = (int64_t)s_idx[i];
 }
 
@@ -125,8 +106,7 @@ extern "C" int tspn_ppn_pair_matrix_topk_f32(const float* cls, int64_t B, int64_
                "tspn_ppn_pair_matrix_topk_f32: N=%lld Cin=%lld H=%lld Cout=%lld over limits "
                "(N<=128, channels<=256)",
                (long long)N, (long long)Cin, (long long)H, (long long)Cout);
-  int n2p = 1;
-  while (n2p < N * N) n2p <<= 1;
+  const int n2p = (int)tspn::next_pow2(N * N);
   const size_t smem = sizeof(float) * (size_t)(N * Cin + N * H + 2 * N * Cout) +
                       (sizeof(float) + sizeof(int)) * (size_t)n2p;
   TSPN_REQUIRE(smem <= 160 * 1024, TSPN_EUNSUPPORTED,

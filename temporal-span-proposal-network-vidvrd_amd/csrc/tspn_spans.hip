@@ -14,13 +14,15 @@
 // The float64 arithmetic makes the result reproducible to the bit on any IEEE machine, so the
 // span indices are checked bit-exactly against the CPU oracle.
 //
-// One workgroup per pair: bitonic sort of the A*T (logit, c) keys in LDS, span decode of the
-// leaders, an m x m/64 suppression bit matrix built by all threads, then one wave walks the
-// sorted list (lane w owns word w of the `removed` set; one shuffle + one LDS read per step).
+// One workgroup per pair: the A*T (logit, c) keys sorted in LDS by tspn::bitonic_sort_desc
+// (tspn_topk_select.h), span decode of the leaders, an m x m/64 suppression bit matrix built by all
+// threads, then one wave walks the sorted list (lane w owns word w of the `removed` set; one shuffle +
+// one LDS read per step).
 #include <algorithm>
 #include <cmath>
 
 #include "tspn_common.h"
+#include "tspn_topk_select.h"
 
 namespace {
 
@@ -57,43 +59,24 @@ __global__ __launch_bounds__(SP_THREADS) void decode_spans_kernel(
   const float* rel = heads + p * 3 * A * (int64_t)T;  // rows [0,A) relationness, [A,3A) duration
   const float* dur = rel + (int64_t)A * T;
 
-  // sort key: tspn::order_key of the logit for a proposal, 0 (below every real key) for a candidate with a NaN logit,
-  // d_c or d_w and for the padding; the valid ones lead the sorted list in the oracle's order
+  // sort key: tspn::order_key of the logit for a proposal, tspn::kPadKey for a candidate with a NaN logit, d_c or d_w and
+  // for the padding; the valid ones lead the sorted list in the oracle's order
   if (tid == 0) s_m = 0;
   for (int c = tid; c < n2; c += SP_THREADS) {
-    unsigned key = 0u;
+    unsigned key = tspn::kPadKey;
     if (c < n) {
       const int t = c / A, a = c - t * A;
       const float lg = rel[a * T + t], dc = dur[(2 * a) * T + t], dw = dur[(2 * a + 1) * T + t];
-      key = (lg == lg && dc == dc && dw == dw) ? tspn::order_key(lg) : 0u;
+      key = (lg == lg && dc == dc && dw == dw) ? tspn::order_key(lg) : tspn::kPadKey;
     }
     s_key[c] = key;
-    s_idx[c] = c < n ? c : 0x7fffffff;
+    s_idx[c] = c < n ? c : tspn::kPadIdx;
   }
   __syncthreads();
-  for (int k = 2; k <= n2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < n2; i += SP_THREADS) {
-        const int l = i ^ j;
-        if (l > i) {
-          const unsigned ki = s_key[i], kl = s_key[l];
-          const int ii = s_idx[i], il = s_idx[l];
-          const bool fwd = (i & k) == 0;
-          const bool swap = fwd ? tspn::key_before(kl, il, ki, ii) : tspn::key_before(ki, ii, kl, il);
-          if (swap) {
-            s_key[i] = kl;
-            s_key[l] = ki;
-            s_idx[i] = il;
-            s_idx[l] = ii;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
-  // ---- the proposals among the m leaders: the first m_eff (the sorted keys fall to 0 where they end)
+  tspn::bitonic_sort_desc<SP_THREADS>(s_key, s_idx, n2);
+  // ---- the proposals among the m leaders: the first m_eff (the sorted keys fall to kPadKey where they end)
   for (int i = tid; i < m; i += SP_THREADS)
-    if (s_key[i] != 0u && (i + 1 == m || s_key[i + 1] == 0u)) s_m = i + 1;
+    if (s_key[i] != tspn::kPadKey && (i + 1 == m || s_key[i + 1] == tspn::kPadKey)) s_m = i + 1;
   __syncthreads();
   m = s_m;
   // ---- decode the m leaders (float64), compact
@@ -199,8 +182,7 @@ extern "C" int tspn_decode_spans_f32(const float* heads, int64_t P, int64_t A, i
   const int m = (int)std::min<int64_t>(std::min<int64_t>(pre_nms, SP_MAX_PRE), n);
   TSPN_REQUIRE(top_k <= SP_MAX_PRE, TSPN_EUNSUPPORTED, "tspn_decode_spans_f32: top_k=%lld > %d",
                (long long)top_k, SP_MAX_PRE);
-  int n2 = 1;
-  while (n2 < n) n2 <<= 1;
+  const int n2 = (int)tspn::next_pow2(n);
   const int mw = (m + 63) >> 6;
   const size_t compact = (size_t)SP_MAX_PRE * 16;
   const size_t uni = std::max<size_t>((size_t)n2 * 8, (size_t)m * mw * 8);

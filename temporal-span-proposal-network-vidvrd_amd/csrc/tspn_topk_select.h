@@ -1,9 +1,92 @@
-// Exact top-M of Q keyed candidates by one workgroup, in torch's stable descending order: shared by
-// segment_topk_kernel (tspn_decode.hip) and segment_span_topk_kernel (relations/tspn_span_relations.hip).
+// The one home of selection ("Top-k ties" and "Selection": larger tspn::order_key first, lower index on ties,
+// key 0 below every real key).  Users:
+//   bitonic_sort_desc    ppn_kernel (tspn_ppn.hip), decode_spans_kernel (tspn_spans.hip), select_topk_sorted below
+//   wave_row_topk        pair_topk_kernel (tspn_decode.hip), span_row_topk_kernel (relations/tspn_span_relations.hip)
+//   select_topk_sorted   segment_topk_kernel (tspn_decode.hip), segment_span_topk_kernel
+//                        (relations/tspn_span_relations.hip): exact top-M of Q keyed candidates by one workgroup, in
+//                        torch's stable descending order
+//   argmax_first         the class labels of both segment kernels
 #pragma once
 #include "tspn_common.h"
 
 namespace tspn {
+
+// Padding of a sort or of an arg-max seed: real keys are never 0 (tspn::order_key), so padding sorts last, and among
+// padding the index is irrelevant.
+constexpr unsigned kPadKey = 0u;
+constexpr int kPadIdx = 0x7fffffff;
+
+// Bitonic sort of n2 (a power of two) pairs (key[i], idx[i]) in LDS into key_before order.  All THREADS threads of the
+// workgroup call it, after a barrier that made the arrays visible; one barrier per (k, j) step (none when n2 == 1), and
+// on return, after the last of them, the arrays are sorted.
+template <int THREADS>
+__device__ __forceinline__ void bitonic_sort_desc(unsigned* key, int* idx, int n2) {
+  const int tid = threadIdx.x;
+  for (int k = 2; k <= n2; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      for (int i = tid; i < n2; i += THREADS) {
+        const int l = i ^ j;
+        if (l > i) {
+          const unsigned ki = key[i], kl = key[l];
+          const int ii = idx[i], il = idx[l];
+          const bool fwd = (i & k) == 0;
+          const bool swap = fwd ? key_before(kl, il, ki, ii) : key_before(ki, ii, kl, il);
+          if (swap) {
+            key[i] = kl;
+            key[l] = ki;
+            idx[i] = il;
+            idx[l] = ii;
+          }
+        }
+      }
+      __syncthreads();
+    }
+  }
+}
+
+constexpr int kRowTopkVPT = 4;                      // values a lane holds in registers
+constexpr int kRowTopkMaxK = 64 * kRowTopkVPT;
+
+// The R best of a row of K <= kRowTopkMaxK values by one wave, in key_before order.  Lane `lane` holds value
+// k = lane + 64 i in v[i] (anything where k >= K).  R rounds of a lane-local best over the unused slots followed by a
+// wave arg-max; R <= K and every real value has a key > 0, so each round selects an unused k < K.  emit(r, value, k)
+// runs on the lane that owns the winner of round r only, with the value as loaded (NaN payloads kept).
+template <class Emit>
+__device__ __forceinline__ void wave_row_topk(const float (&v)[kRowTopkVPT], int K, int R, int lane, Emit emit) {
+  unsigned kv[kRowTopkVPT];
+#pragma unroll
+  for (int i = 0; i < kRowTopkVPT; ++i) kv[i] = order_key(v[i]);
+  unsigned used = 0;
+  for (int r = 0; r < R; ++r) {
+    unsigned bk = kPadKey;
+    int bi = kPadIdx;
+#pragma unroll
+    for (int i = 0; i < kRowTopkVPT; ++i) {
+      const int k = lane + 64 * i;
+      if (k < K && !((used >> i) & 1u) && key_before(kv[i], k, bk, bi)) {
+        bk = kv[i];
+        bi = k;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+      const unsigned ok = __shfl_xor(bk, off);
+      const int oi = __shfl_xor(bi, off);
+      if (key_before(ok, oi, bk, bi)) {
+        bk = ok;
+        bi = oi;
+      }
+    }
+    if ((bi & 63) == lane && bi < K) {
+      float bv = v[0];
+#pragma unroll
+      for (int i = 1; i < kRowTopkVPT; ++i)
+        if ((bi >> 6) == i) bv = v[i];
+      used |= 1u << (bi >> 6);
+      emit(r, bv, bi);
+    }
+  }
+}
 
 constexpr int kSelectThreads = 1024;   // the workgroup size select_topk_sorted expects
 constexpr int kSelectMaxM = 1024;
@@ -99,34 +182,14 @@ __device__ __forceinline__ void select_topk_sorted(SelectLds& L, KeyFn key, int 
     }
   }
   __syncthreads();
-  int m2 = 1;
-  while (m2 < M) m2 <<= 1;
+  const int m2 = (int)next_pow2(M);
   for (int i = tid; i < m2; i += kSelectThreads)
     if (i >= M) {
-      L.kk[i] = 0u;                                  // below every real key
-      L.ki[i] = 0x7fffffff;
+      L.kk[i] = kPadKey;
+      L.ki[i] = kPadIdx;
     }
   __syncthreads();
-  for (int k = 2; k <= m2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < m2; i += kSelectThreads) {
-        const int l = i ^ j;
-        if (l > i) {
-          const unsigned vi = L.kk[i], vl = L.kk[l];
-          const int ii = L.ki[i], il = L.ki[l];
-          const bool fwd = (i & k) == 0;
-          const bool swap = fwd ? key_before(vl, il, vi, ii) : key_before(vi, ii, vl, il);
-          if (swap) {
-            L.kk[i] = vl;
-            L.kk[l] = vi;
-            L.ki[i] = il;
-            L.ki[l] = ii;
-          }
-        }
-      }
-      __syncthreads();
-    }
-  }
+  bitonic_sort_desc<kSelectThreads>(L.kk, L.ki, m2);
 }
 
 // torch.argmax over n values: the first NaN, else the first maximum

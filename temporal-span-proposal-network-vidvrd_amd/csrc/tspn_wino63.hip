@@ -153,11 +153,7 @@ __device__ __forceinline__ void wino63_absmax_own_frames(const f32x4 (&d)[8], fl
 }
 // the wave's largest key into slot `slot` of `hot`: one 64-bit atomic max per wave, no return value
 __device__ __forceinline__ void wino63_hot_publish(unsigned long long* __restrict__ hot, unsigned long long key, unsigned slot) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned long long other = __shfl_xor(key, o, 64);
-    key = other > key ? other : key;
-  }
+  key = tspn::wave_max_u64(key);
   if ((threadIdx.x & 63) == 0)
     __hip_atomic_fetch_max(hot + 32 * (slot & (TSPN_CONV_CHECK_HOT_SLOTS - 1)), key, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
