@@ -137,18 +137,9 @@ __global__ __launch_bounds__(G_THREADS, 1) void conv3_bf16_big_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   // workgroup -> tile: bijective XCD remap, then groups of 2 weight panels x all column tiles
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   constexpr int GM = 2;
-  const int group_sz = GM * tiles_n;
-  const int group = wg / group_sz;
-  const int first_m = group * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int in_group = wg - group * group_sz;
-  const int tile_m = first_m + in_group % gm;
-  const int tile_n = in_group / gm;
+  int tile_m, tile_n;
+  grouped_tile(xcd_remap(blockIdx.x, gridDim.x), GM, tiles_m, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * G_BM;
   const int64_t n0 = (int64_t)tile_n * G_BN;
 
@@ -389,10 +380,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void heads_pairgrid_bf16_
   static_assert(ROWS == 4 * NW, "each wave stages 4 rows");
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int ob = wg % nob;
   wg /= nob;
   const int sb = wg % nsb;
@@ -606,8 +594,6 @@ __global__ __launch_bounds__(256) void heads_dense_bf16_kernel(
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 }  // namespace
 
 extern "C" int tspn_cast_bf16(const float* src, int64_t n, uint16_t* dst, void* stream) {
@@ -652,7 +638,7 @@ extern "C" int tspn_temporal_mean_bf16(const uint16_t* x, int64_t R, int64_t T, 
                "tspn_temporal_mean_bf16: bad sizes R=%lld T=%lld D=%lld (D %% 8 == 0)", (long long)R,
                (long long)T, (long long)D);
   if (R == 0) return TSPN_OK;
-  TSPN_REQUIRE(x && out && aligned16(x), TSPN_EINVAL, "tspn_temporal_mean_bf16: null / unaligned pointer");
+  TSPN_REQUIRE(x && out && tspn::aligned16(x), TSPN_EINVAL, "tspn_temporal_mean_bf16: null / unaligned pointer");
   const int64_t items = R * (D / 8);
   hipLaunchKernelGGL(temporal_mean_bf16_kernel, dim3((unsigned)tspn::ceil_div(items, 64)), dim3(256), 0,
                      TSPN_STREAM(stream), reinterpret_cast<const __bf16*>(x), R, (int)T, (int)D, out);
@@ -670,7 +656,7 @@ extern "C" int tspn_conv3_tc_bf16(const uint16_t* x, int64_t B, int64_t T, int64
   TSPN_REQUIRE(Cin % R_KC == 0 && M % 4 == 0 && ldm % 4 == 0, TSPN_EUNSUPPORTED,
                "tspn_conv3_tc_bf16: needs Cin %% 16 == 0, M %% 4 == 0, ldm %% 4 == 0 (Cin=%lld M=%lld ldm=%lld)",
                (long long)Cin, (long long)M, (long long)ldm);
-  TSPN_REQUIRE(aligned16(x) && aligned16(packed) && aligned16(y) && (bias == nullptr || aligned16(bias)),
+  TSPN_REQUIRE(tspn::all_aligned16(x, packed, y) && (bias == nullptr || tspn::aligned16(bias)),
                TSPN_EUNSUPPORTED, "tspn_conv3_tc_bf16: pointers must be 16-byte aligned");
   TSPN_REQUIRE(Cin < (1 << 24) && T < (1 << 24) && M < (1 << 24) && ldm < (1 << 24) && 3 * Cin * M * 2 < (1LL << 31),
                TSPN_EUNSUPPORTED, "tspn_conv3_tc_bf16: dimension too large");
@@ -698,7 +684,7 @@ extern "C" int tspn_heads_pairgrid_bf16(const float* y, int64_t ldm, int64_t B, 
                (long long)B, (long long)N, (long long)C, (long long)T, (long long)H, (long long)ldm);
   if (B == 0 || N < 2) return TSPN_OK;
   TSPN_REQUIRE(y && head_packed && head_b && out, TSPN_EINVAL, "tspn_heads_pairgrid_bf16: null pointer");
-  TSPN_REQUIRE(C % HP_KC == 0 && ldm % 4 == 0 && aligned16(y) && aligned16(head_packed), TSPN_EUNSUPPORTED,
+  TSPN_REQUIRE(C % HP_KC == 0 && ldm % 4 == 0 && tspn::aligned16(y) && tspn::aligned16(head_packed), TSPN_EUNSUPPORTED,
                "tspn_heads_pairgrid_bf16: needs C %% 32 == 0, ldm %% 4 == 0, 16-byte aligned y / weights");
   const bool big = N > 12;
   const int64_t sblk = big ? 16 : 8;
@@ -749,7 +735,7 @@ extern "C" int tspn_heads_dense_bf16(const float* y, int64_t ldm, int64_t P, int
                (long long)T, (long long)H, (long long)ldm);
   if (P == 0) return TSPN_OK;
   TSPN_REQUIRE(y && head_packed && head_b && out, TSPN_EINVAL, "tspn_heads_dense_bf16: null pointer");
-  TSPN_REQUIRE(C % HP_KC == 0 && ldm % 4 == 0 && aligned16(y) && aligned16(head_packed), TSPN_EUNSUPPORTED,
+  TSPN_REQUIRE(C % HP_KC == 0 && ldm % 4 == 0 && tspn::aligned16(y) && tspn::aligned16(head_packed), TSPN_EUNSUPPORTED,
                "tspn_heads_dense_bf16: needs C %% 32 == 0, ldm %% 4 == 0, 16-byte aligned y / weights");
   const int64_t nfb = tspn::ceil_div(T, 16);
   const int64_t blocks = tspn::ceil_div(P * nfb, 4);

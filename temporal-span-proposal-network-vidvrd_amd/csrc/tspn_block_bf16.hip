@@ -72,9 +72,7 @@ __global__ __launch_bounds__(THREADS, 2) void bottleneck_block_bf16_kernel(
   extern __shared__ __attribute__((aligned(16))) char Bs[];   // h1 image, then (same memory) the h2 image
 
   // consecutive tiles stay on one XCD (shared halo rows in its L2)
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   if (wg >= ntiles) return;
   const int per_img = tiles_x * tiles_y;
   const int img = wg / per_img, tin = wg - img * per_img;
@@ -540,8 +538,7 @@ extern "C" int tspn_bottleneck_block_bf16(const uint16_t* x, int64_t NB, int64_t
   if (NB == 0) return TSPN_OK;
   TSPN_REQUIRE(x && frag1 && bias1 && frag2 && bias2 && frag3 && bias3 && out, TSPN_EINVAL, "%s: null pointer", what);
   TSPN_REQUIRE(x != out, TSPN_EINVAL, "%s: the block cannot run in place (tiles read their neighbours' pixels)", what);
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(x) && al16(frag1) && al16(bias1) && al16(frag2) && al16(bias2) && al16(frag3) && al16(bias3) && al16(out),
+  TSPN_REQUIRE(tspn::all_aligned16(x, frag1, bias1, frag2, bias2, frag3, bias3, out),
                TSPN_EUNSUPPORTED, "%s: operands must be 16-byte aligned", what);
   // 32-bit byte offsets inside one image
   TSPN_REQUIRE(H * W * 4 * CM * 2 < (1LL << 31), TSPN_EUNSUPPORTED, "%s: one image's map must stay below 2 GB", what);
@@ -565,9 +562,7 @@ extern "C" int tspn_bottleneck_block_proj_bf16(const uint16_t* x, int64_t NB, in
   if (NB == 0) return TSPN_OK;
   TSPN_REQUIRE(x && frag1 && bias1 && frag2 && bias2 && frag3 && bias3 && frags && biass && out, TSPN_EINVAL,
                "%s: null pointer", what);
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(x) && al16(frag1) && al16(bias1) && al16(frag2) && al16(bias2) && al16(frag3) && al16(bias3) &&
-                   al16(frags) && al16(biass) && al16(out),
+  TSPN_REQUIRE(tspn::all_aligned16(x, frag1, bias1, frag2, bias2, frag3, bias3, frags, biass, out),
                TSPN_EUNSUPPORTED, "%s: operands must be 16-byte aligned", what);
   const int64_t H = (Hin - 1) / stride + 1, W = (Win - 1) / stride + 1;
   TSPN_REQUIRE(H * W * 4 * CM * 2 < (1LL << 31) && Hin * Win * CIN * 2 < (1LL << 31), TSPN_EUNSUPPORTED,
@@ -587,9 +582,7 @@ extern "C" int tspn_bottleneck_block_res_bf16(const uint16_t* x, int64_t NB, int
   if (NB == 0) return TSPN_OK;
   TSPN_REQUIRE(x && frag1 && bias1 && frag2 && bias2 && frag3 && bias3 && residual && out, TSPN_EINVAL, "%s: null pointer", what);
   TSPN_REQUIRE(residual != out, TSPN_EINVAL, "%s: out must not alias the residual", what);
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(x) && al16(frag1) && al16(bias1) && al16(frag2) && al16(bias2) && al16(frag3) && al16(bias3) &&
-                   al16(residual) && al16(out),
+  TSPN_REQUIRE(tspn::all_aligned16(x, frag1, bias1, frag2, bias2, frag3, bias3, residual, out),
                TSPN_EUNSUPPORTED, "%s: operands must be 16-byte aligned", what);
   const int64_t H = (Hin - 1) / stride + 1, W = (Win - 1) / stride + 1;
   TSPN_REQUIRE(H * W * 4 * CM * 2 < (1LL << 31) && Hin * Win * CIN * 2 < (1LL << 31), TSPN_EUNSUPPORTED,

@@ -32,6 +32,7 @@
 #include <type_traits>
 
 #include "tspn_common.h"
+#include "tspn_conv3x3_ranges.h"
 #include "tspn_device.h"
 
 namespace {
@@ -39,10 +40,9 @@ namespace {
 using namespace tspn_dev;
 
 constexpr int THREADS = 256;
-constexpr int BN = 128;                 // pixels per workgroup
-constexpr int KC = 64;                  // channels per chunk
-constexpr int SLP = 132;                // padded pixel slots per channel group
-constexpr int B_ST = 8 * SLP * 16;      // bytes per x stage = per 64 channels of the h2 image
+// BN, KC, SLP, B_ST: tspn_conv3x3_ranges.h.  Two waves of 64 lanes stage the 128 pixels of a range, and SLP keeps the
+// fragment reads of phase 2 and phase 3 free of bank conflicts: the plan below depends on these values.
+static_assert(BN == 128 && KC == 64 && SLP == 132 && B_ST == 8 * SLP * 16, "tile plan of the tail");
 
 // NEXT (CM = 256, round 4): the kernel also computes conv1 of the FOLLOWING block on its own output tile,
 //     h1n = relu(W1n . out + b1n)        1x1, K = 4 CM = 1024 -> CM rows,
@@ -87,11 +87,7 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
   constexpr int SLPC = 68;                                  // 64 pixels + padding: conflict-free 16-byte reads like SLP
   constexpr int CHUNK_BYTES = (CM / 8) * SLPC * 16;         // CM channels of 64 pixels: CM / 8 groups x SLPC slots x 16 B
 
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;      // consecutive pixel tiles stay on one XCD (shared halo rows)
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int64_t n0 = (int64_t)wg * BN;
+  const int64_t n0 = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * BN;   // consecutive pixel tiles stay on one XCD (shared halo rows)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -117,7 +113,6 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
   // pixel outside the tensor is an offset beyond the descriptor's range and arrives as ZEROS (tools/probes/
   // buffer_lds_oob_probe.hip): no zero page, no choice between two 64-bit pointers per lane, and the buffer form is the
   // cheaper one to issue beside MFMAs (tools/probes/lds_dma_issue_probe.hip)
-  constexpr unsigned OOB = 0x80000000u;
   const int64_t rbase = n0 - W - 1 > 0 ? n0 - W - 1 : 0;
   const __amdgpu_buffer_rsrc_t rsrc_h1 = buffer_rsrc_unbounded(h1 + rbase * CM);
 
@@ -171,18 +166,7 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
     constexpr int NRNG = 3 * CCH;
     static_assert(NRNG > DIST && NI == 4 && WN == 1, "range ring");
     char* const extra = Bs + NST * B_ST;                     // [stage][8 groups][2 slots] x 16 B
-    auto tap_mask = [&](int64_t n) {
-      unsigned m = 0;
-      const bool okn = n < npix;
-      const int64_t nc = okn ? n : 0;
-      const int64_t nb = nc / ((int64_t)H * W);
-      const int r = (int)(nc - nb * H * W);
-      const int oh = r / W, ow = r - oh * W;
-      for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b)
-          if (okn && oh - 1 + a >= 0 && oh - 1 + a < H && ow - 1 + b >= 0 && ow - 1 + b < W) m |= 1u << (a * 3 + b);
-      return m;
-    };
+    const TapMask tap_mask{npix, H, W};
     unsigned rmask[NI];                                      // of the pixels this lane reads as its B columns
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) rmask[ni] = tap_mask(n0 + ni * 32 + li);
@@ -299,18 +283,7 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
     constexpr int RW = CM == 64 ? 12 : (CM == 128 ? 8 : 4);
     static_assert(NST >= 3 && MI == 2, "once-staged form");
     char* const extra = Bs + 3 * B_ST;
-    auto tap_mask = [&](int64_t n) {
-      unsigned m = 0;
-      const bool okn = n < npix;
-      const int64_t nc = okn ? n : 0;
-      const int64_t nb = nc / ((int64_t)H * W);
-      const int r = (int)(nc - nb * H * W);
-      const int oh = r / W, ow = r - oh * W;
-      for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b)
-          if (okn && oh - 1 + a >= 0 && oh - 1 + a < H && ow - 1 + b >= 0 && ow - 1 + b < W) m |= 1u << (a * 3 + b);
-      return m;
-    };
+    const TapMask tap_mask{npix, H, W};
     unsigned rmask[NI];                                      // of the pixels this lane reads as its B columns
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) rmask[ni] = tap_mask(n0 + (wn * NI + ni) * 32 + li);
@@ -852,16 +825,12 @@ int launch(const uint16_t* h1, int64_t NB, int64_t H, int64_t W, const uint16_t*
 extern "C" int tspn_bottleneck_tail_bf16(const uint16_t* h1, int64_t NB, int64_t H, int64_t W, int64_t CM,
                                          const uint16_t* frag2, const float* bias2, const uint16_t* frag3,
                                          const float* bias3, const uint16_t* residual, uint16_t* out, void* stream) {
-  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0, TSPN_EINVAL, "tspn_bottleneck_tail_bf16: bad sizes");
-  TSPN_REQUIRE(CM == 64 || CM == 128 || CM == 256, TSPN_EUNSUPPORTED,
-               "tspn_bottleneck_tail_bf16: bottleneck channels must be 64, 128 or 256 (got %lld)", (long long)CM);
+  const char* what = "tspn_bottleneck_tail_bf16";
+  if (int rc = tspn::tail_shape_checks(what, NB, H, W, CM, CM == 64 || CM == 128 || CM == 256,
+                                       "bottleneck channels must be 64, 128 or 256"))
+    return rc;
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(h1 && frag2 && bias2 && frag3 && bias3 && residual && out, TSPN_EINVAL,
-               "tspn_bottleneck_tail_bf16: null pointer");
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(h1) && al16(frag2) && al16(bias2) && al16(frag3) && al16(bias3) && al16(residual) && al16(out),
-               TSPN_EUNSUPPORTED, "tspn_bottleneck_tail_bf16: operands must be 16-byte aligned");
-  TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20), TSPN_EUNSUPPORTED, "tspn_bottleneck_tail_bf16: dimension too large");
+  if (int rc = tspn::tail_operand_checks(what, H, W, {h1, frag2, bias2, frag3, bias3, residual, out})) return rc;
   if (CM == 256) return launch<256, false>(h1, NB, H, W, frag2, bias2, frag3, bias3, residual, out, stream);
   if (CM == 128) return launch<128, false>(h1, NB, H, W, frag2, bias2, frag3, bias3, residual, out, stream);
   return launch<64, false>(h1, NB, H, W, frag2, bias2, frag3, bias3, residual, out, stream);
@@ -871,16 +840,11 @@ extern "C" int tspn_bottleneck_tail_next_bf16(const uint16_t* h1, int64_t NB, in
                                               const uint16_t* frag2, const float* bias2, const uint16_t* frag3,
                                               const float* bias3, const uint16_t* residual, uint16_t* out,
                                               const uint16_t* frag1n, const float* bias1n, uint16_t* h1n, void* stream) {
-  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0, TSPN_EINVAL, "tspn_bottleneck_tail_next_bf16: bad sizes");
-  TSPN_REQUIRE(CM == 256, TSPN_EUNSUPPORTED,
-               "tspn_bottleneck_tail_next_bf16: built for 256 bottleneck channels (got %lld)", (long long)CM);
+  const char* what = "tspn_bottleneck_tail_next_bf16";
+  if (int rc = tspn::tail_shape_checks(what, NB, H, W, CM, CM == 256, "built for 256 bottleneck channels")) return rc;
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(h1 && frag2 && bias2 && frag3 && bias3 && residual && out && frag1n && bias1n && h1n, TSPN_EINVAL,
-               "tspn_bottleneck_tail_next_bf16: null pointer");
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(h1) && al16(frag2) && al16(bias2) && al16(frag3) && al16(bias3) && al16(residual) && al16(out) &&
-                   al16(frag1n) && al16(bias1n) && al16(h1n),
-               TSPN_EUNSUPPORTED, "tspn_bottleneck_tail_next_bf16: operands must be 16-byte aligned");
-  TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20), TSPN_EUNSUPPORTED, "tspn_bottleneck_tail_next_bf16: dimension too large");
+  if (int rc = tspn::tail_operand_checks(what, H, W,
+                                         {h1, frag2, bias2, frag3, bias3, residual, out, frag1n, bias1n, h1n}))
+    return rc;
   return launch<256, true>(h1, NB, H, W, frag2, bias2, frag3, bias3, residual, out, stream, frag1n, bias1n, h1n);
 }

@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "tspn_common.h"
+#include "tspn_conv3x3_ranges.h"
 #include "tspn_device.h"
 #include "tspn_status.h"
 
@@ -35,10 +36,8 @@ using namespace tspn_dev;
 
 constexpr int CM = 256;
 constexpr int THREADS = 512;
-constexpr int BN = 128;                 // pixels per tile
-constexpr int KC = 64;                  // channels per chunk
-constexpr int SLP = 132;                // padded pixel slots per channel group
-constexpr int B_ST = 8 * SLP * 16;      // bytes per x stage = per 64 channels of the h2 image
+// BN, KC, SLP, B_ST: tspn_conv3x3_ranges.h -- the tile of bottleneck_bf16_kernel<256>, whose layouts this kernel repeats
+static_assert(BN == 128 && KC == 64 && SLP == 132 && B_ST == 8 * SLP * 16, "tile plan of the tail");
 constexpr int MI = 2, NI = 4;           // 32-row blocks / 32-pixel blocks per A wave (wave wm: rows [64 wm, 64 wm + 64))
 constexpr int CCH = CM / KC;            // 4
 constexpr int NCHUNKS = 9 * CCH;
@@ -73,13 +72,6 @@ __device__ __forceinline__ void a_barrier(char* Bs, int lane, unsigned& epoch, i
   lds_wait_ge(Bs, SYNC_OFF, epoch, status);
 }
 
-// tile of workgroup-slot `v` (0 .. tiles - 1): consecutive tiles stay on one XCD (shared halo rows), as in the
-// one-tile-per-workgroup kernel
-__device__ __forceinline__ int64_t tile_of(int v, int ntiles) {
-  const int q8 = ntiles >> 3, r8 = ntiles & 7, xcd = v & 7;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (v >> 3);
-}
-
 // ------------------------------------------------------------------------------------------------ team A: phase 2
 __device__ __forceinline__ void team_a(const __bf16* __restrict__ h1, const __bf16* __restrict__ Wf2,
                                        const float* __restrict__ bias2, int H, int W, int64_t npix, int ntiles,
@@ -110,19 +102,9 @@ __device__ __forceinline__ void team_a(const __bf16* __restrict__ h1, const __bf
     char* const extra = Bs + EXTRA_OFF;
     const int slot = 64 * (w4 & 1) + lane;                 // x pieces: one pixel per lane, channel groups bg, bg + 2, ..
     const int bg = w4 >> 1;
-    const int64_t n0 = tile_of(it * G + (int)blockIdx.x, ntiles) * BN;
-    auto tap_mask = [&](int64_t n) {
-      unsigned m = 0;
-      const bool okn = n < npix;
-      const int64_t nc = okn ? n : 0;
-      const int64_t nb = nc / ((int64_t)H * W);
-      const int r = (int)(nc - nb * H * W);
-      const int oh = r / W, ow = r - oh * W;
-      for (int a = 0; a < 3; ++a)
-        for (int b = 0; b < 3; ++b)
-          if (okn && oh - 1 + a >= 0 && oh - 1 + a < H && ow - 1 + b >= 0 && ow - 1 + b < W) m |= 1u << (a * 3 + b);
-      return m;
-    };
+    // tile of workgroup-slot it G + b: consecutive tiles stay on one XCD (shared halo rows), as in the one-tile-per-workgroup kernel
+    const int64_t n0 = (int64_t)xcd_remap(it * G + (int)blockIdx.x, ntiles) * BN;
+    const TapMask tap_mask{npix, H, W};
     unsigned rmask[NI];
 #pragma unroll
     for (int ni = 0; ni < NI; ++ni) rmask[ni] = tap_mask(n0 + ni * 32 + li);
@@ -299,7 +281,8 @@ __device__ __forceinline__ void team_b(const __bf16* __restrict__ Wf3, const flo
       return w3base + (int64_t)(sub_rb(sp) + ms) * (CCH * 4096) + k * 1024;
     };
     const unsigned voff_in = (unsigned)(li * C4 + 16 * kh) * 2, voff_out = (unsigned)(16 * kh) * 2;
-    const int64_t n0 = tile_of(it * G + (int)blockIdx.x, ntiles) * BN;
+    // tile of workgroup-slot it G + b: consecutive tiles stay on one XCD (shared halo rows), as in the one-tile-per-workgroup kernel
+    const int64_t n0 = (int64_t)xcd_remap(it * G + (int)blockIdx.x, ntiles) * BN;
     unsigned okmask = 0;
 #pragma unroll
     for (int b = 0; b < 4; ++b) okmask |= (n0 + b * 32 + li < npix ? 1u : 0u) << b;
@@ -450,16 +433,10 @@ extern "C" int tspn_bottleneck_tail_pipe_bf16(const uint16_t* h1, int64_t NB, in
                                               const uint16_t* frag2, const float* bias2, const uint16_t* frag3,
                                               const float* bias3, const uint16_t* residual, uint16_t* out,
                                               int64_t max_workgroups, void* stream) {
-  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0, TSPN_EINVAL, "tspn_bottleneck_tail_pipe_bf16: bad sizes");
-  TSPN_REQUIRE(CMi == CM, TSPN_EUNSUPPORTED,
-               "tspn_bottleneck_tail_pipe_bf16: built for 256 bottleneck channels (got %lld)", (long long)CMi);
+  const char* what = "tspn_bottleneck_tail_pipe_bf16";
+  if (int rc = tspn::tail_shape_checks(what, NB, H, W, CMi, CMi == CM, "built for 256 bottleneck channels")) return rc;
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(h1 && frag2 && bias2 && frag3 && bias3 && residual && out, TSPN_EINVAL,
-               "tspn_bottleneck_tail_pipe_bf16: null pointer");
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(h1) && al16(frag2) && al16(bias2) && al16(frag3) && al16(bias3) && al16(residual) && al16(out),
-               TSPN_EUNSUPPORTED, "tspn_bottleneck_tail_pipe_bf16: operands must be 16-byte aligned");
-  TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20), TSPN_EUNSUPPORTED, "tspn_bottleneck_tail_pipe_bf16: dimension too large");
+  if (int rc = tspn::tail_operand_checks(what, H, W, {h1, frag2, bias2, frag3, bias3, residual, out})) return rc;
   const int64_t npix = NB * H * W;
   const int64_t tiles = tspn::ceil_div(npix, BN);
   TSPN_REQUIRE(tiles < (1LL << 30), TSPN_EUNSUPPORTED, "tspn_bottleneck_tail_pipe_bf16: too many tiles");

@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <initializer_list>
 
 #include "tspn_mi355x.h"
 
@@ -35,6 +36,12 @@ inline int check_launch(const char* what) {
 }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+// 16-byte alignment, which every vector load, LDS-DMA piece and buffer descriptor of the kernels asks of its operands
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+template <class... P>
+inline bool all_aligned16(const P*... p) {
+  return (aligned16(p) && ...);
+}
 // the smallest power of two >= n (1 for n <= 1)
 __host__ __device__ inline int64_t next_pow2(int64_t n) {
   int64_t p = 1;
@@ -141,3 +148,30 @@ int span_prefix_stage(const float* feats, int64_t NT, int64_t T, int64_t D, cons
   } while (0)
 
 #define TSPN_STREAM(s) reinterpret_cast<hipStream_t>(s)
+
+namespace tspn {
+
+// The opening checks of the four res4 tail entries (tail, tail_next, tail_io, tail_pipe), in two steps with the entry's
+// own `if (NB == 0) return TSPN_OK;` between them -- an empty batch is accepted without a look at its operands.  The
+// order decides which error a doubly wrong call gets.  First the sizes and the channel count (`channels_ok`;
+// `channel_rule` words the refusal) ...
+inline int tail_shape_checks(const char* what, int64_t NB, int64_t H, int64_t W, int64_t CM, bool channels_ok,
+                             const char* channel_rule) {
+  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0, TSPN_EINVAL, "%s: bad sizes", what);
+  TSPN_REQUIRE(channels_ok, TSPN_EUNSUPPORTED, "%s: %s (got %lld)", what, channel_rule, (long long)CM);
+  return TSPN_OK;
+}
+// ... then null operands, their alignment, and H, W below 2^20 (32-bit pixel arithmetic in the tap mask).
+inline int tail_operand_checks(const char* what, int64_t H, int64_t W, std::initializer_list<const void*> operands) {
+  bool all = true, aligned = true;
+  for (const void* p : operands) {
+    all = all && p != nullptr;
+    aligned = aligned && aligned16(p);
+  }
+  TSPN_REQUIRE(all, TSPN_EINVAL, "%s: null pointer", what);
+  TSPN_REQUIRE(aligned, TSPN_EUNSUPPORTED, "%s: operands must be 16-byte aligned", what);
+  TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20), TSPN_EUNSUPPORTED, "%s: dimension too large", what);
+  return TSPN_OK;
+}
+
+}  // namespace tspn

@@ -66,20 +66,10 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_mfma_kernel(
   float* As = reinterpret_cast<float*>(smem_raw);  // [2][3][KC][BM]
   float* Bs = As + 2 * A_STAGE;                     // [2][KC][BNP]
 
-  // ---- workgroup -> tile: bijective XCD remap, then 8x8 tile groups so that the
-  // workgroups resident on one XCD share weight panels and x panels in its L2.
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (bid >> 3);
+  // ---- workgroup -> tile: bijective XCD remap, then groups of 8 weight panels (tspn_device.h)
   constexpr int GM = 8;
-  const int group_sz = GM * tiles_n;
-  const int group = wg / group_sz;
-  const int first_m = group * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int in_group = wg - group * group_sz;
-  const int tile_m = first_m + in_group % gm;
-  const int tile_n = in_group / gm;
+  int tile_m, tile_n;
+  grouped_tile(xcd_remap(blockIdx.x, gridDim.x), GM, tiles_m, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * BM;
   const int64_t n0 = (int64_t)tile_n * BN;
 
@@ -327,18 +317,9 @@ __global__ __launch_bounds__(THREADS, (KCD == 8 ? 4 : 2)) void conv3_mfma_dma_ke
   float* As = reinterpret_cast<float*>(smem_raw);  // [2][3][KCD][BM]
   float* Bs = As + 2 * A_ST;                        // [2][KCD][BNP]
 
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q + 1) : r8 * (q + 1) + (xcd - r8) * q) + (bid >> 3);
   constexpr int GM = 8;
-  const int group_sz = GM * tiles_n;
-  const int group = wg / group_sz;
-  const int first_m = group * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int in_group = wg - group * group_sz;
-  const int tile_m = first_m + in_group % gm;
-  const int tile_n = in_group / gm;
+  int tile_m, tile_n;
+  grouped_tile(xcd_remap(blockIdx.x, gridDim.x), GM, tiles_m, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * BM;
   const int64_t n0 = (int64_t)tile_n * BN;
 
@@ -583,18 +564,9 @@ __global__ __launch_bounds__(THREADS, 2) void conv3_mfma_cl_kernel(
   float* As = reinterpret_cast<float*>(smem_raw);  // [2][3][16][BM]
   float* Bs = As + 2 * CL_A_ST;                     // [2][4][132][4]
 
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   constexpr int GM = 8;
-  const int group_sz = GM * tiles_n;
-  const int group = wg / group_sz;
-  const int first_m = group * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int in_group = wg - group * group_sz;
-  const int tile_m = first_m + in_group % gm;
-  const int tile_n = in_group / gm;
+  int tile_m, tile_n;
+  grouped_tile(xcd_remap(blockIdx.x, gridDim.x), GM, tiles_m, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * BM;
   const int64_t n0 = (int64_t)tile_n * BN;
 
@@ -809,7 +781,7 @@ extern "C" int tspn_conv3_f32(const float* x, int64_t B, int64_t Cin, int64_t T,
   const int64_t tiles_m = tspn::ceil_div(M, BM);
   const int64_t tiles_n = tspn::ceil_div(ncols, BN);
   TSPN_REQUIRE(tiles_m * tiles_n < (1LL << 31), TSPN_EUNSUPPORTED, "tspn_conv3_f32: grid too large");
-  const bool vec = (M % 4 == 0) && ((reinterpret_cast<uintptr_t>(packed) & 15) == 0);
+  const bool vec = (M % 4 == 0) && tspn::aligned16(packed);
   const bool dma = vec && (Cin % 8 == 0);
   const int kcd = (Cin % 16 != 0) ? 8 : 16;
   const bool dma8 = dma && kcd == 8;
@@ -844,9 +816,8 @@ int tspn::conv3_tc_direct(const float* x, int64_t B, int64_t T, int64_t Cin, con
   TSPN_REQUIRE(Cin % CL_KC == 0 && M % 4 == 0, TSPN_EUNSUPPORTED,
                "tspn_conv3_tc_f32: needs Cin %% 16 == 0 and M %% 4 == 0 (Cin=%lld M=%lld)",
                (long long)Cin, (long long)M);
-  TSPN_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(x) & 15) == 0,
-               TSPN_EUNSUPPORTED, "tspn_conv3_tc_f32: x and packed must be 16-byte aligned");
+  TSPN_REQUIRE(tspn::all_aligned16(packed, x), TSPN_EUNSUPPORTED,
+               "tspn_conv3_tc_f32: x and packed must be 16-byte aligned");
   TSPN_REQUIRE(Cin < (1 << 24) && T < (1 << 24) && M < (1 << 24), TSPN_EUNSUPPORTED,
                "tspn_conv3_tc_f32: dimension too large");
   const int64_t ncols = B * T;

@@ -1,5 +1,6 @@
 // Device-side vocabulary shared by the MFMA kernel files (gfx950 only): vector types, the global-to-LDS DMA pieces in
-// their pointer and buffer forms, buffer descriptors, and the inline-asm fragment loads with their counted waits.  One
+// their pointer and buffer forms, buffer descriptors, the inline-asm fragment loads with their counted waits, and the
+// workgroup-to-tile maps.  One
 // definition each; a kernel file pulls them in with `using namespace tspn_dev;` inside its anonymous namespace.  What
 // belongs to ONE kernel's plan (tile constants, LDS counters, role barriers, packed-math helpers) stays in its file.
 // Everything here is force-inlined: -fno-gpu-rdc gives no device symbols across translation units.
@@ -72,6 +73,27 @@ __device__ __forceinline__ void wait_w(f32x4& r0, f32x4& r1) {
 template <int N>
 __device__ __forceinline__ void wait_vmcnt() {
   asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
+}
+
+// ---- workgroup -> tile maps.
+// bijective XCD remap of `n` workgroups: the hardware deals consecutive block ids round the 8 XCDs, this gives XCD x a
+// contiguous range of the logical ids (which therefore share its L2)
+__device__ __forceinline__ int xcd_remap(int id, int n) {
+  const int q8 = n >> 3, r8 = n & 7, xcd = id & 7;
+  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
+}
+// Grouped tile numbering of a tiles_m x tiles_n grid: groups of GM weight panels (row tiles) x all column tiles, the
+// row tile running fastest inside a group, so that the workgroups resident on one XCD (consecutive `wg` after
+// xcd_remap) share a few weight panels and column panels in its L2.  The last group holds tiles_m % GM row tiles when
+// that is not zero.
+__device__ __forceinline__ void grouped_tile(int wg, int GM, int tiles_m, int tiles_n, int& tile_m, int& tile_n) {
+  const int group_sz = GM * tiles_n;
+  const int group = wg / group_sz;
+  const int first_m = group * GM;
+  const int gm = min(GM, tiles_m - first_m);
+  const int in_group = wg - group * group_sz;
+  tile_m = first_m + in_group % gm;
+  tile_n = in_group / gm;
 }
 
 }  // namespace tspn_dev

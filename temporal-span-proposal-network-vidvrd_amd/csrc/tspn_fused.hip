@@ -98,8 +98,7 @@ extern "C" int tspn_forward_fused_f32(const tspn_fused_desc* d, void* stream) {
   // The conv algorithm and its refusals, before anything is launched (a refused pass leaves both outputs untouched).
   // The channels-last kernel consumes the tracklet layout [NT,T,D] directly; ragged shapes go
   // through a transpose to channels-first [NT,D,T] and the general kernel.
-  const bool tc = (D % 16 == 0) && ((reinterpret_cast<uintptr_t>(d->feats) & 15) == 0) &&
-                  ((reinterpret_cast<uintptr_t>(d->conv_packed) & 15) == 0);
+  const bool tc = (D % 16 == 0) && tspn::all_aligned16(d->feats, d->conv_packed);
   TSPN_REQUIRE(d->conv_algo == TSPN_CONV_DIRECT || d->conv_algo == TSPN_CONV_WINOGRAD63 ||
                    d->conv_algo == TSPN_CONV_WINOGRAD63_F16X3,
                TSPN_EINVAL,

@@ -160,6 +160,20 @@ constexpr int PG_S = 8, PG_O = 8, PG_CK = 16, PG_T = 32;
 constexpr int PG_ROWS = PG_S + PG_O;
 constexpr int PG_STAGE = PG_ROWS * PG_CK * PG_T;  // floats per LDS buffer (32 KB)
 
+// Pair-stage map: workgroup -> (group = (video, frame block), subject block sb, object block ob).  The nsb * nob
+// workgroups of one group read the same tracklet rows and walk the channels in step, so they are placed on ONE XCD
+// (ids congruent mod 8 share an XCD) and dispatched back to back: each row chunk then comes from HBM once and from that
+// XCD's L2 for the other blocks.  The grid is rounded up to whole rounds of 8 groups: a kernel returns where the
+// group number is >= its ngroups (uniform per workgroup, before any barrier).
+__device__ __forceinline__ int64_t pair_stage_group(int id, int nsb, int nob, int& sb, int& ob) {
+  const int per_group = nsb * nob;
+  const int xcd = id & 7, k = id >> 3;
+  const int member = k % per_group;
+  sb = member / nob;
+  ob = member - sb * nob;
+  return (int64_t)(k / per_group) * 8 + xcd;
+}
+
 template <bool VEC2>
 __global__ __launch_bounds__(256, 2) void heads_pairgrid_kernel(
     const float* __restrict__ y, int C, int T, int N, const float* __restrict__ Wh,
@@ -171,17 +185,9 @@ __global__ __launch_bounds__(256, 2) void heads_pairgrid_kernel(
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int j = lane & 15, kq = lane >> 4;
-  // Workgroup -> (video, frame block, subject block, object block).  The nsb*nob workgroups of
-  // one (video, frame block) group read the same tracklet rows and walk the channels in step, so
-  // they are placed on ONE XCD (ids congruent mod 8 share an XCD) and dispatched back to back:
-  // each row chunk then comes from HBM once and from that XCD's L2 for the other blocks.
-  const int per_group = nsb * nob;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, k = id >> 3;
-  const int64_t G = (int64_t)(k / per_group) * 8 + xcd;
+  int sb, ob;
+  const int64_t G = pair_stage_group(blockIdx.x, nsb, nob, sb, ob);
   if (G >= ngroups) return;  // uniform per workgroup, before any barrier
-  const int member = k % per_group;
-  const int sb = member / nob, ob = member - sb * nob;
   const int64_t b = G / ntb;
   const int tb = (int)(G - b * ntb);
   const int t0 = tb * PG_T;
@@ -330,13 +336,9 @@ __global__ __launch_bounds__(256, 2) void heads_pairgrid3_kernel(
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int j = lane & 15, kq = lane >> 4;
-  const int per_group = nsb * nob;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, k = id >> 3;
-  const int64_t G = (int64_t)(k / per_group) * 8 + xcd;
+  int sb, ob;
+  const int64_t G = pair_stage_group(blockIdx.x, nsb, nob, sb, ob);
   if (G >= ngroups) return;
-  const int member = k % per_group;
-  const int sb = member / nob, ob = member - sb * nob;
   const int64_t b = G / ntb;
   const int tb = (int)(G - b * ntb);
   const int t0 = tb * PG_T;
@@ -557,13 +559,9 @@ __global__ __launch_bounds__(256, CK == 8 ? 3 : 2) void heads_pairgrid4_kernel(
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int si = lane >> 5, tl = lane & 31;
-  const int per_group = nsb * nob;
-  const int id = blockIdx.x;
-  const int xcd = id & 7, k = id >> 3;
-  const int64_t G = (int64_t)(k / per_group) * 8 + xcd;
+  int sb, ob;
+  const int64_t G = pair_stage_group(blockIdx.x, nsb, nob, sb, ob);
   if (G >= ngroups) return;
-  const int member = k % per_group;
-  const int sb = member / nob, ob = member - sb * nob;
   const int64_t b = G / ntb;
   const int tb = (int)(G - b * ntb);
   const int t0 = tb * PG_T;
@@ -764,7 +762,7 @@ int tspn::heads_pairgrid(const float* y, int64_t ldt, int64_t B, int64_t N, int6
   // v3 (LDS-DMA staging + pipelined activations) needs 16-byte pieces inside a row and even frame
   // pairs in the output; anything else runs the register-staged kernel
   const bool v3 = (ldt % 4 == 0) && ldt >= 4 && (C % PG_CK == 0) && (T % 2 == 0) &&
-                  ((reinterpret_cast<uintptr_t>(y) & 15) == 0) &&
+                  tspn::aligned16(y) &&
                   ((reinterpret_cast<uintptr_t>(out) & 7) == 0);
   const bool vec2 = (T % 2 == 0) && (ldt % 2 == 0) && ((reinterpret_cast<uintptr_t>(y) & 7) == 0) &&
                     ((reinterpret_cast<uintptr_t>(out) & 7) == 0);

@@ -152,9 +152,7 @@ extern "C" int tspn_traj_iou_f32(const float* boxes1, int64_t N1, const float* b
   }
   if (B == 0 || N1 == 0 || N2 == 0) return TSPN_OK;
   TSPN_REQUIRE(boxes1 && out, TSPN_EINVAL, "tspn_traj_iou_f32: null pointer");
-  TSPN_REQUIRE((reinterpret_cast<uintptr_t>(boxes1) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(boxes2) & 15) == 0,
-               TSPN_EINVAL, "tspn_traj_iou_f32: boxes must be 16-byte aligned");
+  TSPN_REQUIRE(tspn::all_aligned16(boxes1, boxes2), TSPN_EINVAL, "tspn_traj_iou_f32: boxes must be 16-byte aligned");
   TSPN_REQUIRE(B < 65536, TSPN_EUNSUPPORTED, "tspn_traj_iou_f32: B too large");
   dim3 grid((unsigned)tspn::ceil_div(N1 * N2, 256), (unsigned)B);
   hipLaunchKernelGGL(traj_iou_kernel, grid, dim3(256), 0, TSPN_STREAM(stream),

@@ -276,11 +276,11 @@ extern "C" int tspn_pair_gather_f32(const float* feats, const float* boxes, int6
   TSPN_REQUIRE(pairs, TSPN_EINVAL, "tspn_pair_gather_f32: null pairs");
   TSPN_REQUIRE(!out_feat || feats, TSPN_EINVAL, "tspn_pair_gather_f32: out_feat needs feats");
   TSPN_REQUIRE(!out_geom || boxes, TSPN_EINVAL, "tspn_pair_gather_f32: out_geom needs boxes");
-  TSPN_REQUIRE(!boxes || (reinterpret_cast<uintptr_t>(boxes) & 15) == 0, TSPN_EINVAL,
+  TSPN_REQUIRE(!boxes || tspn::aligned16(boxes), TSPN_EINVAL,
                "tspn_pair_gather_f32: boxes must be 16-byte aligned");
   hipStream_t s = TSPN_STREAM(stream);
-  const bool rows_form = out_feat && D % TG_C == 0 && T <= TG_TMAX && ((reinterpret_cast<uintptr_t>(feats) & 15) == 0) &&
-                         ((reinterpret_cast<uintptr_t>(out_feat) & 15) == 0) && (2 * P) * (D / TG_C) < (1LL << 31);
+  const bool rows_form = out_feat && D % TG_C == 0 && T <= TG_TMAX && tspn::all_aligned16(feats, out_feat) &&
+                         (2 * P) * (D / TG_C) < (1LL << 31);
   if (rows_form) {
     const size_t smem = sizeof(float) * TG_C * T;
     hipLaunchKernelGGL(transpose_gather_rows_kernel, dim3((unsigned)((2 * P) * (D / TG_C))), dim3(256), smem, s, feats, pairs,

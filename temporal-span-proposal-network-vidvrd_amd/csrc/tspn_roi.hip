@@ -60,18 +60,9 @@ __global__ __launch_bounds__(THREADS, 2) void conv2d_nhwc_kernel(
   float* Bs = As + 2 * A_ST;                         // [2][KC/4 groups][132 slots][4 ch]
 
   // workgroup -> tile: bijective XCD remap, then groups of GM weight panels x all pixel tiles
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   constexpr int GM = 4;
-  const int group_sz = GM * tiles_n;
-  const int group = wg / group_sz;
-  const int first_m = group * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int in_group = wg - group * group_sz;
-  const int tile_m = first_m + in_group % gm;
-  const int tile_n = in_group / gm;
+  int tile_m, tile_n;
+  grouped_tile(xcd_remap(blockIdx.x, gridDim.x), GM, tiles_m, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * BM;
   const int64_t n0 = (int64_t)tile_n * BN;
 
@@ -270,18 +261,9 @@ __global__ __launch_bounds__(THREADS, 2) void conv2d_nhwc_frag_kernel(
     int KW, int stride, int pad, int OH, int OW, int64_t npix, int tiles_m, int tiles_n, int relu) {
   __shared__ __attribute__((aligned(16))) float Bs[2 * F_B_ST];
 
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   constexpr int GM = 4;
-  const int group_sz = GM * tiles_n;
-  const int group = wg / group_sz;
-  const int first_m = group * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int in_group = wg - group * group_sz;
-  const int tile_m = first_m + in_group % gm;
-  const int tile_n = in_group / gm;
+  int tile_m, tile_n;
+  grouped_tile(xcd_remap(blockIdx.x, gridDim.x), GM, tiles_m, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * BM;
   const int64_t n0 = (int64_t)tile_n * BN;
 
@@ -572,8 +554,8 @@ extern "C" int tspn_conv2d_nhwc_f32(const float* x, int64_t NB, int64_t H, int64
   TSPN_REQUIRE(Cin % 16 == 0 && Cout % 4 == 0, TSPN_EUNSUPPORTED,
                "tspn_conv2d_nhwc_f32: needs Cin %% 16 == 0 and Cout %% 4 == 0 (Cin=%lld Cout=%lld)", (long long)Cin,
                (long long)Cout);
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(x) && al16(packed) && al16(out) && (!bias || al16(bias)) && (!residual || al16(residual)),
+  TSPN_REQUIRE(tspn::all_aligned16(x, packed, out) && (!bias || tspn::aligned16(bias)) &&
+                   (!residual || tspn::aligned16(residual)),
                TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_f32: operands must be 16-byte aligned");
   TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20) && Cin < (1 << 24) && Cout < (1 << 24), TSPN_EUNSUPPORTED,
                "tspn_conv2d_nhwc_f32: dimension too large");
@@ -617,8 +599,8 @@ extern "C" int tspn_conv2d_nhwc_frag_f32(const float* x, int64_t NB, int64_t H, 
   TSPN_REQUIRE(Cin % 16 == 0 && Cout % 32 == 0, TSPN_EUNSUPPORTED,
                "tspn_conv2d_nhwc_frag_f32: needs Cin %% 16 == 0 and Cout %% 32 == 0 (Cin=%lld Cout=%lld)",
                (long long)Cin, (long long)Cout);
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(x) && al16(frag) && al16(out) && (!bias || al16(bias)) && (!residual || al16(residual)),
+  TSPN_REQUIRE(tspn::all_aligned16(x, frag, out) && (!bias || tspn::aligned16(bias)) &&
+                   (!residual || tspn::aligned16(residual)),
                TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_frag_f32: operands must be 16-byte aligned");
   TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20) && Cin < (1 << 24) && Cout < (1 << 24), TSPN_EUNSUPPORTED,
                "tspn_conv2d_nhwc_frag_f32: dimension too large");
@@ -655,8 +637,7 @@ extern "C" int tspn_conv2d_nhwc_cin4_f32(const float* x, int64_t NB, int64_t H, 
   TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "tspn_conv2d_nhwc_cin4_f32: empty output");
   if (NB == 0) return TSPN_OK;
   TSPN_REQUIRE(x && frag && out, TSPN_EINVAL, "tspn_conv2d_nhwc_cin4_f32: null pointer");
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(x) && al16(frag) && al16(out) && (!bias || al16(bias)), TSPN_EUNSUPPORTED,
+  TSPN_REQUIRE(tspn::all_aligned16(x, frag, out) && (!bias || tspn::aligned16(bias)), TSPN_EUNSUPPORTED,
                "tspn_conv2d_nhwc_cin4_f32: operands must be 16-byte aligned");
   const int64_t npix = NB * OH * OW;
   const int64_t tiles_m = tspn::ceil_div(Cout, BM), tiles_n = tspn::ceil_div(npix, BN);
@@ -676,8 +657,7 @@ static int roi_align_launch(const void* feat, bool bf16_in, int64_t NF, int64_t 
                TSPN_EINVAL, "tspn_roi_align_nhwc_f32: bad sizes");
   if (R == 0) return TSPN_OK;
   TSPN_REQUIRE(feat && rois && out, TSPN_EINVAL, "tspn_roi_align_nhwc_f32: null pointer");
-  TSPN_REQUIRE(C % 4 == 0 && (reinterpret_cast<uintptr_t>(feat) & 15) == 0 &&
-                   (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+  TSPN_REQUIRE(C % 4 == 0 && tspn::all_aligned16(feat, out),
                TSPN_EUNSUPPORTED, "tspn_roi_align_nhwc_f32: needs C %% 4 == 0 and 16-byte aligned tensors");
   TSPN_REQUIRE(R * P < (1LL << 31) && H < (1 << 20) && W < (1 << 20), TSPN_EUNSUPPORTED,
                "tspn_roi_align_nhwc_f32: problem too large");
@@ -722,7 +702,7 @@ extern "C" int tspn_max_pool_nhwc_f32(const float* x, int64_t NB, int64_t H, int
   TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "tspn_max_pool_nhwc_f32: empty output");
   if (NB == 0) return TSPN_OK;
   TSPN_REQUIRE(x && out, TSPN_EINVAL, "tspn_max_pool_nhwc_f32: null pointer");
-  TSPN_REQUIRE(C % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+  TSPN_REQUIRE(C % 4 == 0 && tspn::all_aligned16(x, out),
                TSPN_EUNSUPPORTED, "tspn_max_pool_nhwc_f32: needs C %% 4 == 0 and 16-byte aligned tensors");
   const int64_t total = NB * OH * OW * (C / 4);
   const int blocks = (int)std::min<int64_t>(tspn::ceil_div(total, 256), 1 << 20);

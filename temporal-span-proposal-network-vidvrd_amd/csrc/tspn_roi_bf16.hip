@@ -76,18 +76,9 @@ __global__ __launch_bounds__(THREADS, (MI == 1 ? TSPN_ROI_BF16_MI1_WAVES : 2)) v
   constexpr int ZERO_OFF = 2 * B_ST + 512;                // RNG: 16 bytes of zeros, the target of taps that fall off the image
   __shared__ __attribute__((aligned(16))) char Bs[ZERO_OFF + 16 > EPI_BYTES ? ZERO_OFF + 16 : EPI_BYTES];
 
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
   constexpr int GM = 4;
-  const int group_sz = GM * tiles_n;
-  const int group = wg / group_sz;
-  const int first_m = group * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int in_group = wg - group * group_sz;
-  const int tile_m = first_m + in_group % gm;
-  const int tile_n = in_group / gm;
+  int tile_m, tile_n;
+  grouped_tile(xcd_remap(blockIdx.x, gridDim.x), GM, tiles_m, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * BM;
   const int64_t n0 = (int64_t)tile_n * BN;
 
@@ -468,8 +459,8 @@ extern "C" int tspn_conv2d_nhwc_bf16(const uint16_t* x, int64_t NB, int64_t H, i
   TSPN_REQUIRE(Cin % KC == 0 && Cout % 32 == 0, TSPN_EUNSUPPORTED,
                "tspn_conv2d_nhwc_bf16: needs Cin %% 64 == 0 and Cout %% 32 == 0 (Cin=%lld Cout=%lld)", (long long)Cin,
                (long long)Cout);
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(x) && al16(frag) && al16(out) && (!bias || al16(bias)) && (!residual || al16(residual)),
+  TSPN_REQUIRE(tspn::all_aligned16(x, frag, out) && (!bias || tspn::aligned16(bias)) &&
+                   (!residual || tspn::aligned16(residual)),
                TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_bf16: operands must be 16-byte aligned");
   TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20) && Cin < (1 << 24) && Cout < (1 << 24), TSPN_EUNSUPPORTED,
                "tspn_conv2d_nhwc_bf16: dimension too large");

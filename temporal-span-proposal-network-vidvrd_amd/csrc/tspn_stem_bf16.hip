@@ -394,8 +394,7 @@ extern "C" int tspn_stem_conv_bf16(const float* x, int64_t NB, int64_t H, int64_
   const size_t need = tspn_stem_bf16_workspace_bytes(NB, H, W);
   TSPN_REQUIRE(workspace_bytes >= need, TSPN_EWORKSPACE, "tspn_stem_conv_bf16: workspace %zu < %zu bytes", workspace_bytes,
                need);
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(frag) && al16(bias) && al16(workspace) && al16(out), TSPN_EUNSUPPORTED,
+  TSPN_REQUIRE(tspn::all_aligned16(frag, bias, workspace, out), TSPN_EUNSUPPORTED,
                "tspn_stem_conv_bf16: operands must be 16-byte aligned");
   __bf16* S = static_cast<__bf16*>(workspace);
   hipStream_t s = TSPN_STREAM(stream);
@@ -440,8 +439,7 @@ extern "C" int tspn_stem_pool_bf16(const float* x, int64_t NB, int64_t H, int64_
   const size_t need = tspn_stem_bf16_workspace_bytes(NB, H, W);
   TSPN_REQUIRE(workspace_bytes >= need, TSPN_EWORKSPACE, "tspn_stem_pool_bf16: workspace %zu < %zu bytes", workspace_bytes,
                need);
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(frag) && al16(bias) && al16(workspace) && al16(out), TSPN_EUNSUPPORTED,
+  TSPN_REQUIRE(tspn::all_aligned16(frag, bias, workspace, out), TSPN_EUNSUPPORTED,
                "tspn_stem_pool_bf16: operands must be 16-byte aligned");
   __bf16* S = static_cast<__bf16*>(workspace);
   hipStream_t s = TSPN_STREAM(stream);
@@ -481,7 +479,7 @@ extern "C" int tspn_max_pool_nhwc_bf16(const uint16_t* x, int64_t NB, int64_t H,
   TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "tspn_max_pool_nhwc_bf16: empty output");
   if (NB == 0) return TSPN_OK;
   TSPN_REQUIRE(x && out, TSPN_EINVAL, "tspn_max_pool_nhwc_bf16: null pointer");
-  TSPN_REQUIRE(C % 8 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0,
+  TSPN_REQUIRE(C % 8 == 0 && tspn::aligned16(x) && tspn::aligned16(out),
                TSPN_EUNSUPPORTED, "tspn_max_pool_nhwc_bf16: needs C %% 8 == 0 and 16-byte aligned tensors");
   const int64_t total = NB * OH * OW * (C / 8);
   hipLaunchKernelGGL(max_pool_nhwc_bf16_kernel, dim3((unsigned)std::min<int64_t>(tspn::ceil_div(total, 256), 1 << 20)),

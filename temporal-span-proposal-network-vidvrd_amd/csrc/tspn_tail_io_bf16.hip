@@ -31,6 +31,7 @@
 #include <type_traits>
 
 #include "tspn_common.h"
+#include "tspn_conv3x3_ranges.h"
 #include "tspn_device.h"
 #include "tspn_status.h"
 
@@ -39,10 +40,10 @@ namespace {
 using namespace tspn_dev;
 
 constexpr int THREADS = 512;
-constexpr int BN = 128;                 // pixels per workgroup
-constexpr int CM = 256, C4 = 4 * CM, KC = 64, CCH = CM / KC;
-constexpr int SLP = 132;                // padded pixel slots per channel group
-constexpr int B_ST = 8 * SLP * 16;      // bytes per h1 range stage = per 64 channels of the h2 image
+constexpr int CM = 256, C4 = 4 * CM, CCH = CM / KC;
+// BN, KC, SLP, B_ST: tspn_conv3x3_ranges.h -- the tile of bottleneck_bf16_kernel<256>; the exchange buffers and the
+// quad -> pixel map below are laid out for exactly these values
+static_assert(BN == 128 && KC == 64 && SLP == 132 && B_ST == 8 * SLP * 16, "tile plan of the tail");
 constexpr int NST = 4, DIST = 3;        // ring of range stages, filled DIST ranges ahead
 constexpr int NRNG = 3 * CCH;           // ranges per tile: (64-channel part, tap row)
 constexpr int EXTRA_OFF = NST * B_ST;   // slots 128, 129 of a stage: [stage][8 groups][2 slots] x 16 B
@@ -74,10 +75,7 @@ __global__ __launch_bounds__(THREADS, 1) void tail_io_bf16_kernel(
     __bf16* __restrict__ out, int H, int W, int64_t npix, int32_t* __restrict__ status) {
   extern __shared__ __attribute__((aligned(16))) char Bs[];
 
-  const int nwg = gridDim.x, bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;      // consecutive pixel tiles stay on one XCD (shared halo rows)
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int64_t n0 = (int64_t)wg * BN;
+  const int64_t n0 = (int64_t)xcd_remap(blockIdx.x, gridDim.x) * BN;   // consecutive pixel tiles stay on one XCD (shared halo rows)
 
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -89,7 +87,6 @@ __global__ __launch_bounds__(THREADS, 1) void tail_io_bf16_kernel(
   if (tid >= 64 && tid < 80) reinterpret_cast<int*>(Bs + FLAG_OFF)[tid - 64] = 0;  // likewise
   for (int i = tid; i < CM; i += THREADS)                                          // b3 -> LDS, likewise
     *reinterpret_cast<float4*>(Bs + B3_OFF + 16 * i) = *reinterpret_cast<const float4*>(bias3 + 4 * i);
-  constexpr unsigned OOB = 0x80000000u;
   const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)Bs;
   const unsigned f_pub = lds0 + FLAG_OFF + 8 * w4, f_con = f_pub + 4;            // counters of this wave pair
   char* const xw = Bs + XCH_OFF + w4 * XCH_WAVE;                                   // exchange buffer of this wave pair
@@ -418,14 +415,10 @@ extern "C" int tspn_bottleneck_tail_io_bf16(const uint16_t* h1, int64_t NB, int6
                                             const uint16_t* frag2, const float* bias2, const uint16_t* frag3,
                                             const float* bias3, const uint16_t* residual, uint16_t* out, void* stream) {
   const char* what = "tspn_bottleneck_tail_io_bf16";
-  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0, TSPN_EINVAL, "%s: bad sizes", what);
-  TSPN_REQUIRE(CM_ == CM, TSPN_EUNSUPPORTED, "%s: built for 256 bottleneck channels (got %lld)", what, (long long)CM_);
+  if (int rc = tspn::tail_shape_checks(what, NB, H, W, CM_, CM_ == CM, "built for 256 bottleneck channels")) return rc;
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(h1 && frag2 && bias2 && frag3 && bias3 && residual && out, TSPN_EINVAL, "%s: null pointer", what);
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  TSPN_REQUIRE(al16(h1) && al16(frag2) && al16(bias2) && al16(frag3) && al16(bias3) && al16(residual) && al16(out),
-               TSPN_EUNSUPPORTED, "%s: operands must be 16-byte aligned", what);
-  TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20) && H * W < (1LL << 30), TSPN_EUNSUPPORTED, "%s: dimension too large", what);
+  if (int rc = tspn::tail_operand_checks(what, H, W, {h1, frag2, bias2, frag3, bias3, residual, out})) return rc;
+  TSPN_REQUIRE(H * W < (1LL << 30), TSPN_EUNSUPPORTED, "%s: dimension too large", what);   // 32-bit offsets inside an image
   const int64_t npix = NB * H * W;
   const int64_t tiles = tspn::ceil_div(npix, BN);
   TSPN_REQUIRE(tiles < (1LL << 31), TSPN_EUNSUPPORTED, "%s: grid too large", what);

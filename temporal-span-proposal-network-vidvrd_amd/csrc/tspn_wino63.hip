@@ -206,17 +206,8 @@ __global__ __launch_bounds__(THREADS) __attribute__((amdgpu_waves_per_eu(1, 1)))
   float* Vs = reinterpret_cast<float*>(smem_raw);
 
   // workgroup -> tile: bijective XCD remap, then groups of GM weight panels x all sextet tiles
-  const int nwg = gridDim.x;
-  const int bid = blockIdx.x;
-  const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-  const int wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-  const int group_sz = GM * tiles_n;
-  const int group = wg / group_sz;
-  const int first_m = group * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int in_group = wg - group * group_sz;
-  const int tile_m = first_m + in_group % gm;
-  const int tile_n = in_group / gm;
+  int tile_m, tile_n;
+  grouped_tile(xcd_remap(blockIdx.x, gridDim.x), GM, tiles_m, tiles_n, tile_m, tile_n);
   const int m0 = tile_m * BM;
   const int64_t S0 = (int64_t)tile_n * SWG;
 
@@ -831,13 +822,6 @@ __device__ __forceinline__ void wino63_f16x3_tile(
   }
 }
 
-// bijective XCD remap of `n` workgroups: the hardware deals consecutive block ids round the 8 XCDs, this gives XCD x a
-// contiguous range of the logical ids (which therefore share its L2)
-__device__ __forceinline__ int xcd_remap(int id, int n) {
-  const int q8 = n >> 3, r8 = n & 7, xcd = id & 7;
-  return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (id >> 3);
-}
-
 // The launch.  tiles_m x tiles_n tiles of 256 x 256, numbered in groups of GM row tiles x all sextet tiles.
 // `GM`: bits 0..7 the row tiles per group; bits 8..15 the tail split f (0 or 1: none).  With f = 2 or 4 the LAST
 // R = (gridDim.x - tiles) / (f - 1) tiles of that numbering are each cut into f tiles of 256 x 256 / f (sub-tiles), so
@@ -869,13 +853,8 @@ __global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
     wg = nfull + s / f;
     sub = s - (s / f) * f;
   }
-  const int group_sz = GM * tiles_n;
-  const int group = wg / group_sz;
-  const int first_m = group * GM;
-  const int gm = min(GM, tiles_m - first_m);
-  const int in_group = wg - group * group_sz;
-  const int tile_m = first_m + in_group % gm;
-  const int tile_n = in_group / gm;
+  int tile_m, tile_n;
+  grouped_tile(wg, GM, tiles_m, tiles_n, tile_m, tile_n);
   if (bid < nfull)
     wino63_f16x3_tile<4>(smem_raw, Vh, Ve, Wp, bias, y, park, Cin, T, M, nq, nsext, nsp2, tile_m, tile_n, tiles_n, 0, relu, ldy, vec2);
   else if (f == 2)
@@ -947,11 +926,11 @@ int tspn::wino63_input_transform(const float* x, int64_t B, int64_t T, int64_t C
   const char* what = "tspn_conv3_tc_wino63_f32(input transform)";
   if (int rc = check_common(what, B, T, Cin, 32, T)) return rc;
   if (B == 0) return TSPN_OK;
-  TSPN_REQUIRE(x && (reinterpret_cast<uintptr_t>(x) & 15) == 0, TSPN_EINVAL, "%s: x must be a 16-byte aligned pointer", what);
+  TSPN_REQUIRE(x && tspn::aligned16(x), TSPN_EINVAL, "%s: x must be a 16-byte aligned pointer", what);
   const size_t need = tspn::wino63_workspace_bytes(B, T, Cin);
   TSPN_REQUIRE(workspace && workspace_bytes >= need, TSPN_EWORKSPACE, "%s: workspace %zu < %zu bytes", what,
                workspace_bytes, need);
-  TSPN_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 15) == 0, TSPN_EINVAL, "%s: workspace must be 16-byte aligned",
+  TSPN_REQUIRE(tspn::aligned16(workspace), TSPN_EINVAL, "%s: workspace must be 16-byte aligned",
                what);
   const int64_t nq = tspn::ceil_div(T, 6);
   const int64_t nsext = B * nq, nsp = padded_sextets(B, T);
@@ -972,7 +951,7 @@ int tspn::wino63_contract(const void* workspace, int64_t B, int64_t T, int64_t C
   if (int rc = check_common(what, B, T, Cin, M, ldy)) return rc;
   if (B == 0) return TSPN_OK;
   TSPN_REQUIRE(workspace && frag && y, TSPN_EINVAL, "%s: null pointer", what);
-  TSPN_REQUIRE((reinterpret_cast<uintptr_t>(frag) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0,
+  TSPN_REQUIRE(tspn::aligned16(frag) && (reinterpret_cast<uintptr_t>(y) & 3) == 0,
                TSPN_EUNSUPPORTED, "%s: frag must be 16-byte aligned", what);
   const int64_t nq = tspn::ceil_div(T, 6);
   const int64_t nsext = B * nq, nsp = padded_sextets(B, T);
@@ -1044,7 +1023,7 @@ extern "C" int tspn_pack_conv3_wino63_f16x3(const float* W, int64_t M, int64_t C
   TSPN_REQUIRE(M > 0 && Cin > 0 && split >= 0, TSPN_EINVAL, "%s: bad sizes", what);
   TSPN_REQUIRE(split == 0 || Cin == 2 * split, TSPN_EINVAL, "%s: split=%lld requires Cin == 2*split (Cin=%lld)", what,
                (long long)split, (long long)Cin);
-  TSPN_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0, TSPN_EINVAL, "%s: packed must be 16-byte aligned", what);
+  TSPN_REQUIRE(tspn::aligned16(packed), TSPN_EINVAL, "%s: packed must be 16-byte aligned", what);
   const int64_t Mp = split ? 2 * M : M, Cp = split ? split : Cin;
   TSPN_REQUIRE(tspn::wino63_f16x3_supported(Cp, Mp), TSPN_EUNSUPPORTED,
                "%s: needs (packed) Cin %% 32 == 0 and M %% 256 == 0 (Cin=%lld M=%lld)", what, (long long)Cp, (long long)Mp);
@@ -1062,7 +1041,7 @@ int tspn::wino63_f16x3_input_transform(const float* x, int64_t B, int64_t T, int
   TSPN_REQUIRE(tspn::wino63_f16x3_supported(Cin, M), TSPN_EUNSUPPORTED,
                "%s: needs Cin %% 32 == 0 and M %% 256 == 0 (Cin=%lld M=%lld)", what, (long long)Cin, (long long)M);
   if (B == 0) return TSPN_OK;
-  TSPN_REQUIRE(x && (reinterpret_cast<uintptr_t>(x) & 15) == 0, TSPN_EINVAL, "%s: x must be a 16-byte aligned pointer", what);
+  TSPN_REQUIRE(x && tspn::aligned16(x), TSPN_EINVAL, "%s: x must be a 16-byte aligned pointer", what);
   const F16x3Layout L = f16x3_layout(B, T, Cin, M);
   TSPN_REQUIRE(workspace && workspace_bytes >= L.total, TSPN_EWORKSPACE, "%s: workspace %zu < %zu bytes", what,
                workspace_bytes, L.total);
@@ -1124,7 +1103,7 @@ int tspn::wino63_f16x3_contract(void* workspace, size_t workspace_bytes, int64_t
                "%s: needs Cin %% 32 == 0 and M %% 256 == 0 (Cin=%lld M=%lld)", what, (long long)Cin, (long long)M);
   if (B == 0) return TSPN_OK;
   TSPN_REQUIRE(workspace && packed && y, TSPN_EINVAL, "%s: null pointer", what);
-  TSPN_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0,
+  TSPN_REQUIRE(tspn::aligned16(packed) && (reinterpret_cast<uintptr_t>(y) & 3) == 0,
                TSPN_EUNSUPPORTED, "%s: packed weights must be 16-byte aligned", what);
   const F16x3Layout L = f16x3_layout(B, T, Cin, M);
   TSPN_REQUIRE(workspace_bytes >= L.total, TSPN_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes,
@@ -1160,7 +1139,7 @@ extern "C" int tspn_conv3_tc_wino63_f16x3(const float* x, int64_t B, int64_t T, 
                "%s: needs Cin %% 32 == 0 and M %% 256 == 0 (Cin=%lld M=%lld)", what, (long long)Cin, (long long)M);
   if (B > 0) {
     TSPN_REQUIRE(workspace && packed && y, TSPN_EINVAL, "%s: null pointer", what);
-    TSPN_REQUIRE((reinterpret_cast<uintptr_t>(packed) & 15) == 0 && (reinterpret_cast<uintptr_t>(y) & 3) == 0,
+    TSPN_REQUIRE(tspn::aligned16(packed) && (reinterpret_cast<uintptr_t>(y) & 3) == 0,
                  TSPN_EUNSUPPORTED, "%s: packed weights must be 16-byte aligned", what);
   }
   if (int rc = tspn::wino63_f16x3_input_transform(x, B, T, Cin, M, workspace, workspace_bytes, stream)) return rc;

@@ -59,7 +59,10 @@ def conv_ref64(xb, wb, b):
 
 
 @pytest.mark.parametrize("B,T,Cin,M", [(1, 1, 16, 4), (2, 5, 32, 8), (3, 30, 64, 128), (5, 33, 48, 132),
-                                       (2, 257, 128, 260), (7, 150, 64, 64), (40, 30, 32, 36)])
+                                       (2, 257, 128, 260), (7, 150, 64, 64), (40, 30, 32, 36),
+                                       # tile map: G_BM = G_BN = 256, GM = 2: M = 640 gives 3 row tiles = two groups, the
+                                       # second a single panel; 5 * 130 = 650 columns = 3 column tiles; grid 9 (9 % 8 = 1)
+                                       (5, 130, 32, 640)])
 def test_conv3_bf16_vs_fp64(tspn, device, B, T, Cin, M):
     x = r16(tspn.hashrng.uniform(82, "x", (B, T, Cin), -1, 1))
     w = tspn.hashrng.normal(82, "w", (M, Cin, 3), std=0.1)

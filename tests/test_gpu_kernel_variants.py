@@ -91,6 +91,28 @@ def test_conv3_mfma_dma_kernel_8_bias_and_tail(tspn, device):
         np.testing.assert_allclose(y.cpu().numpy(), conv_ref(x, w, b, relu), rtol=0, atol=2e-5)
 
 
+@pytest.mark.parametrize("variant,Cin", [("dma16", 32), ("dma8", 8), ("vec", 12), ("scalar", 16), ("cl", 16)])
+def test_conv3_tile_map_with_a_short_last_group(tspn, device, variant, Cin):
+    """The workgroup-to-tile map of the three kernels of tspn_conv3.hip (BM = BN = 128, GM = 8): M = 9 * 128 rows are two
+    groups of weight panels, the second a single panel, and 5 * 43 = 215 columns are two column tiles (the second partial,
+    sequences of 43 frames across the tile edge): a grid of 18 workgroups (> 8, 18 % 8 = 2).  Every output element against
+    the float64 conv; a tile computed twice or not at all shows as garbage in the freshly allocated output."""
+    B, T, M = 5, 43, 9 * 128
+    x = tspn.hashrng.uniform(403, f"x{Cin}", (B, Cin, T), -1, 1)
+    w = tspn.hashrng.normal(403, f"w{Cin}", (M, Cin, 3), std=0.1)
+    b = tspn.hashrng.normal(403, f"b{Cin}", (M,), std=0.1)
+    packed = tspn.ops.pack_conv3(t(w).to(device))
+    if variant == "cl":
+        y = tspn.ops.conv3_tc(t(x).permute(0, 2, 1).contiguous().to(device), packed, t(b).to(device), relu=True)
+    else:
+        if variant == "scalar":
+            packed = off4(packed, device)
+        assert conv3_variant(Cin, M, packed) == variant
+        y = tspn.ops.conv3(t(x).to(device), packed, t(b).to(device), relu=True)
+    assert tuple(y.shape) == (B, M, T)
+    np.testing.assert_allclose(y.cpu().numpy(), conv_ref(x, w, b, True), rtol=0, atol=2e-5)
+
+
 def test_conv3_channels_last_refuses_unaligned(tspn, device):
     """tspn_conv3_tc_f32 stages x and the weights in 16-byte pieces: a view at a 4-byte offset is refused."""
     x = torch.zeros(2, 5, 16, device=device)
@@ -191,6 +213,8 @@ def fused_weights(tspn, D, A):
 @pytest.mark.parametrize("D,T,A,canonical,aligned", [
     (16, 30, 4, True, True),     # channels-last conv, ldy = 32 (T % 4 == 2), pairgrid4<8>
     (16, 32, 4, True, True),     # ldy = T, pairgrid4<8>
+    (16, 148, 4, True, True),    # pairgrid4<8> past one round of its map: PG_T = 32 -> 5 frame blocks x 2 videos = 10 groups
+                                 # (10 % 8 = 2: the last round has two groups, six XCDs' workgroups return early)
     (16, 33, 4, True, True),     # odd T: ldy = T, heads_pairgrid_kernel<false>
     (32, 150, 5, True, True),    # ldy = 152, H = 15: heads_pairgrid3_kernel
     (16, 34, 4, False, True),    # indexed pair stage, heads_kernel<1, true>
@@ -256,6 +280,21 @@ def test_heads_pairgrid_bf16_small_and_big(tspn, device, N, T, C):
 
 
 # --------------------------------------------------------------------------------- gathers and means
+@pytest.mark.parametrize("B,N,T,grid", [(3, 12, 33, 36), (3, 8, 49, 12), (1, 33, 17, 18)])
+def test_heads_pairgrid_bf16_grids_the_xcd_remap_does_not_divide(tspn, device, B, N, T, grid):
+    """heads_pairgrid_bf16_kernel numbers its B x nfb x nsb x nsb workgroups through the XCD remap (HP_FB = 16 frames,
+    8 subjects per block for N <= 12, else 16): <4, 8, 2> with 3 * 3 * 2 * 2 = 36 and 3 * 4 * 1 * 1 = 12 workgroups,
+    <8, 16, SW> with 1 * 2 * 3 * 3 = 18 -- each larger than 8 and no multiple of 8.  Every element against float64."""
+    sblk = 16 if N > 12 else 8
+    assert B * -(-T // 16) * (-(-N // sblk)) ** 2 == grid and grid > 8 and grid % 8
+    C = 32
+    y = t(tspn.hashrng.normal(431, "y", (B * N, T, 2 * C), std=1.0))
+    hw = t(tspn.hashrng.normal(431, "hw", (12, C), std=0.1)).to(torch.bfloat16).float()
+    hb = t(tspn.hashrng.normal(431, "hb", (12,), std=0.1))
+    out = tspn.ops.heads_pairgrid_bf16(y.to(device), B, N, tspn.ops.pack_heads_bf16(hw.to(device)), hb.to(device), 12)
+    np.testing.assert_allclose(out.cpu().numpy(), heads_bf16_ref64(y, B, N, hw, hb).numpy(), rtol=0, atol=3e-5)
+
+
 @pytest.mark.parametrize("T", [160, 161])
 def test_pair_gather_rows_form_and_32x32_form(tspn, device, T):
     """transpose_gather_rows_kernel (D % 64 == 0, T <= TG_TMAX = 160, 16-byte aligned) and transpose_gather_kernel

@@ -18,7 +18,10 @@ def t(x):
 @pytest.mark.parametrize("NB,H,W,Cin,Cout,k,stride,pad", [
     (2, 7, 7, 16, 32, 1, 1, 0), (3, 14, 14, 32, 64, 1, 2, 0), (2, 7, 7, 32, 48, 3, 1, 1),
     (1, 9, 11, 16, 132, 3, 2, 1), (5, 7, 7, 64, 256, 3, 1, 1), (40, 7, 7, 48, 96, 1, 1, 0),
-    (1, 1, 1, 16, 4, 1, 1, 0), (2, 5, 6, 16, 20, 3, 1, 0)])
+    (1, 1, 1, 16, 4, 1, 1, 0), (2, 5, 6, 16, 20, 3, 1, 0),
+    # tile map of both kernels: BM = BN = 128, GM = 4: Cout = 544 gives 5 row tiles = two groups, the second a single
+    # (partial) panel; 3 * 7 * 7 = 147 pixels = 2 pixel tiles; grid 10 (> 8, 10 % 8 = 2)
+    (3, 7, 7, 16, 544, 3, 1, 1)])
 @pytest.mark.parametrize("fused", [False, True])
 def test_conv2d_nhwc_vs_torch(tspn, device, NB, H, W, Cin, Cout, k, stride, pad, fused):
     """Implicit-GEMM conv2d on channels-last tensors == F.conv2d (float64) for 1x1 / 3x3, stride 1 / 2, with
@@ -137,7 +140,11 @@ def test_res5_roi_head_errors(tspn, device):
 
 @pytest.mark.parametrize("NB,H,W,Cin,Cout,k,stride,pad", [
     (2, 7, 7, 64, 32, 1, 1, 0), (3, 14, 14, 128, 64, 1, 2, 0), (2, 7, 7, 64, 96, 3, 1, 1),
-    (1, 9, 11, 64, 160, 3, 2, 1), (5, 7, 7, 192, 256, 3, 1, 1), (40, 7, 7, 64, 128, 1, 1, 0), (1, 1, 1, 64, 32, 1, 1, 0)])
+    (1, 9, 11, 64, 160, 3, 2, 1), (5, 7, 7, 192, 256, 3, 1, 1), (40, 7, 7, 64, 128, 1, 1, 0), (1, 1, 1, 64, 32, 1, 1, 0),
+    # tile map: BN = 128 pixels, BM = 128 mi rows, GM = 4; 147 pixels = 2 pixel tiles and 5 row tiles (two groups, the second
+    # a single panel) give a grid of 10 (> 8, 10 % 8 = 2) in <1, true> (Cout = 544, 3x3), <1, false> (Cout = 544, 1x1) and
+    # <2, true> (Cout = 5 * 256)
+    (3, 7, 7, 64, 544, 3, 1, 1), (3, 7, 7, 64, 544, 1, 1, 0), (3, 7, 7, 64, 1280, 3, 1, 1)])
 @pytest.mark.parametrize("fused", [False, True])
 def test_conv2d_nhwc_bf16_vs_fp64(tspn, device, NB, H, W, Cin, Cout, k, stride, pad, fused):
     """bf16-operand conv2d: exact products, fp32 accumulation (vs float64 on the same bf16 operands), one
@@ -397,6 +404,29 @@ def test_bottleneck_tail_fused_bit_identical_to_two_convs(tspn, device, CM, NB, 
     err = (got.cpu().double() - ref).abs()
     scale = float(ref.abs().max())
     assert float(err.max()) <= 4 * 2.0 ** -8 * scale and float((err <= 2.0 ** -8 * ref.abs() + 1e-6).double().mean()) > 0.97
+
+
+@pytest.mark.parametrize("CM,NB,H,W", [(64, 3, 7, 61), (128, 1, 13, 127)])
+def test_bottleneck_tail_narrow_widths_on_a_ragged_grid_write_every_tile(tspn, device, CM, NB, H, W):
+    """bottleneck_bf16_kernel<64> and <128> on a grid that the XCD remap does not divide evenly: BN = 128 pixels per tile,
+    3 * 7 * 61 = 1281 pixels = 11 tiles (11 % 8 = 3) and 13 * 127 = 1651 pixels = 13 tiles (13 % 8 = 5); rows of 61 and 127
+    pixels make tiles cross rows and images.  The output starts as NaN, so a tile that no workgroup computes shows; every
+    element is compared, bit for bit, with the two-launch chain."""
+    h1 = tspn.hashrng.uniform(96, "h1", (NB, H, W, CM), 0, 1)
+    res = tspn.hashrng.uniform(96, "res", (NB, H, W, 4 * CM), -1, 1)
+    w2 = tspn.hashrng.normal(96, "w2", (CM, CM, 3, 3), std=float(np.sqrt(2.0 / (9 * CM))))
+    w3 = tspn.hashrng.normal(96, "w3", (4 * CM, CM, 1, 1), std=float(np.sqrt(2.0 / CM)))
+    b2 = tspn.hashrng.normal(96, "b2", (CM,), std=0.1)
+    b3 = tspn.hashrng.normal(96, "b3", (4 * CM,), std=0.1)
+    d = lambda a, dt=None: (t(a).to(device) if dt is None else t(a).to(device).to(dt))   # noqa: E731
+    f2, f3 = tspn.ops.pack_conv2d_frag_bf16(d(w2)), tspn.ops.pack_conv2d_frag_bf16(d(w3))
+    h1d, resd = d(h1, torch.bfloat16), d(res, torch.bfloat16)
+    h2 = tspn.ops.conv2d_nhwc_bf16(h1d, f2, (3, 3), 1, 1, bias=d(b2), relu=True)
+    want = tspn.ops.conv2d_nhwc_bf16(h2, f3, (1, 1), 1, 0, bias=d(b3), residual=resd, relu=True)
+    out = torch.full((NB, H, W, 4 * CM), float("nan"), dtype=torch.bfloat16, device=device)
+    tspn.ops.bottleneck_tail_bf16(h1d, f2, d(b2), f3, d(b3), resd, out=out)
+    assert not bool(torch.isnan(out).any()), "a tile was left unwritten"
+    assert torch.equal(out, want), f"max diff {float((out.float() - want.float()).abs().max())}"
 
 
 @pytest.mark.parametrize("CM,NB,H,W", [(64, 2, 9, 13), (128, 1, 16, 16), (64, 1, 1, 1), (128, 2, 30, 17), (64, 3, 4, 30),

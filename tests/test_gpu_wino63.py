@@ -28,7 +28,11 @@ def conv_ref(x_tc, w, b, relu):
 
 @pytest.mark.parametrize("B,Cin,T,M", [(1, 32, 1, 32), (2, 32, 5, 32), (3, 64, 30, 128), (5, 96, 33, 160),
                                        (7, 64, 150, 64), (2, 160, 257, 288), (40, 32, 30, 96), (3, 32, 7, 32),
-                                       (33, 128, 13, 128), (1, 32, 6, 32), (9, 256, 150, 256), (70, 32, 6, 32)])
+                                       (33, 128, 13, 128), (1, 32, 6, 32), (9, 256, 150, 256), (70, 32, 6, 32),
+                                       # tile map: BM = 128 rows, SWG = 64 sextets, GM = 4: M = 5 * 128 gives two groups,
+                                       # the second a single panel; 27 * ceil(31 / 6) = 162 sextets = 3 column tiles;
+                                       # grid 15 (> 8, 15 % 8 = 7)
+                                       (27, 32, 31, 640)])
 @pytest.mark.parametrize("relu", [False, True])
 def test_conv3_winograd63_vs_fp64(tspn, device, B, Cin, T, M, relu):
     x = tspn.hashrng.uniform(61, "x", (B, T, Cin), -1, 1)
