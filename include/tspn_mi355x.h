@@ -605,7 +605,11 @@ int tspn_conv2d_nhwc_bf16(const uint16_t* x, int64_t NB, int64_t H, int64_t W, i
  *   out[R,OP,OP,C]; sampling_ratio 0 = adaptive grid ceil(roi size / P) (detectron2's POOLER_SAMPLING_RATIO 0);
  *   aligned != 0 = the half-pixel-corrected form (ROIAlignV2).  `bin_stride` >= 1: only the bins (bs i, bs j) of the
  *   P x P grid are produced, OP = ceil(P / bs) -- with bs = 2 exactly the bins the stride-2 1x1 convolutions of res5's
- *   first block read (stride_in_1x1), a quarter of the work and of the output.  Needs C % 4 == 0. */
+ *   first block read (stride_in_1x1), a quarter of the work and of the output.  Needs C % 4 == 0.
+ *   The map index (rois[r][0], truncated towards zero) is CLAMPED to [0, NF): an index below 0 reads map 0, an index
+ *   of NF or more reads map NF - 1 -- never memory outside feat (tests/test_gpu_frontend_edges.py pins it).  The
+ *   adaptive grid makes a workgroup's trip count grow with the box (ceil(roi size / P) samples per bin and axis): box
+ *   coordinates are the caller's to keep finite and of the image's order of magnitude. */
 int tspn_roi_align_nhwc_f32(const float* feat, int64_t NF, int64_t H, int64_t W, int64_t C,
                             const float* rois, int64_t R, int64_t P, float spatial_scale,
                             int sampling_ratio, int aligned, int bin_stride, float* out, void* stream);
@@ -620,7 +624,7 @@ int tspn_roi_align_nhwc_f32_bf16out(const float* feat, int64_t NF, int64_t H, in
 
 /* max_pool2d(k, stride, pad) on a channels-last fp32 map x[NB,H,W,C] -> out[NB,OH,OW,C], fp32 (out_bf16 == 0)
  * or bf16 (rounded once); padding positions do not take part.  detectron2 BasicStem uses 3 / 2 / 1.
- * Needs C % 4 == 0. */
+ * Needs C % 4 == 0.  A window larger than the padded map (H + 2 pad < k or W + 2 pad < k) has no output: TSPN_EINVAL. */
 int tspn_max_pool_nhwc_f32(const float* x, int64_t NB, int64_t H, int64_t W, int64_t C, int64_t k,
                            int64_t stride, int64_t pad, void* out, int out_bf16, void* stream);
 

@@ -25,13 +25,12 @@ __all__ = ["roi_align_nhwc", "frozen_bn", "bottleneck_block", "res5_roi_head", "
 BN_EPS = 1e-5
 
 
-def _bilinear(fmap, y, x):
-    """ROIAlign_cpu.cpp:pre_calc_for_bilinear_interpolate (one sample point), float32 arithmetic.
-    fmap [H,W,C] float32 numpy.  Returns [C] float32."""
+def _bilinear(fmap, y, x, f=np.float32):
+    """ROIAlign_cpu.cpp:pre_calc_for_bilinear_interpolate (one sample point), arithmetic in `f` (float32, the
+    kernel's; float64 for the high-precision form).  fmap [H,W,C] numpy of type `f`.  Returns [C] of type `f`."""
     H, W, _ = fmap.shape
-    f = np.float32
     if y < -1.0 or y > H or x < -1.0 or x > W:
-        return np.zeros(fmap.shape[2], dtype=np.float32)
+        return np.zeros(fmap.shape[2], dtype=f)
     y = max(f(y), f(0))
     x = max(f(x), f(0))
     yl, xl = int(y), int(x)
@@ -48,20 +47,21 @@ def _bilinear(fmap, y, x):
     ly, lx = f(y - f(yl)), f(x - f(xl))
     hy, hx = f(f(1) - ly), f(f(1) - lx)
     w1, w2, w3, w4 = f(hy * hx), f(hy * lx), f(ly * hx), f(ly * lx)
-    return (w1 * fmap[yl, xl] + w2 * fmap[yl, xh] + w3 * fmap[yh, xl] + w4 * fmap[yh, xh]).astype(np.float32)
+    return (w1 * fmap[yl, xl] + w2 * fmap[yl, xh] + w3 * fmap[yh, xl] + w4 * fmap[yh, xh]).astype(f)
 
 
-def roi_align_nhwc(feat, rois, output_size, spatial_scale, sampling_ratio=0, aligned=True):
+def roi_align_nhwc(feat, rois, output_size, spatial_scale, sampling_ratio=0, aligned=True, dtype=np.float32):
     """detectron2 ROIAlign (layers/csrc/ROIAlign/ROIAlign_cpu.cpp:ROIAlignForward) on a channels-last map.
     feat [NF,H,W,C], rois [R,5] = (map index, x1, y1, x2, y2) -> [R,P,P,C]; float32 arithmetic in the
-    kernel's order (loops: small cases only)."""
-    feat = np.asarray(feat, dtype=np.float32)
-    rois = np.asarray(rois, dtype=np.float32)
-    f = np.float32
+    kernel's order (loops: small cases only).  `dtype=np.float64`: the same steps in float64 on the same float32
+    operands (map, rois and scale are still read as float32 VALUES), returned as float64."""
+    f = np.dtype(dtype).type
+    feat = np.asarray(feat, dtype=np.float32).astype(f)
+    rois = np.asarray(rois, dtype=np.float32).astype(f)
     P = int(output_size)
     R = rois.shape[0]
-    out = np.zeros((R, P, P, feat.shape[3]), dtype=np.float32)
-    scale = f(spatial_scale)
+    out = np.zeros((R, P, P, feat.shape[3]), dtype=f)
+    scale = f(np.float32(spatial_scale))
     off = f(0.5) if aligned else f(0)
     for r in range(R):
         fmap = feat[int(rois[r, 0])]
@@ -75,12 +75,12 @@ def roi_align_nhwc(feat, rois, output_size, spatial_scale, sampling_ratio=0, ali
         count = f(max(gh * gw, 1))
         for ph in range(P):
             for pw in range(P):
-                acc = np.zeros(feat.shape[3], dtype=np.float32)
+                acc = np.zeros(feat.shape[3], dtype=f)
                 for iy in range(gh):
                     y = f(f(sh + f(f(ph) * bin_h)) + f(f(f(iy) + f(0.5)) * bin_h) / f(gh))
                     for ix in range(gw):
                         x = f(f(sw + f(f(pw) * bin_w)) + f(f(f(ix) + f(0.5)) * bin_w) / f(gw))
-                        acc = acc + _bilinear(fmap, y, x)
+                        acc = acc + _bilinear(fmap, y, x, f)
                 out[r, ph, pw] = acc / count
     return torch.from_numpy(out)
 

@@ -475,8 +475,9 @@ extern "C" int tspn_max_pool_nhwc_bf16(const uint16_t* x, int64_t NB, int64_t H,
                                        int64_t stride, int64_t pad, uint16_t* out, void* stream) {
   TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0 && 2 * pad <= k, TSPN_EINVAL,
                "tspn_max_pool_nhwc_bf16: bad sizes");
+  // (a window larger than the padded map: the truncating division below would still give one output pixel)
+  TSPN_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k, TSPN_EINVAL, "tspn_max_pool_nhwc_bf16: empty output");
   const int64_t OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
-  TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "tspn_max_pool_nhwc_bf16: empty output");
   if (NB == 0) return TSPN_OK;
   TSPN_REQUIRE(x && out, TSPN_EINVAL, "tspn_max_pool_nhwc_bf16: null pointer");
   TSPN_REQUIRE(C % 8 == 0 && tspn::aligned16(x) && tspn::aligned16(out),
