@@ -562,7 +562,9 @@ int tspn_temporal_encoder_heads_bf16(const uint16_t* x_tc, int64_t P, int64_t C,
  * tspn_conv2d_nhwc_f32: out[NB,OH,OW,Cout] = act( conv(x[NB,H,W,Cin]) + bias[Cout] + residual[NB,OH,OW,Cout] ),
  *   zero padding `pad`, `stride`, OH = (H + 2 pad - KH) / stride + 1; bias / residual may be NULL;
  *   relu != 0 applies max(.,0).  BatchNorm is folded into (packed, bias) by the caller.  Implicit GEMM
- *   on fp32 MFMA.  Needs Cin % 16 == 0, Cout % 4 == 0, 16-byte aligned tensors (else TSPN_EUNSUPPORTED). */
+ *   on fp32 MFMA.  Needs Cin % 16 == 0, Cout % 4 == 0, 16-byte aligned tensors (else TSPN_EUNSUPPORTED).
+ *   A kernel larger than the padded map (H + 2 pad < KH or W + 2 pad < KW) has no output: TSPN_EINVAL, whatever the
+ *   stride -- in this entry and in tspn_conv2d_nhwc_frag_f32, tspn_conv2d_nhwc_cin4_f32 and tspn_conv2d_nhwc_bf16. */
 int tspn_pack_conv2d_f32(const float* w, int64_t Cout, int64_t Cin, int64_t KH, int64_t KW,
                          float* packed, void* stream);
 int tspn_conv2d_nhwc_f32(const float* x, int64_t NB, int64_t H, int64_t W, int64_t Cin,
@@ -572,7 +574,8 @@ int tspn_conv2d_nhwc_f32(const float* x, int64_t NB, int64_t H, int64_t W, int64
 /* Fast variant for Cout % 32 == 0 (the res5 widths): FRAGMENT-MAJOR weights
  *   frag[Cout/32][KH*KW][Cin/16][64 lanes = 32 kh + li][8 = (g, r)] = w[32 mb + li][16 c + 4 g + 2 kh + r][tap]
  * loaded straight into MFMA operand registers (each wave owns 32 output rows; only x goes through LDS).
- * Same arguments and result as tspn_conv2d_nhwc_f32 (bit-identical: same contraction order). */
+ * Same arguments, refusals (empty output: TSPN_EINVAL) and result as tspn_conv2d_nhwc_f32 (bit-identical: same
+ * contraction order). */
 int tspn_pack_conv2d_frag_f32(const float* w, int64_t Cout, int64_t Cin, int64_t KH, int64_t KW,
                               float* frag, void* stream);
 int tspn_conv2d_nhwc_frag_f32(const float* x, int64_t NB, int64_t H, int64_t W, int64_t Cin,
@@ -581,7 +584,8 @@ int tspn_conv2d_nhwc_frag_f32(const float* x, int64_t NB, int64_t H, int64_t W, 
                               void* stream);
 /* Stem form for Cin <= 4 (RGB): x[NB,H,W,4] (channels zero-padded to 4); one K chunk = four taps x 4 channels,
  * so a 7x7 stem runs 13 chunks instead of 49 on 16-channel padding.
- *   frag[Cout/32][ceil(KH*KW/4)][64 lanes][8 = (g, r)] = w[32 mb + li][2 kh + r][tap = 4 c + g] (0 beyond Cin / taps) */
+ *   frag[Cout/32][ceil(KH*KW/4)][64 lanes][8 = (g, r)] = w[32 mb + li][2 kh + r][tap = 4 c + g] (0 beyond Cin / taps)
+ * H + 2 pad < KH or W + 2 pad < KW: no output, TSPN_EINVAL. */
 int tspn_pack_conv2d_frag_cin4_f32(const float* w, int64_t Cout, int64_t Cin, int64_t KH, int64_t KW,
                                    float* frag, void* stream);
 int tspn_conv2d_nhwc_cin4_f32(const float* x, int64_t NB, int64_t H, int64_t W, const float* frag,
@@ -593,7 +597,7 @@ int tspn_conv2d_nhwc_cin4_f32(const float* x, int64_t NB, int64_t H, int64_t W, 
  * once into  frag[Cout/32][Cin/64][KH*KW][4 ks][64 lanes = 32 kh + li][8 j] =
  * bf16(w[32 mb + li][64 c + 16 ks + 8 kh + j][tap])  (ABI 5: channel chunk outermost -- the contraction runs chunk by
  * chunk, all taps of a chunk in a row, in tspn_conv2d_nhwc_bf16 and in tspn_bottleneck_tail_bf16 alike).
- * Needs Cin % 64 == 0, Cout % 32 == 0. */
+ * Needs Cin % 64 == 0, Cout % 32 == 0.  H + 2 pad < KH or W + 2 pad < KW: no output, TSPN_EINVAL. */
 int tspn_pack_conv2d_frag_bf16(const float* w, int64_t Cout, int64_t Cin, int64_t KH, int64_t KW,
                                uint16_t* frag, void* stream);
 int tspn_conv2d_nhwc_bf16(const uint16_t* x, int64_t NB, int64_t H, int64_t W, int64_t Cin,

@@ -452,6 +452,8 @@ extern "C" int tspn_conv2d_nhwc_bf16(const uint16_t* x, int64_t NB, int64_t H, i
   TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0,
                TSPN_EINVAL, "tspn_conv2d_nhwc_bf16: bad sizes");
   TSPN_REQUIRE(KH * KW <= 64, TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_bf16: at most 64 taps");
+  // (a kernel larger than the padded map: the truncating division below would still give one output pixel)
+  TSPN_REQUIRE(H + 2 * pad >= KH && W + 2 * pad >= KW, TSPN_EINVAL, "tspn_conv2d_nhwc_bf16: empty output");
   const int64_t OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
   TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "tspn_conv2d_nhwc_bf16: empty output");
   if (NB == 0) return TSPN_OK;

@@ -1166,7 +1166,7 @@ def _out_bf16(out, shape, device, who):
 
 
 def pack_conv2d_frag_bf16(weight):
-    """fp32 nn.Conv2d weight [Cout,Cin,KH,KW] -> bf16 fragment-major [Cout/32, KH*KW, Cin/64, 4, 64, 8]
+    """fp32 nn.Conv2d weight [Cout,Cin,KH,KW] -> bf16 fragment-major [Cout/32, Cin/64, KH*KW, 4, 64, 8]
     (tspn_pack_conv2d_frag_bf16; rounded once, to nearest even).  Needs Cout % 32 == 0, Cin % 64 == 0."""
     _dev(weight, "conv2d weight")
     if weight.dim() != 4:
@@ -1439,6 +1439,8 @@ def conv2d_nhwc_cin4(x, frag, kernel_size, stride=1, padding=0, bias=None, relu=
         raise ValueError("conv2d_nhwc_cin4: x must be [NB,H,W,4] and frag = pack_conv2d_frag_cin4(weight)")
     Cout = frag.shape[0] * 32
     OH, OW = (H + 2 * padding - KH) // stride + 1, (W + 2 * padding - KW) // stride + 1
+    if OH <= 0 or OW <= 0:
+        raise ValueError("conv2d_nhwc_cin4: empty output")
     if bias is not None:
         _dev(bias, "bias")
     out = torch.empty((NB, OH, OW, Cout), dtype=torch.float32, device=x.device)

@@ -130,6 +130,27 @@ def test_abi_argument_validation_without_gpu(tspn):
     assert lib.tspn_forward_fused_f32(ctypes.byref(d), None) == tspn._abi.TSPN_EUNSUPPORTED
 
 
+def test_conv_entries_refuse_a_kernel_larger_than_the_padded_map_without_gpu(tspn):
+    """(H + 2 pad - KH) / stride + 1 is 1 in C for -stride < H + 2 pad - KH < 0: the four conv entries must refuse such a
+    geometry as "empty output" before they look at a pointer (the cases of tests/test_gpu_conv2d_edges.py)."""
+    lib = tspn._abi.lib()
+    for H, W, KH, KW, stride, pad in [(1, 1, 2, 2, 2, 0), (2, 1, 3, 3, 2, 0), (1, 4, 1, 8, 7, 1)]:
+        assert H + 2 * pad < KH or W + 2 * pad < KW
+        assert (H + 2 * pad - KH) // stride + 1 <= 0 or (W + 2 * pad - KW) // stride + 1 <= 0
+        calls = {
+            "tspn_conv2d_nhwc_f32": (None, 2, H, W, 16, None, 32, KH, KW, stride, pad, None, None, 0, None, None),
+            "tspn_conv2d_nhwc_frag_f32": (None, 2, H, W, 16, None, 32, KH, KW, stride, pad, None, None, 0, None, None),
+            "tspn_conv2d_nhwc_cin4_f32": (None, 2, H, W, None, 32, KH, KW, stride, pad, None, 0, None, None),
+            "tspn_conv2d_nhwc_bf16": (None, 2, H, W, 64, None, 32, KH, KW, stride, pad, None, None, 0, None, None),
+        }
+        for name, args in calls.items():
+            assert getattr(lib, name)(*args) == tspn._abi.TSPN_EINVAL, (name, H, W, KH, KW)
+            assert (name + ": empty output").encode() in lib.tspn_last_error(), (name, lib.tspn_last_error())
+    # a geometry with an output goes on to the pointer check
+    assert lib.tspn_conv2d_nhwc_f32(None, 2, 2, 2, 16, None, 32, 2, 2, 2, 0, None, None, 0, None, None) == tspn._abi.TSPN_EINVAL
+    assert b"null pointer" in lib.tspn_last_error()
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the GPU-less behaviour")
 def test_no_cpu_fallback(tspn):
     model = tspn.BaseModel(cases.baseline_cfg())
