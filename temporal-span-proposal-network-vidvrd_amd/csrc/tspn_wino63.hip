@@ -448,7 +448,7 @@ constexpr int F_ST = 4 * 2 * 256 * 16;         // one k-step (16 channels) of Wh
 constexpr int F_NST = 4;                       // ring of stages, filled three k-steps ahead by LDS-DMA
 constexpr size_t F_SMEM = (size_t)F_NST * F_ST;
 constexpr size_t F_SMEM_ALL = F_SMEM + 2 * 256 * sizeof(int);   // + the exponent table of the unscale
-static_assert(TSPN_WINO63_GM > 0 && TSPN_WINO63_GM < 256, "the contraction's GM argument carries the tail split above bit 7");
+static_assert(TSPN_WINO63_GM > 0 && TSPN_WINO63_GM < 256, "the contraction's GM argument carries the tail split and the piece form above bit 7");
 constexpr size_t F_PARK_PER_TILE = (size_t)7 * F_THREADS * 128 * sizeof(float);   // points 0..6 of a tile, fp32
 
 // power-of-two exponent e with max * 2^e in [2^14, 2^15); 0 for a zero or non-finite maximum (a non-finite value then
@@ -609,7 +609,43 @@ __global__ __launch_bounds__(256) void wino63_input_transform_kernel(
 // sextets of each V row, so a stage is 16 + 4 WN DMA pieces of 1 KB.  An output element sees the same operands in the
 // same order whichever shape computes it (a 32x32x16 MFMA result depends on the element's own row and column only),
 // so y does not depend on how the launch was cut.  `sub` = which 64 WN sextets of the 256-sextet tile `tile`.
-template <int WN>
+//
+// The k-step is software-pipelined the way the ring of conv3_bf16_big_kernel is; its three product groups play the
+// role of that kernel's three taps.  For k-step g (ring stage g & 3; fragment registers ah, al, bh, bl):
+//   top of g:     ah, bh of g are already in registers
+//   group ah.bh   with the reads of bl, al of g between its MFMAs
+//   wait for this wave's DMA pieces of g + 1, one bare s_barrier, issue the DMA pieces of g + 3
+//   group ah.bl
+//   group al.bh   with the reads of ah, bh of g + 1 between its MFMAs (ah is dead after the second group; bh is live,
+//                 so there are two bh sets, alternated over an unroll by two: nk = Cin / 16 is even)
+// The order of the products of an output element is what it was (per k-step hh, hl, lh; k ascending; points 0 .. 7).
+// The ring runs on across the points; at a point's end the unscale, the parking stores and the zeroing sit between
+// the third group and the next k-step's first, with that k-step's ah, bh already in registers.
+//   The barrier of k-step g, B(g), orders both directions of the ring:
+//   * stage (g + 3) & 3 = (g - 1) & 3 is refilled only after B(g).  Its last reads are al, bl of g - 1 (group 1 of
+//     g - 1) and ah, bh of g (group 3 of g - 1); every wave has USED ah, bh of g in group 1 of g before it reaches
+//     B(g), and LDS reads return in order, so all of them are complete.
+//   * a wave reads stage g + 1 only after B(g), and reaches B(g) only after vmcnt says its own pieces of g + 1 landed.
+//   The counted wait in front of B(g): the wave's DMA queue holds, oldest first, its pieces of g + 1 (issued in k-step
+//   g - 2) and of g + 2 (issued in k-step g - 1); VMEM returns in order, so "at most n outstanding" with n = this
+//   wave's pieces per stage means g + 1 has landed while g + 2 may still fly: vmcnt(n), and vmcnt(0) for the last two
+//   k-steps, behind which nothing was issued.  Before the loop: three stages issued, vmcnt(2 n) lands stage 0.  The
+//   parking stores and the loads of the unscale are younger than every piece in flight when they issue, so they only
+//   make a counted wait stricter.
+//   The two waves of a SIMD (w and w + 4) issue their pieces at different points of the k-step where the tile is the
+//   full one: wm == 0 right behind the barrier, the other behind the second group.
+//   The unscale keeps its own __syncthreads() (8 per tile, each drains the DMA queue once): ordering the exponent
+//   table by B(g) instead needs its global loads in front of the pieces of g + 2, a k-step earlier, for 8 of 1024
+//   k-steps.
+//
+// DMA pieces, BUF = true: buffer loads (one SGPR descriptor per operand based at the current point's slab of Wp / Vh,
+// a fixed 32-bit lane offset per piece, a scalar offset that advances per k-step; the descriptors are re-based at a
+// point's start) -- the launcher picks it when a point's slab of either operand is below 2 GB.  BUF = false: 64-bit
+// pointers per lane, advanced per k-step.  Both land the same bytes in LDS.
+#ifndef TSPN_WINO63_F16X3_STAGGER
+#define TSPN_WINO63_F16X3_STAGGER 1
+#endif
+template <int WN, bool BUF>
 __device__ __forceinline__ void wino63_f16x3_tile(
     char* smem_raw, const _Float16* __restrict__ Vh, const int* __restrict__ Ve, const int16_t* __restrict__ Wp,
     const float* __restrict__ bias, float* __restrict__ y, float* __restrict__ park, int Cin, int T, int M, int nq,
@@ -619,6 +655,7 @@ __device__ __forceinline__ void wino63_f16x3_tile(
   constexpr int NP = 16 + 4 * WN;              // DMA pieces per stage: 16 of W, 4 WN of V
   constexpr int PW = (NP + 7) / 8;             // pieces per wave, at most
   constexpr bool EVEN = NP % 8 == 0;           // every wave issues PW pieces (else PW or PW - 1, by wave)
+  constexpr bool STAGGER = TSPN_WINO63_F16X3_STAGGER && WN == 4;
   const int m0 = tile_m * F_BM;
   const int64_t S0 = (int64_t)tile_n * F_BN + sub * BN;
 
@@ -628,41 +665,64 @@ __device__ __forceinline__ void wino63_f16x3_tile(
   const int wm = wave / WN, wn = wave % WN;
   const int li = lane & 31, kh = lane >> 5;
   const int ncg = Cin >> 3, nk = Cin >> 4;
-  const int G = NJ * nk;                             // k-steps of the whole workgroup (8 points)
+  const int G = NJ * nk;                             // k-steps of the whole workgroup (8 points): even, >= 16
 
   // DMA pieces of a stage (1 KB each), numbered p: p < 16 is W: region p >> 3 (Wh, Wl), channel group (p >> 2) & 1, rows
   // 64 (p & 3) + lane; p >= 16 is V, v = p - 16: region 2 + v / (2 WN) (Vh, Vl), channel group (v / WN) & 1, sextets
-  // 64 (v % WN) + lane.  Wave w issues pieces [w NP / 8, (w + 1) NP / 8).  Element offsets at k-step 0 of point 0, and
-  // the strides per k-step / point.
+  // 64 (v % WN) + lane.  Wave w issues pieces [w NP / 8, (w + 1) NP / 8).  A lane's element offset in the point's slab
+  // at k-step 0 (rows < M, sextets < nsp2 always: M % 256 == 0, nsp2 % 256 == 0), and the strides per k-step / point.
   const int p0 = wave * NP / 8;
   const int npw = EVEN ? PW : (wave + 1) * NP / 8 - p0;      // wave-uniform
-  const int16_t* src[PW];
-  int64_t kstride[PW], jstride[PW];
+  const int16_t* src[PW];                                    // pointer form: the lane's source at the next k-step to issue
+  unsigned voff[PW];                                         // buffer form: the lane's byte offset from that k-step's base
   int ldst[PW];                                              // byte offset of the piece in its stage
 #pragma unroll
   for (int i = 0; i < PW; ++i) {
     const int p = min(p0 + i, NP - 1);
+    int64_t el;
     if (p < 16) {
       const int region = p >> 3, cgi = (p >> 2) & 1, r = 64 * (p & 3) + lane;
-      src[i] = Wp + (((int64_t)region * ncg + cgi) * M + m0 + r) * 8;
-      kstride[i] = (int64_t)2 * M * 8;
-      jstride[i] = (int64_t)(2 * ncg + 1) * M * 8;
+      el = (((int64_t)region * ncg + cgi) * M + m0 + r) * 8;
+      src[i] = Wp + el;
       ldst[i] = p * 1024;
     } else {
       const int v = p - 16;
       const int region = v / (2 * WN), cgi = (v / WN) & 1, r = 64 * (v % WN) + lane;
-      src[i] = reinterpret_cast<const int16_t*>(Vh) + (((int64_t)region * ncg + cgi) * nsp2 + S0 + r) * 8;
-      kstride[i] = (int64_t)2 * nsp2 * 8;
-      jstride[i] = (int64_t)2 * ncg * nsp2 * 8;
+      el = (((int64_t)region * ncg + cgi) * nsp2 + S0 + r) * 8;
+      src[i] = reinterpret_cast<const int16_t*>(Vh) + el;
       ldst[i] = (2 + region) * 8192 + cgi * 4096 + (v % WN) * 1024;
     }
+    voff[i] = (unsigned)(el * 2);
   }
-  auto issue = [&](int g) {                          // k-step g (point g / nk) into ring stage g & 3
-    const int j = g / nk, k = g - j * nk;
-    char* dst = smem_raw + (g & 3) * F_ST;
+  // The next k-step to issue (wave-uniform): k-step ik of its point, into stage ist.  Buffer form: wbase / vbase are
+  // that k-step's 16 channels in the point's slab of Wp / Vh, and the descriptors are made from them at the issue, so
+  // the advance per k-step and the re-basing at a point's start are one scalar 64-bit add per operand.  (No range to
+  // check: every row and sextet of a tile exists; the descriptor is the unbounded one, the lane offsets stay below the
+  // slab's 2 GB.)
+  int ik = 0, ist = 0;
+  const char* wbase = reinterpret_cast<const char*>(Wp);
+  const char* vbase = reinterpret_cast<const char*>(Vh);
+  auto issue = [&]() {
+    char* dst = smem_raw + ist * F_ST;
 #pragma unroll
     for (int i = 0; i < PW; ++i)
-      if (EVEN || i < npw) glds16(src[i] + j * jstride[i] + k * kstride[i], dst + ldst[i]);
+      if (EVEN || i < npw) {
+        if (BUF) bglds16(buffer_rsrc_unbounded(p0 + i < 16 ? wbase : vbase), voff[i], 0, dst + ldst[i]);   // wave-uniform choice
+        else glds16(src[i], dst + ldst[i]);
+      }
+    ist = (ist + 1) & 3;
+    // bytes to the next k-step: 16 channels on, or from a point's last k-step to the next point's first (W: over the
+    // rest of the hi half, the lo half and the exponent slots; V: over the rest of the hi half and the lo half)
+    const bool wrap = ++ik == nk;
+    if (wrap) ik = 0;
+    const int64_t dw = (int64_t)M * (wrap ? 32 * nk + 48 : 32), dv = nsp2 * (wrap ? 32 * nk + 32 : 32);
+    if (BUF) {
+      wbase += dw;
+      vbase += dv;
+    } else {
+#pragma unroll
+      for (int i = 0; i < PW; ++i) src[i] = reinterpret_cast<const int16_t*>(reinterpret_cast<const char*>(src[i]) + (p0 + i < 16 ? dw : dv));
+    }
   };
   // all but the youngest `ahead` stages of this wave have landed (a wave's VMEM returns in order)
   auto wait_stages = [&](auto ahead_tag) {
@@ -704,65 +764,96 @@ __device__ __forceinline__ void wino63_f16x3_tile(
       }
   };
 
-  issue(0);
-  if (G > 1) issue(1);
-  if (G > 2) issue(2);
-  for (int g = 0; g < G; ++g) {
-    if (g + 2 < G) wait_stages(std::integral_constant<int, 2>{});
-    else if (g + 1 < G) wait_stages(std::integral_constant<int, 1>{});
+  f16x8 ah[MI], al[MI], bh[2][2], bl[2];            // bh[set]: the set of k-step g is g & 1
+  const int a_off = (kh * 256 + wm * (32 * MI) + li) * 16, b_off = (kh * 256 + wn * 64 + li) * 16;
+  auto read_hi = [&](int st, f16x8 (&bhn)[2]) {
+    const char* s = smem_raw + st * F_ST;
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) ah[mi] = *reinterpret_cast<const f16x8*>(s + a_off + mi * 512);
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) bhn[ni] = *reinterpret_cast<const f16x8*>(s + 16384 + b_off + ni * 512);
+  };
+  auto read_lo = [&](int st) {                       // bl first: the second group needs it, al only the third
+    const char* s = smem_raw + st * F_ST;
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni) bl[ni] = *reinterpret_cast<const f16x8*>(s + 24576 + b_off + ni * 512);
+#pragma unroll
+    for (int mi = 0; mi < MI; ++mi) al[mi] = *reinterpret_cast<const f16x8*>(s + 8192 + a_off + mi * 512);
+  };
+  auto group = [&](const f16x8 (&a)[MI], const f16x8 (&b)[2]) {
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[mi], b[ni], acc[mi][ni], 0, 0, 0);
+  };
+  auto point_end = [&](int j) {
+    unscale(j);
+    if (j < NJ - 1) {
+      // (these stores are younger than every DMA piece in flight, so the counted waits only get stricter)
+#pragma unroll
+      for (int mi = 0; mi < MI; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+          for (int eq = 0; eq < 4; ++eq) {
+            const f32x4 v = {acc[mi][ni][4 * eq], acc[mi][ni][4 * eq + 1], acc[mi][ni][4 * eq + 2], acc[mi][ni][4 * eq + 3]};
+            *reinterpret_cast<f32x4*>(my_park + ((int64_t)j * 32 + (mi * 2 + ni) * 4 + eq) * F_THREADS * 4) = v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[mi][ni][4 * eq + e] = 0.f;
+          }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  // one k-step; STEADY: k-steps g + 1 .. g + 3 exist (no conditions inside, so the interleave hints see one block)
+  auto kstep = [&](int g, f16x8 (&bc)[2], f16x8 (&bn)[2], auto steady_tag) {
+    constexpr bool STEADY = decltype(steady_tag)::value;
+    // n MFMAs, then r fragment reads (the full tile: 8 MFMAs and 6 reads per interleaved group)
+#define TSPN_MR(NM, NR)                                \
+  __builtin_amdgcn_sched_group_barrier(0x008, NM, 0);  \
+  __builtin_amdgcn_sched_group_barrier(0x100, NR, 0);
+    group(ah, bc);
+    read_lo(g & 3);
+    if (WN == 4) { TSPN_MR(1, 1) TSPN_MR(1, 1) TSPN_MR(1, 1) TSPN_MR(1, 1) TSPN_MR(1, 1) TSPN_MR(1, 1) TSPN_MR(2, 0) }
+    __builtin_amdgcn_sched_barrier(0);
+    if (STEADY || g + 2 < G) wait_stages(std::integral_constant<int, 1>{});   // g + 2 may still fly; g + 1 has landed
     else wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();                    // B(g): stage g + 1 landed for every wave; stage g - 1 is read out
     __builtin_amdgcn_sched_barrier(0);
-    __builtin_amdgcn_s_barrier();                   // stage g landed for every wave; stage g - 1 is read out
+    const bool more = STEADY || g + 3 < G;
+    if (more && (!STAGGER || wm == 0)) issue();      // k-step g + 3 into stage (g - 1) & 3
     __builtin_amdgcn_sched_barrier(0);
-    if (g + 3 < G) issue(g + 3);
+    group(ah, bl);
     __builtin_amdgcn_sched_barrier(0);
-    const char* st = smem_raw + (g & 3) * F_ST;
-    f16x8 ah[MI], al[MI], bh[2], bl[2];
-#pragma unroll
-    for (int mi = 0; mi < MI; ++mi) {
-      const int off = (kh * 256 + wm * (32 * MI) + mi * 32 + li) * 16;
-      ah[mi] = *reinterpret_cast<const f16x8*>(st + off);
-      al[mi] = *reinterpret_cast<const f16x8*>(st + 8192 + off);
+    if (STAGGER && more && wm != 0) issue();
+    __builtin_amdgcn_sched_barrier(0);
+    group(al, bc);
+    if (STEADY || g + 1 < G) read_hi((g + 1) & 3, bn);
+    if (WN == 4 && STEADY) { TSPN_MR(2, 1) TSPN_MR(1, 1) TSPN_MR(1, 1) TSPN_MR(1, 1) TSPN_MR(1, 1) TSPN_MR(1, 1) TSPN_MR(1, 0) }
+#undef TSPN_MR
+    __builtin_amdgcn_sched_barrier(0);
+  };
+
+  issue();
+  issue();
+  issue();
+  wait_stages(std::integral_constant<int, 2>{});
+  __builtin_amdgcn_s_barrier();                      // stage 0 landed for every wave
+  __builtin_amdgcn_sched_barrier(0);
+  read_hi(0, bh[0]);
+  int g = 0, kc = 0, jc = 0;                         // k-step, its index in its point (even here), its point
+  auto pair = [&](auto steady_tag) {
+    kstep(g, bh[0], bh[1], steady_tag);
+    kstep(g + 1, bh[1], bh[0], steady_tag);
+    g += 2;
+    kc += 2;
+    if (kc == nk) {                                  // nk is even: a point ends behind an odd k-step only
+      point_end(jc);
+      kc = 0;
+      ++jc;
     }
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni) {
-      const int off = (kh * 256 + wn * 64 + ni * 32 + li) * 16;
-      bh[ni] = *reinterpret_cast<const f16x8*>(st + 16384 + off);
-      bl[ni] = *reinterpret_cast<const f16x8*>(st + 24576 + off);
-    }
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[mi], bl[ni], acc[mi][ni], 0, 0, 0);
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int mi = 0; mi < MI; ++mi) acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[mi], bh[ni], acc[mi][ni], 0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (g % nk == nk - 1) {
-      const int j = g / nk;
-      unscale(j);
-      if (j < NJ - 1) {
-        // (these stores are younger than every DMA piece in flight, so the counted waits above only get stricter)
-#pragma unroll
-        for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-          for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-            for (int eq = 0; eq < 4; ++eq) {
-              const f32x4 v = {acc[mi][ni][4 * eq], acc[mi][ni][4 * eq + 1], acc[mi][ni][4 * eq + 2], acc[mi][ni][4 * eq + 3]};
-              *reinterpret_cast<f32x4*>(my_park + ((int64_t)j * 32 + (mi * 2 + ni) * 4 + eq) * F_THREADS * 4) = v;
-#pragma unroll
-              for (int e = 0; e < 4; ++e) acc[mi][ni][4 * eq + e] = 0.f;
-            }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
+  };
+  while (g + 4 < G) pair(std::true_type{});
+  while (g < G) pair(std::false_type{});
 
   // ---- inverse transform + bias + store: acc holds M7; M0..M6 come back from the parking area (this lane's own
   // stores, complete before they are read)
@@ -823,7 +914,8 @@ __device__ __forceinline__ void wino63_f16x3_tile(
 }
 
 // The launch.  tiles_m x tiles_n tiles of 256 x 256, numbered in groups of GM row tiles x all sextet tiles.
-// `GM`: bits 0..7 the row tiles per group; bits 8..15 the tail split f (0 or 1: none).  With f = 2 or 4 the LAST
+// `GM`: bits 0..7 the row tiles per group; bits 8..15 the tail split f (0 or 1: none); bit 16 the piece form (1 = buffer
+// loads, 0 = 64-bit pointers).  With f = 2 or 4 the LAST
 // R = (gridDim.x - tiles) / (f - 1) tiles of that numbering are each cut into f tiles of 256 x 256 / f (sub-tiles), so
 // that the last, partly filled round of the launch keeps f times as many CUs busy:
 //   blocks [0, tiles - R)       one full tile each, XCD remap over these blocks
@@ -840,6 +932,7 @@ __global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
 
   const int f = max((GM >> 8) & 0xff, 1);
+  const bool buf = (GM >> 16) & 1;
   GM &= 0xff;
   const int tiles = tiles_m * tiles_n;
   const int nsplit = f > 1 ? ((int)gridDim.x - tiles) / (f - 1) : 0;     // R
@@ -855,12 +948,16 @@ __global__ __launch_bounds__(F_THREADS, 1) void conv3_wino63_kernel(
   }
   int tile_m, tile_n;
   grouped_tile(wg, GM, tiles_m, tiles_n, tile_m, tile_n);
-  if (bid < nfull)
-    wino63_f16x3_tile<4>(smem_raw, Vh, Ve, Wp, bias, y, park, Cin, T, M, nq, nsext, nsp2, tile_m, tile_n, tiles_n, 0, relu, ldy, vec2);
-  else if (f == 2)
-    wino63_f16x3_tile<2>(smem_raw, Vh, Ve, Wp, bias, y, park, Cin, T, M, nq, nsext, nsp2, tile_m, tile_n, tiles_n, sub, relu, ldy, vec2);
-  else
-    wino63_f16x3_tile<1>(smem_raw, Vh, Ve, Wp, bias, y, park, Cin, T, M, nq, nsext, nsp2, tile_m, tile_n, tiles_n, sub, relu, ldy, vec2);
+  auto tile = [&](auto wn_tag, auto buf_tag) {
+    wino63_f16x3_tile<decltype(wn_tag)::value, decltype(buf_tag)::value>(
+        smem_raw, Vh, Ve, Wp, bias, y, park, Cin, T, M, nq, nsext, nsp2, tile_m, tile_n, tiles_n, sub, relu, ldy, vec2);
+  };
+  auto shape = [&](auto buf_tag) {
+    if (bid < nfull) tile(std::integral_constant<int, 4>{}, buf_tag);
+    else if (f == 2) tile(std::integral_constant<int, 2>{}, buf_tag);
+    else tile(std::integral_constant<int, 1>{}, buf_tag);
+  };
+  if (buf) shape(std::true_type{}); else shape(std::false_type{});
 }
 
 int64_t padded_sextets(int64_t B, int64_t T) { return tspn::ceil_div(B * tspn::ceil_div(T, 6), SWG) * SWG; }
@@ -941,7 +1038,8 @@ int tspn::wino63_input_transform(const float* x, int64_t B, int64_t T, int64_t C
   return tspn::check_launch(what);
 }
 
-// 0 = buffer-load V pieces where the workspace allows (default), 1 = 64-bit pointer pieces everywhere
+// 0 = buffer-load pieces where the operands allow (default), 1 = 64-bit pointer pieces everywhere; governs the fp32
+// contraction (its V pieces) and the split-fp16 one (all of its pieces)
 static std::atomic<int> g_piece_form{0};
 
 // step 2: the MFMA kernel on the transformed input
@@ -1117,6 +1215,11 @@ int tspn::wino63_f16x3_contract(void* workspace, size_t workspace_bytes, int64_t
   int64_t R = 0;
   const int f = tail_split_factor(tiles_m * tiles_n, device_cus(), &R);
   const int64_t grid = tiles_m * tiles_n + R * (f - 1);
+  // buffer-load pieces where the hi + lo halves of one point's slab, of the weights and of the split input, stay below
+  // 2 GB (a descriptor per operand and point, 32-bit offsets inside it); tspn_conv3_tc_wino63_set_piece_form(1)
+  // forces the pointer form
+  const int64_t slab = 4 * Cin * std::max<int64_t>(M, nsp2);
+  const int buf = slab < (1LL << 31) && g_piece_form.load(std::memory_order_relaxed) == 0;
   char* ws = static_cast<char*>(workspace);
   static tspn::LdsLimit lds;     // 128 KB of dynamic LDS
   void (*kern)(const _Float16*, const int*, const int16_t*, const float*, float*, float*, int, int, int, int, int64_t,
@@ -1125,7 +1228,7 @@ int tspn::wino63_f16x3_contract(void* workspace, size_t workspace_bytes, int64_t
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(F_THREADS), F_SMEM_ALL, TSPN_STREAM(stream),
                      reinterpret_cast<const _Float16*>(ws + L.v), reinterpret_cast<const int*>(ws + L.e), packed, bias, y,
                      reinterpret_cast<float*>(ws + L.park), (int)Cin, (int)T, (int)M, (int)nq, nsext, nsp2, (int)tiles_m,
-                     (int)tiles_n, relu, (int)ldy, TSPN_WINO63_GM | (f << 8), vec2);
+                     (int)tiles_n, relu, (int)ldy, TSPN_WINO63_GM | (f << 8) | (buf << 16), vec2);
   return tspn::check_launch(what);
 }
 

@@ -517,8 +517,8 @@ def conv3_tc_wino63_f16x3(x, packed, bias=None, relu=False, workspace=None):
 
 
 def wino63_set_piece_form(form):
-    """0 = buffer-load pieces where the workspace is below 4 GB (default), 1 = 64-bit pointer pieces everywhere
-    (tspn_conv3_tc_wino63_set_piece_form).  Returns the previous setting."""
+    """0 = buffer-load pieces where the operands allow (default), 1 = 64-bit pointer pieces everywhere, for the fp32
+    and the split-fp16 F(6,3) contraction (tspn_conv3_tc_wino63_set_piece_form).  Returns the previous setting."""
     prev = _abi.lib().tspn_conv3_tc_wino63_set_piece_form(int(form))
     if prev < 0:
         _abi.check(prev)
