@@ -44,7 +44,9 @@ extern "C" {
  * tspn_bottleneck_tail_io_bf16, tspn_conv3_tc_wino63_set_piece_form (replaces the TSPN_WINO63_PTRV environment switch);
  * 7 (round 6): the device status block (tspn_status_attach / _fault / _clear / _selftest, TSPN_EDEVICE: a kernel can
  * raise a fault that the NEXT launch entry reports without a synchronisation); tspn_fused_desc gained conv_weight /
- * conv_check at its END (the a-posteriori accuracy guard of the F(6,3) temporal conv, tspn_conv3_spot_check_f32). */
+ * conv_check at its END (the a-posteriori accuracy guard of the F(6,3) temporal conv, tspn_conv3_spot_check_f32).
+ * Still 7 (additive, no layout or signature changed): tspn_pair_plan_i32, tspn_heads_pairlist_bf16 (+ _workspace_bytes),
+ * tspn_forward_fused_bf16_pairs (+ _workspace_bytes): the bf16 path on an arbitrary pair table. */
 #define TSPN_ABI_VERSION 7
 
 enum {
@@ -507,8 +509,9 @@ typedef struct tspn_fused_bf16_desc {
   int64_t B, N, T, D;            /* C = 2D; D % 16 == 0 */
   int64_t A, K;
   const uint16_t* feats;         /* bf16 [B*N, T, D] */
-  const int64_t* pairs;          /* canonical table of tspn_pair_index_i64 for every video, global ids */
-  int64_t P;                     /* == B*N*(N-1) */
+  const int64_t* pairs;          /* canonical table of tspn_pair_index_i64 for every video, global ids
+                                    (tspn_forward_fused_bf16_pairs: any [P,2] table of global ids) */
+  int64_t P;                     /* == B*N*(N-1) (tspn_forward_fused_bf16_pairs: any 0 <= P < 2^31) */
   const uint16_t* conv_packed;   /* tspn_pack_conv3_bf16(conv.weight [C,C,3], split=D): [3][D/8][2C][8] */
   const float* conv_bias;        /* [C] fp32 */
   const uint16_t* head_packed;   /* tspn_pack_heads_bf16([3A, C]) */
@@ -528,6 +531,43 @@ typedef struct tspn_fused_bf16_desc {
 
 size_t tspn_forward_fused_bf16_workspace_bytes(const tspn_fused_bf16_desc* d);
 int tspn_forward_fused_bf16(const tspn_fused_bf16_desc* d, void* stream);
+
+/* ---- bf16-operand path on an ARBITRARY pair table (pairlist/tspn_pairlist_bf16.hip) ----
+ * `pairs` int64 [P,2]: global tracklet ids (video = id / N), in any order, any subset, rows may repeat, (s, s) is a pair
+ * like any other (as in tspn_heads_f32 mode 1).  Cost follows the 16 x 16 (N <= 12: 8 x 8) tiles of the grid
+ * (distinct subjects of a video, ascending) x (distinct objects, ascending) that hold at least one row.
+ *
+ * SKIPPED ROWS: a row with an id outside [0, B*N) or with its two ids in different videos is skipped -- no access
+ * anywhere is made on its behalf and its row of `out` is LEFT UNWRITTEN (the caller's previous contents).
+ * LIMITS: N <= 2048 and P < 2^31, else TSPN_EUNSUPPORTED; ldm < 2C, C % 32 != 0, ldm % 4 != 0 or a y / head_packed that is
+ * not 16-byte aligned are TSPN_EUNSUPPORTED too; one video's rows of y stay below 2 GB as for tspn_heads_pairgrid_bf16.
+ *
+ * tspn_pair_plan_i32: the plan the pair stage runs on, every array the caller's (no allocation, no synchronisation;
+ * one memset node and two kernels on `stream`).  Np = N rounded up to a multiple of 16.  Per video b:
+ *   s_list[b][0 .. ns_b)  int32 [B][Np]  local ids of the distinct subjects that occur, ascending (slots beyond: 0)
+ *   o_list[b][0 .. no_b)  the same for the objects
+ *   counts[b] = (ns_b, no_b)              int32 [B][2]
+ *   head[b][i][j]         int32 [B][Np][Np] over the ranks i, j in the two lists: the first row of the chain of rows whose
+ *                         pair is (s_list[b][i], o_list[b][j]), -1 for none
+ *   next[p]               int32 [P]: the next row of p's chain, -1 at its end and for a skipped row
+ *   rank_ws               int32 [B][2][N] scratch (tracklet -> rank, -1 where it does not occur)
+ * The chains are linked with atomic exchanges: their ORDER differs from run to run, the SET of rows on each does not.
+ *
+ * tspn_heads_pairlist_bf16: out[p][h][t] = head_b[h] + sum_c Wh[h][c] * bf16(relu(U[s_p][t][c] + V[o_p][t][c])) for
+ * every row p that is not skipped; builds the plan in `workspace` (tspn_heads_pairlist_bf16_workspace_bytes, 256-byte
+ * aligned) first.  A row's values equal, bit for bit, the row of tspn_heads_pairgrid_bf16 for the same (s, o).          */
+int tspn_pair_plan_i32(const int64_t* pairs, int64_t P, int64_t B, int64_t N, int32_t* s_list, int32_t* o_list,
+                       int32_t* counts, int32_t* head, int32_t* next, int32_t* rank_ws, void* stream);
+size_t tspn_heads_pairlist_bf16_workspace_bytes(int64_t B, int64_t N, int64_t P);
+int tspn_heads_pairlist_bf16(const float* y, int64_t ldm, int64_t B, int64_t N, int64_t C, int64_t T,
+                             const int64_t* pairs, int64_t P, const uint16_t* head_packed, const float* head_b,
+                             int64_t H, float* out, void* workspace, size_t workspace_bytes, void* stream);
+/* tspn_forward_fused_bf16 on any pair table: the same descriptor, the same order of work (tracklet means and predicate
+ * logits first, ev_logits_ready, the conv, then the plan and the pair-list stage), graph-capturable like it.  Skipped rows
+ * (above) keep their rows of out_heads; their rows of out_logits are computed from whatever ids they hold, so a caller
+ * that cannot vouch for its table checks it first. */
+size_t tspn_forward_fused_bf16_pairs_workspace_bytes(const tspn_fused_bf16_desc* d);
+int tspn_forward_fused_bf16_pairs(const tspn_fused_bf16_desc* d, void* stream);
 
 /* ---- dense reference-faithful encoder + heads on a materialised [P,C,T] --
  * DPNHead.forward (lib/modeling/relpn/dpn.py:69-73) on arbitrary pair feats:

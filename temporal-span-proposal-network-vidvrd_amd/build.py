@@ -18,6 +18,7 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 CSRC_EVAL = os.path.join(CSRC, "eval")   # evaluation kernels (their variant table: tests/eval_kernel_variants.py)
 CSRC_REL = os.path.join(CSRC, "relations")   # span relation decode (its variant table: tests/relations_kernel_variants.py)
+CSRC_PAIRLIST = os.path.join(CSRC, "pairlist")   # bf16 pair-list stage (its variant table: tests/pairlist_kernel_variants.py)
 LIB_NAME = "libtspn_mi355x.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 ARCH = "gfx950"
@@ -38,6 +39,7 @@ RES_PATH = os.path.join(HERE, "kernel_resources.json")   # next to the .so (git-
 NO_SPILL_KERNELS = ("conv3_wino63_kernel", "heads_pairgrid4_kernel", "heads_pairgrid3_kernel",
                     "conv2d_nhwc_frag_kernel", "conv2d_nhwc_bf16_kernel", "conv2d_nhwc_cin4_kernel",
                     "bottleneck_bf16_kernel", "bottleneck_pipe_bf16_kernel", "conv3_bf16_big_kernel", "heads_pairgrid_bf16_kernel",
+                    "heads_pairlist_bf16_kernel",
                     #  254 - 256 and 233 - 234 VGPRs, hand-counted s_waitcnt vmcnt(N) and the "keep the store data
                     # registers live" hazard fence: a spill would change the VMEM counts and could defeat the fence
                     "tail_io_bf16_kernel", "bottleneck_block_bf16_kernel")
@@ -45,12 +47,12 @@ NO_SPILL_KERNELS = ("conv3_wino63_kernel", "heads_pairgrid4_kernel", "heads_pair
 
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC_EVAL, "*.hip")) +
-                  glob.glob(os.path.join(CSRC_REL, "*.hip")))
+                  glob.glob(os.path.join(CSRC_REL, "*.hip")) + glob.glob(os.path.join(CSRC_PAIRLIST, "*.hip")))
 
 
 def _headers():
     return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC_EVAL, "*.h")) + \
-        glob.glob(os.path.join(CSRC_REL, "*.h")) + \
+        glob.glob(os.path.join(CSRC_REL, "*.h")) + glob.glob(os.path.join(CSRC_PAIRLIST, "*.h")) + \
         glob.glob(os.path.join(ROOT, "include", "*.h")) + \
         [os.path.abspath(__file__)]
 

@@ -24,6 +24,7 @@
 
 #include "tspn_common.h"
 #include "tspn_device.h"
+#include "tspn_heads_pair_bf16.h"
 
 namespace {
 
@@ -351,34 +352,44 @@ __global__ __launch_bounds__(G_THREADS, 1) void conv3_bf16_big_kernel(
 #ifndef TSPN_HPB_SW
 #define TSPN_HPB_SW 2        // subjects per wave of the <8, 16> form (probe knob: 4 = 4 subjects x 8 objects per wave)
 #endif
-constexpr int HP_FB = 16;
-constexpr int HP_KC = 32;
-constexpr int HP_ROW = HP_FB * HP_KC * 4;  // 2048 B
-
-__device__ __forceinline__ unsigned relu_pack(float a, float b) {
-  // ReLU in fp32 with the NaN-propagating maximum (F.relu(NaN) = NaN; -0 -> +0; two v_maximum3_f32), then one rounding to
-  // bf16.  The packed int16 maximum on the bf16 pair this replaces zeroed a NaN whose sign bit is set (a negative int16).
-  const f32x2 s = {tspn::relu_f32(a), tspn::relu_f32(b)};
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(s, bf16x2));
-}
-
 // NW waves; workgroup = 2 NW subjects x OB objects x 16 frames, wave w owns subjects 2w, 2w+1.
 // <4, 8>: 8 x 8 pairs, 32 KB per stage, 2 workgroups/CU (small N).  <8, 16>: 16 x 16 pairs, 64 KB per
 // stage, 1 workgroup/CU -- half the bytes streamed from L2 per activation, which is what bounds the
 // kernel (ablation at the config-3 shape, 8 x 8: 4.5 ms, without the DMA stream 2.2, without the
 // VALU work still 4.5).
+struct PairGridCtx {
+  int b, N, T, H, sb, ob;
+  float* __restrict__ out;
+};
+// the canonical table on the tile of tspn_heads_pair_bf16.h: slot = tracklet
+template <int SBLK, int OB>
+struct PairGridMap {
+  // row r < SBLK: subject SBLK sb + r, else object OB ob + r - SBLK
+  static __device__ __forceinline__ int row_trk(const PairGridCtx c, int r) {
+    int trk = r < SBLK ? c.sb * SBLK + r : c.ob * OB + r - SBLK;
+    trk = min(trk, c.N - 1);
+    return trk;
+  }
+  static __device__ __forceinline__ void emit(const PairGridCtx c, int s_slot, int o_slot, int t, int hg, f32x4 acc,
+                                              f32x4 bias) {
+    const int sg = c.sb * SBLK + s_slot;
+    const int og = c.ob * OB + o_slot;
+    if (sg >= c.N || og >= c.N || sg == og || t >= c.T) return;
+    const int64_t p = (int64_t)c.b * c.N * (c.N - 1) + (int64_t)sg * (c.N - 1) + (og < sg ? og : og - 1);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int h = 4 * hg + r;
+      if (h < c.H) c.out[(p * c.H + h) * c.T + t] = acc[r] + bias[r];
+    }
+  }
+};
+
 template <int NW, int OB, int SW>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void heads_pairgrid_bf16_kernel(
     const float* __restrict__ y, int64_t ldm, int B, int N, int C, int T,
     const __bf16* __restrict__ Whp, const float* __restrict__ bh, int H, float* __restrict__ out,
     int nsb, int nob, int nfb) {
   constexpr int SBLK = 2 * NW;
-  constexpr int WS = SBLK / SW, WO = NW / WS, OW = OB / WO;   // waves along subjects / objects, objects per wave
-  static_assert(WS * WO == NW && OW * WO == OB, "wave tiling");
-  constexpr int ROWS = SBLK + OB;
-  constexpr int ST = ROWS * HP_ROW + 1024;  // + the k-step's slice of the head weights (one piece)
-  static_assert(ROWS == 4 * NW, "each wave stages 4 rows");
-  extern __shared__ __attribute__((aligned(16))) char smem[];
 
   int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int ob = wg % nob;
@@ -388,136 +399,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void heads_pairgrid_bf16_
   const int fb = wg % nfb;
   const int b = wg / nfb;
 
-  const int tid = threadIdx.x;
-  const int lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int f = lane & 15, kg = lane >> 4;
-  const int t0 = fb * HP_FB;
-  const int ws = wave % WS, wo = wave / WS;      // this wave's subjects SW ws .., objects OW wo ..
-
-  // DMA sources: wave w stages rows 4w .. 4w+3 (2 pieces each); row r < SBLK: subject SBLK sb + r
-  // (U half, channels [0,C)), else object OB ob + r - SBLK (V half, channels [C,2C))
-  // LDS image of a row: two pieces of 8 frames; inside a piece position = 16 X + slot with
-  //   slot = (f & 7) + 8 ((q >> 1) & 1),  X = 2 (q >> 2) + (q & 1)      (q = 16-byte channel quad 0..7)
-  // so that (a) one DMA piece fetches 8 complete 128-byte lines of y (8 frames x 32 channels) and
-  // (b) the fragment read of lane (f, kg) for quad 2 kg + r sits at slot (f & 7) + 8 (kg & 1): the
-  // four 16-lane groups of a ds_read_b128 each cover all 16 slots -- conflict-free.
-  // (buffer loads: descriptor = this video's rows of y, a fixed 32-bit lane offset per piece, one scalar offset that
-  // advances 128 bytes per k-step -- cheaper to issue beside MFMAs than global_load_lds with eight 64-bit pointers per
-  // lane, and eight registers and sixteen vector adds per k-step less; tools/probes/lds_dma_issue_probe.hip)
-  const __amdgpu_buffer_rsrc_t rsrc_y = buffer_rsrc(y + (int64_t)b * N * T * ldm, (int)(unsigned)((int64_t)N * T * ldm * 4));
-  unsigned voff[8];
-  {
-    const int fq = lane & 7;
-    const int q = (lane >> 5) * 4 + ((lane >> 3) & 1) * 2 + ((lane >> 4) & 1);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const int r = wave * 4 + (i >> 1), j = i & 1;
-      int trk = r < SBLK ? sb * SBLK + r : ob * OB + r - SBLK;
-      trk = min(trk, N - 1);
-      const int t = min(t0 + 8 * j + fq, T - 1);
-      voff[i] = (unsigned)((((int64_t)trk * T + t) * ldm + (r < SBLK ? 0 : C) + 4 * q) * 4);
-    }
-  }
-  const __amdgpu_buffer_rsrc_t rsrc_w = buffer_rsrc(Whp, C * 32);
-  int y_soff = 0, w_soff = 0;
-  auto stage = [&](int buf) {
-    char* dst = smem + buf * ST + wave * 4 * HP_ROW;
-#pragma unroll
-    for (int i = 0; i < 8; ++i)
-      bglds16(rsrc_y, voff[i], y_soff, dst + i * 1024);
-    y_soff += HP_KC * 4;
-    // head weights of the k-step, [4 kg][16 h][8 ch] bf16 = the packed layout itself; staged through
-    // LDS as well so that no register-returning global load (whose wait the compiler would place at the
-    // top of the loop, serialising the whole DMA queue with the compute) is left in the loop
-    if (wave == 0) {
-      bglds16(rsrc_w, lane * 16, w_soff, smem + buf * ST + ROWS * HP_ROW);
-      w_soff += 1024;
-    }
-  };
-
-  f32x4 acc[SW][OW];
-#pragma unroll
-  for (int s = 0; s < SW; ++s)
-#pragma unroll
-    for (int o = 0; o < OW; ++o) acc[s][o] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = C / HP_KC;
-  // fragment of lane (f, kg): quads 2 kg (here) and 2 kg + 1 (256 bytes further)
-  const int frag_off = (64 * (f >> 3) + 32 * (kg >> 1) + 8 * (kg & 1) + (f & 7)) * 16;
-  stage(0);
-  __builtin_amdgcn_s_waitcnt(0x0070);                 // vmcnt(0) lgkmcnt(0)
-  __builtin_amdgcn_s_barrier();
-
-  for (int k = 0; k < nk; ++k) {
-    const int buf = k & 1;
-    if (k + 1 < nk) stage(buf ^ 1);
-    __builtin_amdgcn_sched_barrier(0);
-    const bf16x8 wfrag = *reinterpret_cast<const bf16x8*>(smem + buf * ST + ROWS * HP_ROW + lane * 16);
-    const char* base = smem + buf * ST + frag_off;
-    f32x4 u[SW][2];
-#pragma unroll
-    for (int s = 0; s < SW; ++s) {
-      u[s][0] = *reinterpret_cast<const f32x4*>(base + (SW * ws + s) * HP_ROW);
-      u[s][1] = *reinterpret_cast<const f32x4*>(base + (SW * ws + s) * HP_ROW + 256);
-    }
-    // V fragments are read two objects ahead of their use (LDS latency off the critical path).  The
-    // reads and their counted waits are written out: left to itself the compiler issues every
-    // fragment read right before its first use and waits for it at once (32 exposed LDS round trips
-    // per k-step).  LDS returns in order, so "lgkmcnt(n)" = all but the newest n reads have landed.
-    const unsigned vaddr = (unsigned)(size_t)(__attribute__((address_space(3))) const char*)(base + (SBLK + OW * wo) * HP_ROW);
-    f32x4 vq[3][2];
-#define TSPN_VREAD(slot, o)                                                                             \
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(vq[slot][0]) : "v"(vaddr), "n"((o) * HP_ROW)); \
-  asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(vq[slot][1]) : "v"(vaddr), "n"((o) * HP_ROW + 256));
-    TSPN_VREAD(0, 0)
-    TSPN_VREAD(1, 1)
-#pragma unroll
-    for (int o = 0; o < OW; ++o) {
-      if (o + 2 < OW) {
-        TSPN_VREAD((o + 2) % 3, o + 2)
-        asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(vq[o % 3][0]), "+v"(vq[o % 3][1]));
-      } else if (o + 1 < OW) {
-        asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(vq[o % 3][0]), "+v"(vq[o % 3][1]));
-      } else {
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(vq[o % 3][0]), "+v"(vq[o % 3][1]));
-      }
-      const f32x4 v0 = vq[o % 3][0], v1 = vq[o % 3][1];
-#pragma unroll
-      for (int s = 0; s < SW; ++s) {
-        const f32x4 a0 = u[s][0] + v0, a1 = u[s][1] + v1;
-        u32x4 pk = {relu_pack(a0[0], a0[1]), relu_pack(a0[2], a0[3]), relu_pack(a1[0], a1[1]),
-                    relu_pack(a1[2], a1[3])};
-        acc[s][o] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfrag, __builtin_bit_cast(bf16x8, pk),
-                                                             acc[s][o], 0, 0, 0);
-      }
-    }
-#undef TSPN_VREAD
-    __builtin_amdgcn_s_waitcnt(0x0070);               // vmcnt(0) lgkmcnt(0): the next k-step is in LDS
-    __builtin_amdgcn_s_barrier();
-  }
-
-  // epilogue: lane = (frame f, head group hg): heads 4 hg .. 4 hg + 3
-  const int t = t0 + f;
-  const int hg = lane >> 4;
-  float bias[4];
-#pragma unroll
-  for (int r = 0; r < 4; ++r) bias[r] = (4 * hg + r < H) ? bh[4 * hg + r] : 0.f;
-#pragma unroll
-  for (int s = 0; s < SW; ++s) {
-    const int sg = sb * SBLK + SW * ws + s;
-#pragma unroll
-    for (int o = 0; o < OW; ++o) {
-      const int og = ob * OB + OW * wo + o;
-      if (sg >= N || og >= N || sg == og || t >= T) continue;
-      const int64_t p = (int64_t)b * N * (N - 1) + (int64_t)sg * (N - 1) + (og < sg ? og : og - 1);
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int h = 4 * hg + r;
-        if (h < H) out[(p * H + h) * T + t] = acc[s][o][r] + bias[r];
-      }
-    }
-  }
+  // slot = tracklet; the tile (staging, k-loop, epilogue walk) is tspn_heads_pair_bf16.h, shared with the pair-list kernel
+  heads_pair_tile_bf16<NW, OB, SW, PairGridMap<SBLK, OB>>(y, ldm, b, N, C, T, Whp, bh, H, fb * HP_FB,
+                                                          PairGridCtx{b, N, T, H, sb, ob, out});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -692,7 +576,7 @@ extern "C" int tspn_heads_pairgrid_bf16(const float* y, int64_t ldm, int64_t B, 
   const int64_t grid = B * nsb * nsb * nfb;
   TSPN_REQUIRE(grid < (1LL << 31) && N < (1 << 20) && T < (1 << 24) && C < (1 << 24) && N * T * ldm * 4 < (1LL << 31),
                TSPN_EUNSUPPORTED, "tspn_heads_pairgrid_bf16: problem too large (a video's projections must stay below 2 GB)");
-  const size_t smem = 2 * ((size_t)(2 * sblk) * HP_ROW + 1024);
+  const size_t smem = heads_pair_tile_lds((int)(2 * sblk));
   static tspn::LdsLimit lds[2];
   if (int rc = big ? lds[1].ensure(reinterpret_cast<const void*>(heads_pairgrid_bf16_kernel<8, 16, TSPN_HPB_SW>), smem,
                                    "tspn_heads_pairgrid_bf16")
@@ -787,26 +671,43 @@ extern "C" size_t tspn_forward_fused_bf16_workspace_bytes(const tspn_fused_bf16_
   return bf16_layout(d).total;
 }
 
-extern "C" int tspn_forward_fused_bf16(const tspn_fused_bf16_desc* d, void* stream) {
-  TSPN_REQUIRE(d, TSPN_EINVAL, "tspn_forward_fused_bf16: null descriptor");
+extern "C" size_t tspn_forward_fused_bf16_pairs_workspace_bytes(const tspn_fused_bf16_desc* d) {
+  if (!d || d->B <= 0 || d->N <= 0 || d->T <= 0 || d->D <= 0 || d->K <= 0 || d->P < 0) return 0;
+  const size_t plan = tspn_heads_pairlist_bf16_workspace_bytes(d->B, d->N, d->P);
+  return plan ? bf16_layout(d).total + plan : 0;      // the plan's arrays follow the pass's own (256-byte aligned)
+}
+
+namespace {
+// The two whole passes: `list` = false scores the canonical table on the pair grid, true any [P,2] table through the
+// pair-list stage (pairlist/tspn_pairlist_bf16.hip).  Same order of work in both.
+int forward_fused_bf16_impl(const tspn_fused_bf16_desc* d, void* stream, bool list, const char* who) {
+  TSPN_REQUIRE(d, TSPN_EINVAL, "%s: null descriptor", who);
   TSPN_REQUIRE(d->B >= 0 && d->N >= 0 && d->T > 0 && d->D > 0 && d->A > 0 && d->K > 0, TSPN_EINVAL,
-               "tspn_forward_fused_bf16: bad sizes");
-  TSPN_REQUIRE(3 * d->A <= 16, TSPN_EUNSUPPORTED, "tspn_forward_fused_bf16: 3A=%lld > 16", (long long)(3 * d->A));
-  const int64_t NT = d->B * d->N, P = d->B * d->N * (d->N - 1), C = 2 * d->D;
-  TSPN_REQUIRE(d->P == P, TSPN_EINVAL,
-               "tspn_forward_fused_bf16: P=%lld, the canonical pair table has B*N*(N-1)=%lld rows",
-               (long long)d->P, (long long)P);
-  if (P == 0) return TSPN_OK;
+               "%s: bad sizes", who);
+  TSPN_REQUIRE(3 * d->A <= 16, TSPN_EUNSUPPORTED, "%s: 3A=%lld > 16", who, (long long)(3 * d->A));
+  const int64_t NT = d->B * d->N, C = 2 * d->D;
+  const int64_t P = list ? d->P : d->B * d->N * (d->N - 1);
+  if (list) {
+    TSPN_REQUIRE(P >= 0, TSPN_EINVAL, "%s: P=%lld", who, (long long)P);
+    TSPN_REQUIRE(P < (1LL << 31) && d->N <= 2048, TSPN_EUNSUPPORTED, "%s: needs P < 2^31 and N <= 2048 (P=%lld N=%lld)", who,
+                 (long long)P, (long long)d->N);
+  } else {
+    TSPN_REQUIRE(d->P == P, TSPN_EINVAL,
+                 "%s: P=%lld, the canonical pair table has B*N*(N-1)=%lld rows", who,
+                 (long long)d->P, (long long)P);
+  }
+  if (P == 0 || NT == 0) return TSPN_OK;
   TSPN_REQUIRE(d->feats && d->pairs && d->conv_packed && d->conv_bias && d->head_packed && d->head_b &&
                    d->cls_w && d->cls_b && d->out_heads && d->out_logits && d->workspace,
-               TSPN_EINVAL, "tspn_forward_fused_bf16: null pointer");
-  TSPN_REQUIRE(d->D % 16 == 0, TSPN_EUNSUPPORTED, "tspn_forward_fused_bf16: needs D %% 16 == 0 (D=%lld)",
+               TSPN_EINVAL, "%s: null pointer", who);
+  TSPN_REQUIRE(d->D % 16 == 0, TSPN_EUNSUPPORTED, "%s: needs D %% 16 == 0 (D=%lld)", who,
                (long long)d->D);
   const Bf16Layout L = bf16_layout(d);
-  TSPN_REQUIRE(d->workspace_bytes >= L.total, TSPN_EWORKSPACE,
-               "tspn_forward_fused_bf16: workspace %zu < %zu bytes", d->workspace_bytes, L.total);
+  const size_t plan_bytes = list ? tspn_heads_pairlist_bf16_workspace_bytes(d->B, d->N, P) : 0;
+  TSPN_REQUIRE(d->workspace_bytes >= L.total + plan_bytes, TSPN_EWORKSPACE,
+               "%s: workspace %zu < %zu bytes", who, d->workspace_bytes, L.total + plan_bytes);
   TSPN_REQUIRE((reinterpret_cast<uintptr_t>(d->workspace) & 255) == 0, TSPN_EINVAL,
-               "tspn_forward_fused_bf16: workspace must be 256-byte aligned");
+               "%s: workspace must be 256-byte aligned", who);
   char* ws = static_cast<char*>(d->workspace);
   float* bias2 = reinterpret_cast<float*>(ws + L.bias2);
   float* y = reinterpret_cast<float*>(ws + L.y);
@@ -815,7 +716,7 @@ extern "C" int tspn_forward_fused_bf16(const tspn_fused_bf16_desc* d, void* stre
   // conv bias rides on the subject half: U' = U + b, V' = V
   if (hipMemsetAsync(bias2 + C, 0, C * sizeof(float), s) != hipSuccess ||
       hipMemcpyAsync(bias2, d->conv_bias, C * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
-    return tspn::fail(TSPN_ELAUNCH, "tspn_forward_fused_bf16: bias staging failed");
+    return tspn::fail(TSPN_ELAUNCH, "%s: bias staging failed", who);
   int rc;
   // the predicate logits depend on the tracklet means only: computed FIRST (as in tspn_forward_fused_f32) so that a
   // caller can decode / gather them on another stream behind ev_logits_ready while the encoder runs
@@ -828,6 +729,18 @@ extern "C" int tspn_forward_fused_bf16(const tspn_fused_bf16_desc* d, void* stre
   rc = tspn_conv3_tc_bf16(d->feats, NT, d->T, d->D, d->conv_packed, 2 * C, bias2, y, 2 * C, stream);
   if (d->ev_conv_end) (void)hipEventRecord(static_cast<hipEvent_t>(d->ev_conv_end), s);
   if (rc) return rc;
+  if (list)
+    return tspn_heads_pairlist_bf16(y, 2 * C, d->B, d->N, C, d->T, d->pairs, P, d->head_packed, d->head_b, 3 * d->A,
+                                    d->out_heads, ws + L.total, plan_bytes, stream);
   return tspn_heads_pairgrid_bf16(y, 2 * C, d->B, d->N, C, d->T, d->head_packed, d->head_b, 3 * d->A, d->out_heads,
                                   stream);
+}
+}  // namespace
+
+extern "C" int tspn_forward_fused_bf16(const tspn_fused_bf16_desc* d, void* stream) {
+  return forward_fused_bf16_impl(d, stream, false, "tspn_forward_fused_bf16");
+}
+
+extern "C" int tspn_forward_fused_bf16_pairs(const tspn_fused_bf16_desc* d, void* stream) {
+  return forward_fused_bf16_impl(d, stream, true, "tspn_forward_fused_bf16_pairs");
 }

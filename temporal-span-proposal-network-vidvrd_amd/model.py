@@ -987,6 +987,27 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
             self._pair_tables[key] = hit
         return hit
 
+    def _group_pair_table(self, customs, dev, n):
+        """Pair table of one group of equal-shape segments for a fused pass (either operand type): `customs` holds, per
+        member, its validated-here 'tracklet_pairs' as a host int64 [P,2] of local ids, or None for all ordered pairs.
+        Returns (global table [sum P, 2] on `dev` with member k's ids offset by k*n, rows per member, whether it is the
+        canonical table of every member)."""
+        nm = len(customs)
+        if all(p is None for p in customs):
+            allp, _ = self._canonical_pairs(dev, nm, n)
+            return allp, [n * (n - 1)] * nm, True
+        pairs = []
+        for k, p in enumerate(customs):
+            if p is None:
+                pairs.append(ops.pair_index(n, dev, base=k * n))
+                continue
+            if p.dim() != 2 or p.shape[1] != 2:
+                raise ValueError("tracklet_pairs must be [P,2]")
+            if p.numel() and (int(p.min()) < 0 or int(p.max()) >= n):
+                raise IndexError("tracklet_pairs index out of range")
+            pairs.append(p.to(dev) + k * n)
+        return torch.cat(pairs).contiguous(), [p.shape[0] for p in pairs], False
+
     def _side_stream(self, dev):
         hit = self._side.get(dev.index)
         if hit is None:
@@ -1095,44 +1116,30 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                                          track_token=len(groups) == 1)
                 continue
             if bf16:
-                # bf16 tracklet features select the bf16-operand kernels (BASELINE config 3)
-                if any(custom_pairs(pair_list[i]) is not None for i in members):
-                    raise NotImplementedError("the bf16 path scores the canonical pair table only")
+                # bf16 tracklet features select the bf16-operand kernels (BASELINE config 3); a member with its own
+                # 'tracklet_pairs' sends the group through the pair-list stage (RELPN.DPN.POOL_TOP_SPAN is not applied
+                # on bf16 segments: DESIGN.md §8)
                 if d % 16:
                     raise ValueError(f"the bf16 path needs D % 16 == 0 (D={d})")
                 feats = _batch_rows(src, dev, torch.bfloat16)
-                allp, _ = self._canonical_pairs(dev, nm, n)
+                allp, counts, canonical = self._group_pair_table([custom_pairs(pair_list[i]) for i in members], dev, n)
+                if not canonical and side is not None and self.pair_geometry_in_forward:
+                    side.wait_stream(main)     # the geometry launch on the side stream reads this table
                 packed, cbias, hpk, hb16 = dpn._bf16_weights(dev)
                 cw16, cb16 = self.classifier._cache.get(
                     "cls_bf16", (cls.weight, cls.bias), dev,
                     lambda ts: tuple(ops.cast_bf16(x.contiguous()).float() for x in ts))
-                need = ops.fused_bf16_workspace_bytes(nm, n, t, d, hb16.numel() // 3, cw16.shape[0], allp.shape[0])
+                need = ops.fused_bf16_workspace_bytes(nm, n, t, d, hb16.numel() // 3, cw16.shape[0], allp.shape[0],
+                                                      canonical_pairs=canonical)
                 heads, lg = ops.forward_fused_bf16(feats, allp, nm, n, packed, cbias, hpk, hb16, cw16, cb16,
                                                    workspace=self._workspace(dev, need), conv_events=self._conv_events,
-                                                   logits_event=ev_logits if (overlap and len(groups) == 1) else None)
-                counts = [per] * nm
+                                                   logits_event=ev_logits if (overlap and len(groups) == 1) else None,
+                                                   canonical_pairs=canonical, check_pairs=False)
             else:
                 feats = _batch_rows(src, dev)
-                customs = [custom_pairs(pair_list[i]) for i in members]
-                canonical = all(p is None for p in customs)
-                if canonical:
-                    allp, _ = self._canonical_pairs(dev, nm, n)
-                    counts = [per] * nm
-                else:
-                    pairs = []
-                    for k, p in enumerate(customs):
-                        if p is None:
-                            pairs.append(ops.pair_index(n, dev, base=k * n))
-                            continue
-                        if p.dim() != 2 or p.shape[1] != 2:
-                            raise ValueError("tracklet_pairs must be [P,2]")
-                        if p.numel() and (int(p.min()) < 0 or int(p.max()) >= n):
-                            raise IndexError("tracklet_pairs index out of range")
-                        pairs.append(p.to(dev) + k * n)
-                    counts = [p.shape[0] for p in pairs]
-                    allp = torch.cat(pairs).contiguous()
-                    if side is not None and self.pair_geometry_in_forward:
-                        side.wait_stream(main)     # the geometry launch on the side stream reads this table
+                allp, counts, canonical = self._group_pair_table([custom_pairs(pair_list[i]) for i in members], dev, n)
+                if not canonical and side is not None and self.pair_geometry_in_forward:
+                    side.wait_stream(main)     # the geometry launch on the side stream reads this table
                 # temporal conv algorithm: RELPN.DPN.CONV_ALGO = "auto" (Winograd F(6,3) when D % 32 == 0: 4/9 of the
                 # MFMA work; its fp32 error bound is in DESIGN.md §4) or "direct" (the k=3 taps as one implicit GEMM)
                 algo = self._conv_algo(d, dev)

@@ -17,6 +17,7 @@ __all__ = [
     "pair_gather", "pack_conv3", "conv3", "conv3_tc", "pack_conv3_wino63", "conv3_tc_wino63", "pack_conv3_wino63_f16x3", "conv3_tc_wino63_f16x3", "heads", "heads_pairgrid", "temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
     "forward_fused", "temporal_encoder_heads", "fused_workspace_bytes", "fused_bf16_workspace_bytes", "decode_topk", "decode_spans", "decode_span_relations",
     "cast_bf16", "pack_conv3_bf16", "pack_heads_bf16", "conv3_tc_bf16", "heads_pairgrid_bf16",
+    "pair_plan", "heads_pairlist_bf16",
     "transpose_cast_bf16", "temporal_encoder_heads_bf16",
     "temporal_mean_bf16", "forward_fused_bf16", "span_predicate", "bottleneck_block_bf16", "bottleneck_block_proj_bf16", "bottleneck_block_res_bf16",
     "proposal_pair_filter", "gather_rows", "wino63_set_piece_form", "wino63_f16x3_set_tail_split", "conv3_spot_check",
@@ -918,15 +919,97 @@ def temporal_mean_bf16(x):
     return out
 
 
-def fused_bf16_workspace_bytes(B, N, T, D, A, K, P):
+def fused_bf16_workspace_bytes(B, N, T, D, A, K, P, canonical_pairs=True):
     d = _abi.FusedBf16Desc()
     d.B, d.N, d.T, d.D, d.A, d.K, d.P = B, N, T, D, A, K, P
-    return _abi.lib().tspn_forward_fused_bf16_workspace_bytes(ctypes.byref(d))
+    l = _abi.lib()
+    return (l.tspn_forward_fused_bf16_workspace_bytes if canonical_pairs
+            else l.tspn_forward_fused_bf16_pairs_workspace_bytes)(ctypes.byref(d))
+
+
+def _unsupported(fn):
+    """The operand checks of the pair-list entries: what `_dev` refuses (dtype, device, layout) is reported the way the
+    library reports an operand it cannot take, TspnError(TSPN_EUNSUPPORTED)."""
+    try:
+        return fn()
+    except _abi.TspnError:
+        raise
+    except (TypeError, ValueError, RuntimeError) as exc:
+        raise _abi.TspnError(_abi.TSPN_EUNSUPPORTED, str(exc)) from exc
+
+
+def _check_pair_table(pairs, B, N, who):
+    """Host-synchronising test of a [P,2] table of global ids: every id in [0, B*N), both ids of a row in one video."""
+    if pairs.numel() == 0:
+        return
+    lo, hi = int(pairs.min()), int(pairs.max())
+    if lo < 0 or hi >= B * N:
+        raise IndexError(f"{who}: pair index out of range [0, {B * N}) (min {lo}, max {hi})")
+    if B > 1 and bool((torch.div(pairs[:, 0], N, rounding_mode="floor")
+                       != torch.div(pairs[:, 1], N, rounding_mode="floor")).any()):
+        raise IndexError(f"{who}: a pair joins tracklets of two different videos")
+
+
+def pair_plan(pairs, B, N):
+    """The plan of the bf16 pair-list stage (tspn_pair_plan_i32) for pairs int64 [P,2] (global ids, video = id // N):
+    dict of int32 tensors `s_list` / `o_list` [B,Np] (the distinct subjects / objects of each video, local ids,
+    ascending; Np = N rounded up to 16), `counts` [B,2], `head` [B,Np,Np] (first row of the chain of rows whose pair is
+    (s_list[b][i], o_list[b][j]), -1 for none) and `next` [P].  Rows with an id out of range or ids in two videos are on
+    no chain.  The order of a chain differs from run to run; the set of rows on it does not."""
+    _unsupported(lambda: _dev(pairs, "pairs", torch.int64))
+    if pairs.dim() != 2 or pairs.shape[1] != 2:
+        raise _abi.TspnError(_abi.TSPN_EUNSUPPORTED, "pair_plan: pairs must be [P,2]")
+    B, N, P = int(B), int(N), pairs.shape[0]
+    Np = (N + 15) // 16 * 16
+    i32 = dict(dtype=torch.int32, device=pairs.device)
+    plan = {"s_list": torch.empty((B, Np), **i32), "o_list": torch.empty((B, Np), **i32),
+            "counts": torch.empty((B, 2), **i32), "head": torch.empty((B, Np, Np), **i32), "next": torch.empty((P,), **i32)}
+    rank_ws = torch.empty((B, 2, max(N, 1)), **i32)
+    _abi.check(_abi.lib().tspn_pair_plan_i32(_p(pairs), P, B, N, _p(plan["s_list"]), _p(plan["o_list"]), _p(plan["counts"]),
+                                             _p(plan["head"]), _p(plan["next"]), _p(rank_ws), _stream()))
+    return plan
+
+
+def heads_pairlist_bf16(y, pairs, B, N, head_packed, head_b, H, check_pairs=True, out=None):
+    """Pair stage on y fp32 [B*N, T, ldm >= 2C] (U | V halves, C from head_packed) for ANY pair table: pairs int64 [P,2]
+    of global ids, any order, any subset, repeated rows and (s, s) rows allowed -> heads fp32 [P, H, T]; a row equals,
+    bit for bit, heads_pairgrid_bf16's row of the same (s, o).  `check_pairs` = the host-synchronising range and
+    same-video test (IndexError); without it a row that fails the test is skipped and its row of `out` left unwritten.
+    `out`: a contiguous fp32 [P, H, T] to write into."""
+    def operands():
+        _dev(y, "y"); _dev(pairs, "pairs", torch.int64)
+        _dev(head_packed, "head_packed", torch.bfloat16); _dev(head_b, "head_b")
+        if out is not None:
+            _dev(out, "out")
+    _unsupported(operands)
+    if y.dim() != 3 or pairs.dim() != 2 or pairs.shape[1] != 2 or head_packed.dim() != 3:
+        raise ValueError("heads_pairlist_bf16: y must be [B*N,T,ldm], pairs [P,2], head_packed [C/8,16,8]")
+    BN, T, ldm = y.shape
+    C = head_packed.shape[0] * 8
+    P = pairs.shape[0]
+    if BN != B * N or tuple(head_packed.shape[1:]) != (16, 8) or head_b.numel() != H:
+        raise ValueError("heads_pairlist_bf16: shape mismatch")
+    if check_pairs:
+        _check_pair_table(pairs, B, N, "heads_pairlist_bf16")
+    if out is None:
+        out = torch.empty((P, H, T), dtype=torch.float32, device=y.device)
+    elif tuple(out.shape) != (P, H, T):
+        raise ValueError("heads_pairlist_bf16: out shape mismatch")
+    l = _abi.lib()
+    need = l.tspn_heads_pairlist_bf16_workspace_bytes(B, N, P)
+    ws = _ws(need, y.device)
+    _abi.check(l.tspn_heads_pairlist_bf16(_p(y), ldm, B, N, C, T, _p(pairs), P, _p(head_packed), _p(head_b), H, _p(out),
+                                          _p(ws), ws.numel(), _stream()))
+    return out
 
 
 def forward_fused_bf16(feats, pairs, B, N, conv_packed, conv_bias, head_packed, head_b, cls_w, cls_b,
-                       workspace=None, conv_events=None, logits_event=None, out_heads=None, out_logits=None):
-    """Whole scoring pass, bf16 operands (tspn_forward_fused_bf16), canonical pair table only.
+                       workspace=None, conv_events=None, logits_event=None, out_heads=None, out_logits=None,
+                       canonical_pairs=True, check_pairs=True):
+    """Whole scoring pass, bf16 operands: tspn_forward_fused_bf16 on the canonical pair table (the default), or, with
+    `canonical_pairs=False`, tspn_forward_fused_bf16_pairs on any [P,2] table of global ids (pair-list stage; its
+    workspace is fused_bf16_workspace_bytes(..., canonical_pairs=False)).  `check_pairs` (pair tables only) = the
+    host-synchronising range and same-video test of heads_pairlist_bf16 (IndexError).
 
     feats bf16 [B*N,T,D]; conv_packed = pack_conv3_bf16(conv.weight, split=D); head_packed =
     pack_heads_bf16([3A,C]); cls_w fp32 [K,C] holding bf16-rounded values.
@@ -947,8 +1030,14 @@ def forward_fused_bf16(feats, pairs, B, N, conv_packed, conv_bias, head_packed, 
     if tuple(cls_w.shape) != (K, C) or conv_bias.numel() != C or cls_b.numel() != K:
         raise ValueError("forward_fused_bf16: classifier / bias shapes do not match")
     P = pairs.shape[0]
-    if tuple(pairs.shape) != (B * N * (N - 1), 2):
-        raise ValueError("forward_fused_bf16: needs the canonical pair table [B*N*(N-1), 2]")
+    if canonical_pairs:
+        if tuple(pairs.shape) != (B * N * (N - 1), 2):
+            raise ValueError("forward_fused_bf16: needs the canonical pair table [B*N*(N-1), 2]")
+    else:
+        if pairs.dim() != 2 or pairs.shape[1] != 2:
+            raise ValueError("forward_fused_bf16: pairs must be [P,2]")
+        if check_pairs:
+            _check_pair_table(pairs, B, N, "forward_fused_bf16")
     d = _abi.FusedBf16Desc()
     d.B, d.N, d.T, d.D, d.A, d.K, d.P = B, N, T, D, A, K, P
     d.feats, d.pairs = feats.data_ptr(), pairs.data_ptr()
@@ -956,7 +1045,8 @@ def forward_fused_bf16(feats, pairs, B, N, conv_packed, conv_bias, head_packed, 
     d.head_packed, d.head_b = head_packed.data_ptr(), head_b.data_ptr()
     d.cls_w, d.cls_b = cls_w.data_ptr(), cls_b.data_ptr()
     l = _abi.lib()
-    need = l.tspn_forward_fused_bf16_workspace_bytes(ctypes.byref(d))
+    need = (l.tspn_forward_fused_bf16_workspace_bytes if canonical_pairs
+            else l.tspn_forward_fused_bf16_pairs_workspace_bytes)(ctypes.byref(d))
     if workspace is None:
         workspace = _ws(need, feats.device)
     elif workspace.numel() * workspace.element_size() < need:
@@ -976,7 +1066,7 @@ def forward_fused_bf16(feats, pairs, B, N, conv_packed, conv_bias, head_packed, 
         d.ev_conv_begin, d.ev_conv_end = conv_events[0].cuda_event, conv_events[1].cuda_event
     if logits_event is not None:
         d.ev_logits_ready = logits_event.cuda_event
-    _abi.check(l.tspn_forward_fused_bf16(ctypes.byref(d), _stream()))
+    _abi.check((l.tspn_forward_fused_bf16 if canonical_pairs else l.tspn_forward_fused_bf16_pairs)(ctypes.byref(d), _stream()))
     return out_heads, out_logits
 
 

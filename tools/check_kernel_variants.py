@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Check a profiled test run against the kernel variant tables (tests/kernel_variants.py for csrc/*.hip,
-tests/eval_kernel_variants.py for csrc/eval/*.hip, tests/relations_kernel_variants.py for csrc/relations/*.hip).
+tests/eval_kernel_variants.py for csrc/eval/*.hip, tests/relations_kernel_variants.py for csrc/relations/*.hip,
+tests/pairlist_kernel_variants.py for csrc/pairlist/*.hip).
 
     rocprofv3 --kernel-trace --stats -d OUT -o run -- python -m pytest FILE... -q -m gpu
     python tools/check_kernel_variants.py OUT/.../run_kernel_stats.csv FILE...   (or OUT/.../run_results.db)
@@ -20,6 +21,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import eval_kernel_variants  # noqa: E402
 import kernel_variants  # noqa: E402
+import pairlist_kernel_variants  # noqa: E402
 import relations_kernel_variants  # noqa: E402
 
 BUILTIN = {"v": "void", "b": "bool", "c": "char", "a": "signed char", "h": "unsigned char", "s": "short",
@@ -128,7 +130,8 @@ def main(argv):
     calls = launched(argv[1])
     files = {rel(f) for f in argv[2:]}
     checked, missing = 0, []
-    for r in kernel_variants.VARIANTS + eval_kernel_variants.VARIANTS + relations_kernel_variants.VARIANTS:
+    for r in (kernel_variants.VARIANTS + eval_kernel_variants.VARIANTS + relations_kernel_variants.VARIANTS
+              + pairlist_kernel_variants.VARIANTS):
         if not any(node.partition("::")[0] in files for node in r["tests"]):
             continue
         checked += 1

@@ -9,7 +9,7 @@ offen` directly followed by `v_add_f32 v32, ...` stored the new v32 in some lane
 tspn_block_bf16.hip: ~0.02 % wrong outputs with several waves per SIMD, none with one; profiles/r5/
 bottleneck_block_study.md).
 
-This tool compiles every csrc/*.hip and csrc/relations/*.hip to assembly (hipcc -S --cuda-device-only, the build's flags) and reports every
+This tool compiles every csrc/*.hip, csrc/relations/*.hip and csrc/pairlist/*.hip to assembly (hipcc -S --cuda-device-only, the build's flags) and reports every
 buffer_store_dwordx3 / x4 with a register soffset whose data registers are written by a v_* instruction within the next
 `--window` instructions (default 3; LLVM inserts 2 wait states on gfx940 where it sees the hazard; the failing code had
 0 and 1).  s_nop N counts as N + 1; matrix instructions are not counted as writers (their results land tens of cycles
@@ -108,7 +108,8 @@ def main():
     ap.add_argument("--jobs", type=int, default=6)
     args = ap.parse_args()
     files = [os.path.abspath(f) for f in args.files] or sorted(glob.glob(os.path.join(CSRC, "*.hip")) +
-                                                                glob.glob(os.path.join(CSRC, "relations", "*.hip")))
+                                                                glob.glob(os.path.join(CSRC, "relations", "*.hip")) +
+                                                                glob.glob(os.path.join(CSRC, "pairlist", "*.hip")))
     bad = 0
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     flags = build_flags()
