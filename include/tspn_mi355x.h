@@ -46,7 +46,9 @@ extern "C" {
  * raise a fault that the NEXT launch entry reports without a synchronisation); tspn_fused_desc gained conv_weight /
  * conv_check at its END (the a-posteriori accuracy guard of the F(6,3) temporal conv, tspn_conv3_spot_check_f32).
  * Still 7 (additive, no layout or signature changed): tspn_pair_plan_i32, tspn_heads_pairlist_bf16 (+ _workspace_bytes),
- * tspn_forward_fused_bf16_pairs (+ _workspace_bytes): the bf16 path on an arbitrary pair table. */
+ * tspn_forward_fused_bf16_pairs (+ _workspace_bytes): the bf16 path on an arbitrary pair table;
+ * tspn_pack_span_cls_bf16, tspn_span_predicate_bf16, tspn_decode_span_relations_bf16 (+ _workspace_bytes): span pooling and
+ * the relations with their spans on bf16 segments. */
 #define TSPN_ABI_VERSION 7
 
 enum {
@@ -568,6 +570,46 @@ int tspn_heads_pairlist_bf16(const float* y, int64_t ldm, int64_t B, int64_t N, 
  * that cannot vouch for its table checks it first. */
 size_t tspn_forward_fused_bf16_pairs_workspace_bytes(const tspn_fused_bf16_desc* d);
 int tspn_forward_fused_bf16_pairs(const tspn_fused_bf16_desc* d, void* stream);
+
+/* ---- span pooling and span relations on bf16 segments (spanbf16/tspn_span_bf16.hip) ----
+ * tspn_span_predicate_f32 / tspn_decode_span_relations_f32 with the bf16 semantics of tspn_forward_fused_bf16
+ * (DESIGN.md 2, 4c).  feats bf16 [NT, T, D], D % 16 == 0; a row (s, o, span) pools the frames [a, e) that
+ * tspn_span_predicate_f32 pools (the same row rewrite) and gives
+ *   pooled_h[c] = bf16((float)(sum_{t in [a,e)} (double) f[h][t][c] / (double)(e - a)))             h = s, o
+ *   out[k]      = sigmoid(sum_c pooled_s[c] W16[k][c] + sum_c pooled_o[c] W16[k][D + c] + b16[k])
+ * with W16 / b16 the classifier rounded to bf16 (round to nearest even), exact products and fp32 accumulation on the bf16
+ * MFMAs.  A NaN / Inf frame reaches exactly the outputs of the spans that contain it; every other output has the bits of a
+ * launch on clean features.  An output depends on its own row only, wherever the row stands in the table.
+ *   tspn_pack_span_cls_bf16  cls_w fp32 [K, 2D] -> `packed`, ceil(K / 16) * 16 * 2D bf16, 16-byte aligned: fragment-major
+ *                            [ceil(K/16)][2D/32][64 lanes][8], rows past K zero.  cls_b stays fp32 [K] (or NULL); the
+ *                            kernels round it to bf16 themselves.
+ *   tspn_span_predicate_bf16 pairs int64 [P,2] global tracklet ids (any table: repeated rows, (i, i)), spans int64 [P,2] ->
+ *                            out fp32 [P, K].  Workspace (256-byte aligned): float64 prefix sums [NT, T+1, D] and the pooled
+ *                            rows bf16 [P, 2D].
+ *   tspn_decode_span_relations_bf16  the arguments, the selection and the outputs of tspn_decode_span_relations_f32;
+ *                            q[p, j, k] is what tspn_span_predicate_bf16 returns for (pair p, spans[p, j]), bit for bit.
+ *                            Its workspace also holds q fp32 [S*P*J, K] and the three candidate arrays.
+ * A tracklet id out of range is NOT refused and not detected: the kernels clamp the global id (for the relations
+ * seg * N + the segment-local id) into [0, NT) resp. [0, S*N), so nothing outside feats is read and the row holds the
+ * values of whichever tracklet the clamped id names.  A caller that cannot vouch for its table checks it first (ops.py does).
+ * TSPN_EUNSUPPORTED: D % 16 != 0, feats / cls_packed not 16-byte aligned, a workspace not 256-byte aligned, and for the
+ * relations K > 256, topk_per_seg > 1024, J > 16, P*J*min(topk_per_span, K) >= 2^31.  TSPN_EINVAL: a null pointer.
+ * TSPN_EWORKSPACE: a short workspace.  All are answered before any device work; P == 0 or NT == 0 (S == 0) is TSPN_OK
+ * without a launch. */
+int tspn_pack_span_cls_bf16(const float* cls_w, int64_t K, int64_t D, uint16_t* packed, void* stream);
+size_t tspn_span_predicate_bf16_workspace_bytes(int64_t NT, int64_t T, int64_t D, int64_t K, int64_t P);
+int tspn_span_predicate_bf16(const uint16_t* feats, int64_t NT, int64_t T, int64_t D, const int64_t* pairs,
+                             const int64_t* spans, int64_t P, const uint16_t* cls_packed, const float* cls_b,
+                             int64_t K, float* out, void* workspace, size_t workspace_bytes, void* stream);
+size_t tspn_decode_span_relations_bf16_workspace_bytes(int64_t S, int64_t N, int64_t T, int64_t D, int64_t P, int64_t J,
+                                                       int64_t K, int64_t topk_per_span);
+int tspn_decode_span_relations_bf16(const uint16_t* feats, int64_t S, int64_t N, int64_t T, int64_t D,
+                                    const int64_t* pairs, int64_t P, const int64_t* spans, const float* span_scores,
+                                    const int64_t* span_counts, int64_t J, const uint16_t* cls_packed,
+                                    const float* cls_b, int64_t K, const float* cls_logits, int64_t NO,
+                                    int64_t topk_per_span, int64_t topk_per_seg, float* out_score, int64_t* out_triplet,
+                                    int64_t* out_pair_tid, int64_t* out_span, int64_t* out_span_rank,
+                                    int64_t* out_valid, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---- dense reference-faithful encoder + heads on a materialised [P,C,T] --
  * DPNHead.forward (lib/modeling/relpn/dpn.py:69-73) on arbitrary pair feats:

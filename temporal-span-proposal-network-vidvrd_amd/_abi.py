@@ -175,6 +175,12 @@ PROTOTYPES = {
     "tspn_heads_pairlist_bf16": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "tspn_forward_fused_bf16_pairs_workspace_bytes": (_sz, [ctypes.POINTER(FusedBf16Desc)]),
     "tspn_forward_fused_bf16_pairs": (_int, [ctypes.POINTER(FusedBf16Desc), _vp]),
+    "tspn_pack_span_cls_bf16": (_int, [_vp, _i64, _i64, _vp, _vp]),
+    "tspn_span_predicate_bf16_workspace_bytes": (_sz, [_i64] * 5),
+    "tspn_span_predicate_bf16": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "tspn_decode_span_relations_bf16_workspace_bytes": (_sz, [_i64] * 8),
+    "tspn_decode_span_relations_bf16": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64,
+                                               _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "tspn_eval_traj_volume_f64": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "tspn_eval_viou_f64": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "tspn_eval_greedy_match_f64": (_int, [_vp, _vp, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _vp]),

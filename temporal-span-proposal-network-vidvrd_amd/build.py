@@ -19,6 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 CSRC_EVAL = os.path.join(CSRC, "eval")   # evaluation kernels (their variant table: tests/eval_kernel_variants.py)
 CSRC_REL = os.path.join(CSRC, "relations")   # span relation decode (its variant table: tests/relations_kernel_variants.py)
 CSRC_PAIRLIST = os.path.join(CSRC, "pairlist")   # bf16 pair-list stage (its variant table: tests/pairlist_kernel_variants.py)
+CSRC_SPANBF16 = os.path.join(CSRC, "spanbf16")   # bf16 span pooling / span relations (its variant table: tests/spanbf16_kernel_variants.py)
 LIB_NAME = "libtspn_mi355x.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 ARCH = "gfx950"
@@ -47,12 +48,14 @@ NO_SPILL_KERNELS = ("conv3_wino63_kernel", "heads_pairgrid4_kernel", "heads_pair
 
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC_EVAL, "*.hip")) +
-                  glob.glob(os.path.join(CSRC_REL, "*.hip")) + glob.glob(os.path.join(CSRC_PAIRLIST, "*.hip")))
+                  glob.glob(os.path.join(CSRC_REL, "*.hip")) + glob.glob(os.path.join(CSRC_PAIRLIST, "*.hip")) +
+                  glob.glob(os.path.join(CSRC_SPANBF16, "*.hip")))
 
 
 def _headers():
     return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC_EVAL, "*.h")) + \
         glob.glob(os.path.join(CSRC_REL, "*.h")) + glob.glob(os.path.join(CSRC_PAIRLIST, "*.h")) + \
+        glob.glob(os.path.join(CSRC_SPANBF16, "*.h")) + \
         glob.glob(os.path.join(ROOT, "include", "*.h")) + \
         [os.path.abspath(__file__)]
 

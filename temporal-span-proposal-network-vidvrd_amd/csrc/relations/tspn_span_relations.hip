@@ -13,7 +13,8 @@
 //            tspn::wave_row_topk (tspn_topk_select.h); writes R x (key of the product, product, k).  A row
 //            j >= count[p] writes tspn::kPadKey, below every real key: [rows, K] never reaches HBM
 //   kernel c one workgroup per segment: tspn::select_topk_sorted over the P*J*R keys, then the gathers (pair ids,
-//            predicate, class argmax, span, span rank)
+//            predicate, class argmax, span, span rank); its launch is tspn::segment_span_topk, which the bf16 entry
+//            (spanbf16/tspn_span_bf16.hip) ends with too
 #include <algorithm>
 
 #include "tspn_common.h"
@@ -113,17 +114,27 @@ __global__ __launch_bounds__(tspn::kSelectThreads) void segment_span_topk_kernel
   }
 }
 
-size_t cand_bytes(int64_t S, int64_t P, int64_t J, int64_t R) {
-  return tspn::align_up((size_t)S * P * J * R * sizeof(float), 256);   // one of the three arrays (key, product, k)
-}
+using tspn::span_cand_bytes;   // one of the three arrays (key, product, k)
 
 }  // namespace
+
+int tspn::segment_span_topk(const unsigned* key, const float* sc, const int* ix, const int64_t* pairs,
+                            const int64_t* spans, const int64_t* span_counts, const float* cls_logits, int64_t S,
+                            int64_t N, int64_t NO, int64_t P, int64_t J, int64_t R, int64_t topk_per_seg,
+                            float* out_score, int64_t* out_triplet, int64_t* out_pair_tid, int64_t* out_span,
+                            int64_t* out_span_rank, int64_t* out_valid, void* stream, const char* what) {
+  const int64_t mcap = std::min<int64_t>(topk_per_seg, P * J * R);
+  hipLaunchKernelGGL(segment_span_topk_kernel, dim3((unsigned)S), dim3(tspn::kSelectThreads), 0, TSPN_STREAM(stream), key,
+                     sc, ix, pairs, spans, span_counts, cls_logits, (int)N, (int)NO, (int)P, (int)J, (int)R, (int)mcap,
+                     (int)topk_per_seg, out_score, out_triplet, out_pair_tid, out_span, out_span_rank, out_valid);
+  return tspn::check_launch(what);
+}
 
 extern "C" size_t tspn_decode_span_relations_workspace_bytes(int64_t S, int64_t N, int64_t T, int64_t D, int64_t P,
                                                              int64_t J, int64_t K, int64_t topk_per_span) {
   if (S <= 0 || N <= 0 || T <= 0 || D <= 0 || P <= 0 || J <= 0 || K <= 0 || topk_per_span <= 0) return 0;
   const int64_t R = std::min<int64_t>(topk_per_span, K);
-  return tspn::align_up(tspn::span_prefix_workspace_bytes(S * N, T, D, K), 256) + 3 * cand_bytes(S, P, J, R);
+  return tspn::align_up(tspn::span_prefix_workspace_bytes(S * N, T, D, K), 256) + 3 * span_cand_bytes(S, P, J, R);
 }
 
 extern "C" int tspn_decode_span_relations_f32(const float* feats, int64_t S, int64_t N, int64_t T, int64_t D,
@@ -154,7 +165,7 @@ extern "C" int tspn_decode_span_relations_f32(const float* feats, int64_t S, int
                    out_triplet && out_pair_tid && out_span && out_span_rank && out_valid,
                TSPN_EINVAL, "%s: null pointer", who);
   const size_t pre = tspn::align_up(tspn::span_prefix_workspace_bytes(S * N, T, D, K), 256);
-  const size_t cb = cand_bytes(S, P, J, R);
+  const size_t cb = span_cand_bytes(S, P, J, R);
   TSPN_REQUIRE(workspace && workspace_bytes >= pre + 3 * cb, TSPN_EWORKSPACE, "%s: workspace %zu < %zu bytes", who,
                workspace_bytes, pre + 3 * cb);
   const int64_t rows = S * P * J;
@@ -172,9 +183,7 @@ extern "C" int tspn_decode_span_relations_f32(const float* feats, int64_t S, int
   hipLaunchKernelGGL(span_row_topk_kernel, dim3((unsigned)nb), dim3(256), 0, s, PS, G, pairs, spans, span_scores,
                      span_counts, cls_b, rows, (int)N, (int)P, (int)J, (int)T, (int)K, (int)R, key, sc, ix);
   if ((rc = tspn::check_launch("tspn_decode_span_relations_f32(rows)"))) return rc;
-  const int64_t mcap = std::min<int64_t>(topk_per_seg, P * J * R);
-  hipLaunchKernelGGL(segment_span_topk_kernel, dim3((unsigned)S), dim3(tspn::kSelectThreads), 0, s, key, sc, ix, pairs,
-                     spans, span_counts, cls_logits, (int)N, (int)NO, (int)P, (int)J, (int)R, (int)mcap,
-                     (int)topk_per_seg, out_score, out_triplet, out_pair_tid, out_span, out_span_rank, out_valid);
-  return tspn::check_launch("tspn_decode_span_relations_f32(segment)");
+  return tspn::segment_span_topk(key, sc, ix, pairs, spans, span_counts, cls_logits, S, N, NO, P, J, R, topk_per_seg,
+                                 out_score, out_triplet, out_pair_tid, out_span, out_span_rank, out_valid, stream,
+                                 "tspn_decode_span_relations_f32(segment)");
 }

@@ -139,6 +139,17 @@ size_t span_prefix_workspace_bytes(int64_t NT, int64_t T, int64_t D, int64_t K);
 int span_prefix_stage(const float* feats, int64_t NT, int64_t T, int64_t D, const float* cls_w, int64_t K,
                       void* workspace, size_t workspace_bytes, void* stream, const float** G_out,
                       const double** PS_out, const char* who);
+// Last stage of the span relation decode (relations/tspn_span_relations.hip), shared by tspn_decode_span_relations_f32
+// and tspn_decode_span_relations_bf16: per segment the topk_per_seg best of the P*J*R candidates a row top-k left in
+// key / sc / ix (each [S, P*J*R], span_cand_bytes() apart in the entries' workspaces), and the gathers.
+inline size_t span_cand_bytes(int64_t S, int64_t P, int64_t J, int64_t R) {
+  return align_up((size_t)S * P * J * R * sizeof(float), 256);
+}
+int segment_span_topk(const unsigned* key, const float* sc, const int* ix, const int64_t* pairs, const int64_t* spans,
+                      const int64_t* span_counts, const float* cls_logits, int64_t S, int64_t N, int64_t NO, int64_t P,
+                      int64_t J, int64_t R, int64_t topk_per_seg, float* out_score, int64_t* out_triplet,
+                      int64_t* out_pair_tid, int64_t* out_span, int64_t* out_span_rank, int64_t* out_valid, void* stream,
+                      const char* what);
 
 }  // namespace tspn
 

@@ -1,5 +1,6 @@
 // Span pooling, the per-(row, predicate) expression: shared by span_combine_kernel (tspn_linear.hip) and
-// span_row_topk_kernel (relations/tspn_span_relations.hip), which must return the same fp32 bits.
+// span_row_topk_kernel (relations/tspn_span_relations.hip), which must return the same fp32 bits; and the
+// row rewrite span_frames, which the bf16 span path (spanbf16/tspn_span_bf16.hip) takes from here too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -7,6 +8,13 @@
 #include <cstdint>
 
 namespace tspn {
+
+// The frames [a, e) a span row (a0, e0) pools over on a segment of T frames (oracle.span_frames):
+// out-of-range / unused (-1) spans fall back to the whole segment / one frame, so 0 <= a < e <= T for any row.
+__device__ inline void span_frames(int64_t a0, int64_t e0, int T, int64_t& a, int64_t& e) {
+  a = a0 < 0 ? 0 : (a0 > T - 1 ? T - 1 : a0);
+  e = e0 < a + 1 ? (a0 < 0 ? T : a + 1) : (e0 > T ? T : e0);
+}
 
 // Sum of G over the frames [a, e) of one (tracklet, column) in float64, in frame order: what PS[e] - PS[a] is when
 // both are finite.  span_logit takes it when the running sum of span_prefix_kernel has met a NaN / Inf in an
@@ -22,9 +30,8 @@ __device__ inline double span_sum_frames(const float* __restrict__ g, int64_t K2
 __device__ inline float span_logit(const double* __restrict__ PS, const float* __restrict__ G, int64_t s, int64_t o,
                                    int64_t a0, int64_t e0, int T, int64_t K2, int64_t k,
                                    const float* __restrict__ b) {
-  int64_t a = a0, e = e0;
-  a = a < 0 ? 0 : (a > T - 1 ? T - 1 : a);       // out-of-range / unused (-1) spans fall back to
-  e = e < a + 1 ? (a0 < 0 ? T : a + 1) : (e > T ? T : e);  // the whole segment / one frame
+  int64_t a, e;
+  span_frames(a0, e0, T, a, e);
   const double* ps = PS + (s * (T + 1)) * K2 + 2 * k;
   const double* po = PS + (o * (T + 1)) * K2 + 2 * k + 1;
   // a prefix value is non-finite from the first NaN / Inf frame on (PS[a] non-finite implies PS[e] non-finite), so

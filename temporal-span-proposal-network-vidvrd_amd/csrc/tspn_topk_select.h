@@ -1,7 +1,8 @@
 // The one home of selection ("Top-k ties" and "Selection": larger tspn::order_key first, lower index on ties,
 // key 0 below every real key).  Users:
 //   bitonic_sort_desc    ppn_kernel (tspn_ppn.hip), decode_spans_kernel (tspn_spans.hip), select_topk_sorted below
-//   wave_row_topk        pair_topk_kernel (tspn_decode.hip), span_row_topk_kernel (relations/tspn_span_relations.hip)
+//   wave_row_topk        pair_topk_kernel (tspn_decode.hip), span_row_topk_kernel (relations/tspn_span_relations.hip),
+//                        span_row_topk_q_kernel (spanbf16/tspn_span_bf16.hip)
 //   select_topk_sorted   segment_topk_kernel (tspn_decode.hip), segment_span_topk_kernel
 //                        (relations/tspn_span_relations.hip): exact top-M of Q keyed candidates by one workgroup, in
 //                        torch's stable descending order

@@ -1117,8 +1117,7 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                 continue
             if bf16:
                 # bf16 tracklet features select the bf16-operand kernels (BASELINE config 3); a member with its own
-                # 'tracklet_pairs' sends the group through the pair-list stage (RELPN.DPN.POOL_TOP_SPAN is not applied
-                # on bf16 segments: DESIGN.md §8)
+                # 'tracklet_pairs' sends the group through the pair-list stage
                 if d % 16:
                     raise ValueError(f"the bf16 path needs D % 16 == 0 (D={d})")
                 feats = _batch_rows(src, dev, torch.bfloat16)
@@ -1135,6 +1134,11 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                                                    workspace=self._workspace(dev, need), conv_events=self._conv_events,
                                                    logits_event=ev_logits if (overlap and len(groups) == 1) else None,
                                                    canonical_pairs=canonical, check_pairs=False)
+                if self.pool_top_span and allp.shape[0]:
+                    # RelOIPool over each pair's best span, bf16 semantics: canonical and custom tables alike
+                    top = ops.decode_spans(heads, self.anchor_sizes(t), top_k=1)["span"][:, 0].contiguous()
+                    cpk, cb16s = self._span_cls_bf16(dev)
+                    lg = ops.span_predicate_bf16(feats, allp, top, cpk, cb16s, cls.weight.shape[0])
             else:
                 feats = _batch_rows(src, dev)
                 allp, counts, canonical = self._group_pair_table([custom_pairs(pair_list[i]) for i in members], dev, n)
@@ -1157,7 +1161,7 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                     # RelOIPool over each pair's best span (decode + NMS, top-1) instead of the whole segment
                     top = ops.decode_spans(heads, self.anchor_sizes(t), top_k=1)["span"][:, 0].contiguous()
                     lg = ops.span_predicate(feats, allp, top, cw, cb)
-            if overlap and len(groups) == 1 and not (self.pool_top_span and not bf16):
+            if overlap and len(groups) == 1 and not self.pool_top_span:
                 # `decode` may start behind the logits-ready event of THIS pass (same logits tensor, same caller stream)
                 # (the token keeps `lg` alive: its address cannot be handed to another tensor while the token stands)
                 self._logits_token = (dev.index, lg, main.cuda_stream)
@@ -1416,10 +1420,19 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
             out.append({k: v.to(heads.device) for k, v in res.items()})
         return out
 
+    def _span_cls_bf16(self, dev):
+        """(packed bf16 classifier of the bf16 span entries, its bias rounded to bf16 as fp32), cached beside "cls_bf16"."""
+        cls = self.classifier.rel_predictor
+        return self.classifier._cache.get(
+            "cls_span_bf16", (cls.weight, cls.bias), dev,
+            lambda ts: (ops.pack_span_cls_bf16(ts[0].contiguous()), ops.cast_bf16(ts[1].contiguous()).float()))
+
     def classify_spans(self, pair_list, spans):
         """Predicate logits with RelOIPool restricted to given spans: per segment `spans[i]` int64 [P,2]
         frames [start,end) (e.g. decode_spans(...)[i]["span"][:, j]); the build-defined meaning of
-        RelOIPool.__call__(feats, duration_proposals) (reference model.py:68-73) + RelationPredictor."""
+        RelOIPool.__call__(feats, duration_proposals) (reference model.py:68-73) + RelationPredictor.  A segment whose
+        'tracklet_feats' are bf16 (D % 16 == 0) is pooled and classified with the bf16 semantics of `forward`
+        (DESIGN.md §2): its logits equal forward's RELPN.DPN.POOL_TOP_SPAN logits for the same spans, bit for bit."""
         cls = self.classifier.rel_predictor
         out = []
         with torch.no_grad():
@@ -1434,6 +1447,13 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                 else:
                     p = ops.pair_index(n, dev)
                 sp = (sp if isinstance(sp, torch.Tensor) else torch.as_tensor(np.asarray(sp))).long().to(dev)
+                if isinstance(f, torch.Tensor) and f.dtype == torch.bfloat16:
+                    if f.shape[2] % 16:
+                        raise ValueError(f"the bf16 path needs D % 16 == 0 (D={f.shape[2]})")
+                    cpk, cb16 = self._span_cls_bf16(dev)
+                    out.append(ops.span_predicate_bf16(f.to(dev).contiguous(), p.contiguous(), sp.contiguous(), cpk, cb16,
+                                                       cls.weight.shape[0]).to(f.device))
+                    continue
                 out.append(ops.span_predicate(_f32(f, dev), p.contiguous(), sp.contiguous(), cw, cb).to(f.device))
         return out
 
@@ -1446,8 +1466,8 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
         predicate, object class), pair_tids int64 [M,2], spans int64 [M,2] frames [start, end) inside the segment), in
         descending score order, on the device of the segment's 'tracklet_feats'.  Needs the tracklet fields
         ('tracklet_feats' [N,T,D], 'track_cls_logits' [N,num_obj]); honours 'tracklet_pairs'.  Segments with fewer than
-        2 tracklets or no pair yield empty results.  Equal-shape segments share one launch; everything runs on the
-        caller's stream."""
+        2 tracklets or no pair yield empty results.  Equal-shape segments of one feature dtype share one launch; bf16
+        'tracklet_feats' (D % 16 == 0) take the bf16 entries and semantics; everything runs on the caller's stream."""
         cls = self.classifier.rel_predictor
         out = [None] * len(pair_list)
         groups = {}
@@ -1466,8 +1486,11 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                 c = plist.get_field("track_cls_logits")
                 if tuple(c.shape) != (n, num_obj):
                     raise ValueError(f"decode_span_relations: segment {i}: 'track_cls_logits' must be [{n},{num_obj}], got {tuple(c.shape)}")
-                groups.setdefault((tuple(f.shape), tuple(heads.shape)), []).append(i)
-            for (fshape, hshape), members in groups.items():
+                bf16 = isinstance(f, torch.Tensor) and f.dtype == torch.bfloat16
+                if bf16 and f.shape[2] % 16:
+                    raise ValueError(f"the bf16 path needs D % 16 == 0 (D={f.shape[2]})")
+                groups.setdefault((tuple(f.shape), tuple(heads.shape), bf16), []).append(i)
+            for (fshape, hshape, bf16), members in groups.items():
                 n, nm = fshape[0], len(members)
                 dev = _compute_device(*[pair_list[i].get_field("tracklet_feats") for i in members], cls.weight)
                 cw, cb = self.classifier._cache.get("cls", (cls.weight, cls.bias), dev, lambda ts: ts)
@@ -1482,10 +1505,18 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                 heads = _batch_rows([duration_proposals[i].heads for i in members], dev)
                 sz = sizes if sizes is not None else self.anchor_sizes(hshape[2])
                 sp = ops.decode_spans(heads, sz, top_k=spans_per_pair, nms_threshold=nms_threshold)
-                feats = _batch_rows([pair_list[i].get_field("tracklet_feats") for i in members], dev)
+                feats = _batch_rows([pair_list[i].get_field("tracklet_feats") for i in members], dev,
+                                    torch.bfloat16 if bf16 else torch.float32)
                 clog = _batch_rows([pair_list[i].get_field("track_cls_logits") for i in members], dev).view(nm, n, num_obj)
-                res = ops.decode_span_relations(feats, pairs, sp["span"], sp["score"], sp["count"], cw, cb, clog,
-                                                topk_per_span=topk_per_span, topk_per_seg=topk_per_seg, check_pairs=False)
+                if bf16:
+                    cpk, cb16 = self._span_cls_bf16(dev)
+                    res = ops.decode_span_relations_bf16(feats, pairs, sp["span"], sp["score"], sp["count"], cpk, cb16,
+                                                         cls.weight.shape[0], clog, topk_per_span=topk_per_span,
+                                                         topk_per_seg=topk_per_seg, check_pairs=False)
+                else:
+                    res = ops.decode_span_relations(feats, pairs, sp["span"], sp["score"], sp["count"], cw, cb, clog,
+                                                    topk_per_span=topk_per_span, topk_per_seg=topk_per_seg,
+                                                    check_pairs=False)
                 valid = res[5].tolist()
                 for k, i in enumerate(members):
                     tgt = pair_list[i].get_field("tracklet_feats").device

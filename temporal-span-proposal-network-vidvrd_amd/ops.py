@@ -19,7 +19,8 @@ __all__ = [
     "cast_bf16", "pack_conv3_bf16", "pack_heads_bf16", "conv3_tc_bf16", "heads_pairgrid_bf16",
     "pair_plan", "heads_pairlist_bf16",
     "transpose_cast_bf16", "temporal_encoder_heads_bf16",
-    "temporal_mean_bf16", "forward_fused_bf16", "span_predicate", "bottleneck_block_bf16", "bottleneck_block_proj_bf16", "bottleneck_block_res_bf16",
+    "temporal_mean_bf16", "forward_fused_bf16", "span_predicate",
+    "pack_span_cls_bf16", "span_predicate_bf16", "decode_span_relations_bf16", "bottleneck_block_bf16", "bottleneck_block_proj_bf16", "bottleneck_block_res_bf16",
     "proposal_pair_filter", "gather_rows", "wino63_set_piece_form", "wino63_f16x3_set_tail_split", "conv3_spot_check",
     "pack_conv2d", "pack_conv2d_frag", "conv2d_nhwc", "roi_align_nhwc", "pack_conv2d_frag_bf16", "conv2d_nhwc_bf16", "max_pool_nhwc", "pack_conv2d_frag_cin4", "conv2d_nhwc_cin4", "max_pool_nhwc_bf16", "pack_stem_bf16", "stem_conv_bf16", "stem_pool_bf16", "bottleneck_tail_bf16",
     "eval_traj_volume", "eval_viou", "eval_greedy_match",
@@ -1151,6 +1152,114 @@ def decode_span_relations(feats, pairs, spans, span_scores, span_counts, cls_w, 
                                                 _p(span_counts), J, _p(cls_w), _p(cls_b), K, _p(cls_logits), NO,
                                                 int(topk_per_span), int(topk_per_seg), *[_p(t) for t in out],
                                                 _p(ws), ws.numel(), _stream()))
+    return tuple(out)
+
+
+def pack_span_cls_bf16(cls_w):
+    """Classifier weight fp32 [K, 2D] (D % 16 == 0) -> the packed bf16 image of the bf16 span entries
+    (tspn_pack_span_cls_bf16): [ceil(K/16), 2D/32, 64, 8], fragment-major, rounded to nearest even, rows past K zero."""
+    _dev(cls_w, "cls_w")
+    if cls_w.dim() != 2 or cls_w.shape[1] % 2:
+        raise ValueError("pack_span_cls_bf16: cls_w must be [K, 2D]")
+    K, D = cls_w.shape[0], cls_w.shape[1] // 2
+    if K < 1 or D < 1 or D % 16:
+        raise ValueError(f"the bf16 path needs D % 16 == 0 (D={D})")
+    packed = torch.empty(((K + 15) // 16, 2 * D // 32, 64, 8), dtype=torch.bfloat16, device=cls_w.device)
+    _abi.check(_abi.lib().tspn_pack_span_cls_bf16(_p(cls_w), K, D, _p(packed), _stream()))
+    return packed
+
+
+def _span_cls_packed(cls_packed, cls_b, K, D, who):
+    _dev(cls_packed, "cls_packed", torch.bfloat16)
+    if cls_b is not None:
+        _dev(cls_b, "cls_b")
+    K = int(K)
+    if D % 16:
+        raise ValueError(f"the bf16 path needs D % 16 == 0 (D={D})")
+    if K < 1 or tuple(cls_packed.shape) != ((K + 15) // 16, 2 * D // 32, 64, 8) or (cls_b is not None and tuple(cls_b.shape) != (K,)):
+        raise ValueError(f"{who}: cls_packed must be pack_span_cls_bf16 of a [K={K}, 2D={2 * D}] weight and cls_b [K]")
+    return K
+
+
+def span_predicate_bf16(feats, pairs, spans, cls_packed, cls_b, K, out=None, workspace=None):
+    """Span-restricted RelOIPool + predicate head on a bf16 segment (tspn_span_predicate_bf16): feats
+    bf16 [NT,T,D] (D % 16 == 0), pairs int64 [P,2] global tracklet ids (any table: repeated rows, (i, i)), spans int64
+    [P,2] frames [start,end), cls_packed = pack_span_cls_bf16(cls_w [K,2D]), cls_b fp32 [K] or None (rounded to bf16 by
+    the kernel) -> sigmoid logits fp32 [P,K].  `out`: a contiguous fp32 [P,K] to write into; `workspace`: a uint8 tensor
+    of at least tspn_span_predicate_bf16_workspace_bytes."""
+    _dev(feats, "feats", torch.bfloat16); _dev(pairs, "pairs", torch.int64); _dev(spans, "spans", torch.int64)
+    if feats.dim() != 3:
+        raise ValueError("span_predicate_bf16: feats must be [NT,T,D]")
+    NT, T, D = feats.shape
+    K = _span_cls_packed(cls_packed, cls_b, K, D, "span_predicate_bf16")
+    P = pairs.shape[0]
+    if tuple(pairs.shape) != (P, 2) or tuple(spans.shape) != (P, 2):
+        raise ValueError("span_predicate_bf16: shape mismatch")
+    if P and (int(pairs.min()) < 0 or int(pairs.max()) >= NT):
+        raise IndexError("span_predicate_bf16: pair index out of range")
+    if out is None:
+        out = torch.empty((P, K), dtype=torch.float32, device=feats.device)
+    elif tuple(_dev(out, "out").shape) != (P, K):
+        raise ValueError("span_predicate_bf16: out shape mismatch")
+    l = _abi.lib()
+    need = l.tspn_span_predicate_bf16_workspace_bytes(NT, T, D, K, P)
+    if workspace is None:
+        workspace = _ws(need, feats.device)
+    elif workspace.numel() * workspace.element_size() < need:
+        raise ValueError("span_predicate_bf16: workspace too small")
+    _abi.check(l.tspn_span_predicate_bf16(_p(feats), NT, T, D, _p(pairs), _p(spans), P, _p(cls_packed), _p(cls_b), K,
+                                          _p(out), _p(workspace), workspace.numel() * workspace.element_size(), _stream()))
+    return out
+
+
+def decode_span_relations_bf16(feats, pairs, spans, span_scores, span_counts, cls_packed, cls_b, K, cls_logits,
+                               topk_per_span=20, topk_per_seg=200, check_pairs=True, out=None):
+    """decode_span_relations for S equal-shape bf16 segments (tspn_decode_span_relations_bf16): feats bf16 [S,N,T,D] (or
+    [S*N,T,D]), cls_packed = pack_span_cls_bf16(cls_w [K,2D]), cls_b fp32 [K] or None; every other argument and the six
+    results as decode_span_relations.  A candidate's predicate value is span_predicate_bf16's for that (pair, span) row,
+    bit for bit."""
+    _dev(feats, "feats", torch.bfloat16); _dev(pairs, "pairs", torch.int64); _dev(spans, "spans", torch.int64)
+    _dev(span_scores, "span_scores"); _dev(span_counts, "span_counts", torch.int64); _dev(cls_logits, "cls_logits")
+    if pairs.dim() != 3 or pairs.shape[2] != 2 or cls_logits.dim() != 3 or cls_logits.shape[0] != pairs.shape[0]:
+        raise ValueError("decode_span_relations_bf16: pairs must be [S,P,2] and cls_logits [S,N,num_obj]")
+    S, P, _ = pairs.shape
+    N, NO = cls_logits.shape[1], cls_logits.shape[2]
+    if feats.dim() == 4:
+        feats = feats.view(-1, feats.shape[2], feats.shape[3])
+    if feats.dim() != 3 or feats.shape[0] != S * N:
+        raise ValueError(f"decode_span_relations_bf16: feats must hold S*N = {S * N} tracklets [S*N,T,D], got {tuple(feats.shape)}")
+    T, D = feats.shape[1], feats.shape[2]
+    K = _span_cls_packed(cls_packed, cls_b, K, D, "decode_span_relations_bf16")
+    if spans.dim() < 3 or spans.shape[-1] != 2:
+        raise ValueError("decode_span_relations_bf16: spans must be [S*P,J,2]")
+    J = spans.shape[-2]
+    if spans.numel() != S * P * J * 2 or span_scores.numel() != S * P * J or span_counts.numel() != S * P \
+            or (span_scores.numel() and span_scores.shape[-1] != J):
+        raise ValueError(f"decode_span_relations_bf16: spans [S*P,J,2], span_scores [S*P,J] and span_counts [S*P] expected "
+                         f"for S*P = {S * P}, J = {J}")
+    if check_pairs and S * P and (int(pairs.min()) < 0 or int(pairs.max()) >= N):
+        raise IndexError("decode_span_relations_bf16: tracklet id outside the segment")
+    R = min(int(topk_per_span), K)
+    Mc = min(int(topk_per_seg), P * J * R)
+    dev = feats.device
+    shapes = (((S, Mc), torch.float32), ((S, Mc, 3), torch.int64), ((S, Mc, 2), torch.int64), ((S, Mc, 2), torch.int64),
+              ((S, Mc), torch.int64), ((S,), torch.int64))
+    if out is None:
+        out = tuple(torch.empty(sh, dtype=dt, device=dev) for sh, dt in shapes)
+        if S * P == 0:
+            out[5].zero_()                       # nothing is launched
+    else:
+        if len(out) != 6:
+            raise ValueError("decode_span_relations_bf16: out must be the six result tensors")
+        for t, (sh, dt), name in zip(out, shapes, ("scores", "triplets", "pair_tids", "spans", "span_rank", "valid")):
+            if tuple(_dev(t, "out." + name, dt).shape) != sh:
+                raise ValueError(f"decode_span_relations_bf16: out.{name} must be {sh}")
+    l = _abi.lib()
+    ws = _ws(l.tspn_decode_span_relations_bf16_workspace_bytes(S, N, T, D, P, J, K, int(topk_per_span)), dev)
+    _abi.check(l.tspn_decode_span_relations_bf16(_p(feats), S, N, T, D, _p(pairs), P, _p(spans), _p(span_scores),
+                                                 _p(span_counts), J, _p(cls_packed), _p(cls_b), K, _p(cls_logits), NO,
+                                                 int(topk_per_span), int(topk_per_seg), *[_p(t) for t in out],
+                                                 _p(ws), ws.numel(), _stream()))
     return tuple(out)
 
 
