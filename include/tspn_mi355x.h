@@ -14,6 +14,17 @@
  *     allocator); the library borrows them for the duration of the call and
  *     allocates nothing.  Scratch space is passed in explicitly (see the
  *     *_workspace_bytes helpers).
+ *   - The workspace contract, for every entry that takes a `workspace` (as a parameter or as a member of its
+ *     descriptor): a workspace may hold ANYTHING on entry -- the library clears what it needs cleared -- and its
+ *     contents are unspecified on return; the `need` bytes its *_workspace_bytes helper returns for the same shape
+ *     suffice, and nothing outside them is touched; a shorter workspace (or none, where need > 0) is refused with
+ *     TSPN_EWORKSPACE (a null one possibly with TSPN_EINVAL) before any device work, outputs and workspace untouched.
+ *     A helper returns 0 where its own arguments already say that the entry refuses the shape or has nothing to do
+ *     (tests/test_workspace_contract_table.py pins which).  One buffer may therefore serve
+ *     calls of different entries and shapes one after the other on a stream.  The two scratch arguments that are NOT
+ *     a workspace in this sense say so where they are declared: `det_ws` of tspn_eval_greedy_match_f64 and `scratch`
+ *     of the stand-alone tspn_conv3_spot_check_f32 are zeroed by the caller.  (tests/workspace_contracts.py has the
+ *     layouts; tests/test_gpu_workspace_contract.py holds every entry to this.)
  *   - All tensors are dense, row-major, fp32 unless stated; sizes are int64.
  *   - `stream` is a hipStream_t passed as void* (torch's current stream).  The
  *     functions enqueue work and return; they never synchronise, never touch

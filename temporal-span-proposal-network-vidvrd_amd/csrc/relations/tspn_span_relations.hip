@@ -133,7 +133,9 @@ int tspn::segment_span_topk(const unsigned* key, const float* sc, const int* ix,
 extern "C" size_t tspn_decode_span_relations_workspace_bytes(int64_t S, int64_t N, int64_t T, int64_t D, int64_t P,
                                                              int64_t J, int64_t K, int64_t topk_per_span) {
   if (S <= 0 || N <= 0 || T <= 0 || D <= 0 || P <= 0 || J <= 0 || K <= 0 || topk_per_span <= 0) return 0;
+  if (K > tspn::kRowTopkMaxK || J > MAX_J || S >= (1LL << 31) || P >= (1LL << 31)) return 0;     // what the entry refuses
   const int64_t R = std::min<int64_t>(topk_per_span, K);
+  if (P * J * R >= (1LL << 31)) return 0;
   return tspn::align_up(tspn::span_prefix_workspace_bytes(S * N, T, D, K), 256) + 3 * span_cand_bytes(S, P, J, R);
 }
 

@@ -666,13 +666,18 @@ Bf16Layout bf16_layout(const tspn_fused_bf16_desc* d) {
 }
 }  // namespace
 
+// 0 for the shapes forward_fused_bf16_impl refuses (and for the empty ones, which need none)
+static bool bf16_desc_has_layout(const tspn_fused_bf16_desc* d) {
+  return d && d->B > 0 && d->N > 0 && d->T > 0 && d->D > 0 && d->K > 0 && d->A > 0 && 3 * d->A <= 16 && d->D % 16 == 0;
+}
+
 extern "C" size_t tspn_forward_fused_bf16_workspace_bytes(const tspn_fused_bf16_desc* d) {
-  if (!d || d->B <= 0 || d->N <= 0 || d->T <= 0 || d->D <= 0 || d->K <= 0) return 0;
+  if (!bf16_desc_has_layout(d)) return 0;
   return bf16_layout(d).total;
 }
 
 extern "C" size_t tspn_forward_fused_bf16_pairs_workspace_bytes(const tspn_fused_bf16_desc* d) {
-  if (!d || d->B <= 0 || d->N <= 0 || d->T <= 0 || d->D <= 0 || d->K <= 0 || d->P < 0) return 0;
+  if (!bf16_desc_has_layout(d) || d->P < 0) return 0;
   const size_t plan = tspn_heads_pairlist_bf16_workspace_bytes(d->B, d->N, d->P);
   return plan ? bf16_layout(d).total + plan : 0;      // the plan's arrays follow the pass's own (256-byte aligned)
 }

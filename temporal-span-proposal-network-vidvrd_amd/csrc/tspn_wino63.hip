@@ -992,7 +992,7 @@ int check_common(const char* what, int64_t B, int64_t T, int64_t Cin, int64_t M,
 bool tspn::wino63_supported(int64_t Cin, int64_t M) { return Cin > 0 && M > 0 && Cin % 32 == 0 && M % 32 == 0; }
 
 size_t tspn::wino63_workspace_bytes(int64_t B, int64_t T, int64_t Cin) {
-  if (B <= 0 || T <= 0 || Cin <= 0) return 0;
+  if (B <= 0 || T <= 0 || Cin <= 0 || Cin % 32 != 0) return 0;     // Cin % 32 != 0: refused by the entries
   return (size_t)(Cin / 4) * NJ * (size_t)padded_sextets(B, T) * 4 * sizeof(float);
 }
 
@@ -1100,7 +1100,7 @@ bool tspn::wino63_f16x3_supported(int64_t Cin, int64_t M) {
 }
 
 size_t tspn::wino63_f16x3_workspace_bytes(int64_t B, int64_t T, int64_t Cin, int64_t M) {
-  if (B <= 0 || T <= 0 || Cin <= 0 || M <= 0) return 0;
+  if (B <= 0 || T <= 0 || !tspn::wino63_f16x3_supported(Cin, M)) return 0;     // what the entries refuse
   return f16x3_layout(B, T, Cin, M).total;
 }
 
