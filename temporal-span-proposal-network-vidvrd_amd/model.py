@@ -19,6 +19,8 @@ Differences from the reference, all in code the reference cannot execute:
 There is no CPU execution path: without the HIP library or a HIP device,
 forward raises.
 """
+import contextlib
+import functools
 import warnings
 import weakref
 from collections import namedtuple
@@ -118,11 +120,28 @@ def _batch_rows(tensors, device, dtype=torch.float32):
     return conv[0] if len(conv) == 1 else torch.cat(conv)
 
 
+def _pairs_field(plist):
+    """A segment's 'tracklet_pairs' field as an int64 tensor on the device it lives on (no copy between devices: every
+    caller moves it where it validates or reads it), or None when the segment scores all ordered pairs."""
+    p = plist.get_field("tracklet_pairs") if plist.has_field("tracklet_pairs") else None
+    if p is None:
+        return None
+    return (p.detach() if isinstance(p, torch.Tensor) else torch.as_tensor(np.asarray(p))).long()
+
+
+def _have_boxes(pair_list, members, on_device=False):
+    """Every member carries 'tracklet_boxes' (`on_device`: as HIP tensors, which the side stream may read in place)."""
+    boxes = [pair_list[i].get_field("tracklet_boxes") if pair_list[i].has_field("tracklet_boxes") else None for i in members]
+    if on_device:
+        return all(isinstance(b, torch.Tensor) and b.is_cuda for b in boxes)
+    return all(b is not None for b in boxes)
+
+
 def _segment_pairs(plist, n, device):
     """int64 [P,2] pair table of a tracklet segment: its 'tracklet_pairs' field or all ordered pairs."""
-    if plist.has_field("tracklet_pairs") and plist.get_field("tracklet_pairs") is not None:
-        p = plist.get_field("tracklet_pairs")
-        p = (p.detach() if isinstance(p, torch.Tensor) else torch.as_tensor(np.asarray(p))).long().to(device)
+    p = _pairs_field(plist)
+    if p is not None:
+        p = p.to(device)
         if p.dim() != 2 or p.shape[1] != 2:
             raise ValueError("tracklet_pairs must be [P,2]")
         if p.numel() and (int(p.min()) < 0 or int(p.max()) >= n):
@@ -811,6 +830,108 @@ class _HostPipeline:
         self.d2h.synchronize()             # the caller gets host tensors: they must be complete
 
 
+class _ScorerF32:
+    """How BaseModel scores one group of fp32 segments on `dev`: the weight set out of the model's caches, the shape
+    figures callers size outputs by (`dtype`, `rows` = 3A, `K`), and the one call of each fused and span entry.
+    _ScorerBf16 has the same methods; callers pick one of the two by the features' dtype (_scorer_kind) and know nothing
+    else about the operand type.
+
+    The fused pass's weights are resolved on first use (`rows`, `workspace_bytes`, `run`), never by the span methods:
+    choosing the conv algorithm (BaseModel._conv_algo) reads and clears the device's guard words, counts clean reads and
+    may promote or fall back, so it happens once per fp32 group and forward, in group order, behind the host-pipeline
+    test and behind the pair table of a resident group."""
+    dtype = torch.float32
+
+    def __init__(self, model, dev, d):
+        self.model, self.dev, self.d = model, dev, d
+        cls = model.classifier.rel_predictor
+        self.K = cls.weight.shape[0]
+        self.cw, self.cb = model.classifier._cache.get("cls", (cls.weight, cls.bias), dev, lambda ts: ts)
+
+    @functools.cached_property
+    def _fused(self):
+        """(packed conv, conv bias, head weight, head bias, raw conv weight and rows of the guard's spot check or
+        (None, 0), conv_algo of the workspace query)."""
+        m, dpn = self.model, self.model.relpn.duration_proposal_network
+        hw, hb = dpn._head_weights(self.dev)
+        # temporal conv algorithm: RELPN.DPN.CONV_ALGO = "auto" (Winograd F(6,3) when D % 32 == 0: 4/9 of the
+        # MFMA work; its fp32 error bound is in DESIGN.md §4) or "direct" (the k=3 taps as one implicit GEMM)
+        algo = m._conv_algo(self.d, self.dev)
+        packed, cbias = dpn._conv_packed(self.dev, algo)
+        craw, crows = (dpn._conv_raw(self.dev), m.conv_check_rows) if algo != "direct" and m.conv_check_rows > 0 else (None, 0)
+        return packed, cbias, hw, hb, craw, crows, _abi.CONV_WINOGRAD63_F16X3 if algo == "f16x3" else 0
+
+    @property
+    def rows(self):
+        return self._fused[3].numel()
+
+    def workspace_bytes(self, nm, n, t, d, P, canonical):
+        return ops.fused_workspace_bytes(nm, n, t, d, self.rows // 3, self.K, P, conv_algo=self._fused[6])
+
+    def run(self, feats, pairs, nm, n, workspace, canonical, conv_events, logits_event, out_heads=None, out_logits=None):
+        packed, cbias, hw, hb, craw, crows, _ = self._fused
+        return ops.forward_fused(feats, pairs, nm, n, packed, cbias, hw, hb, self.cw, self.cb, workspace=workspace,
+                                 check_pairs=False, canonical_pairs=canonical, conv_events=conv_events,
+                                 conv_weight=craw, conv_check=crows, logits_event=logits_event,
+                                 out_heads=out_heads, out_logits=out_logits)
+
+    def span_logits(self, feats, pairs, spans):
+        """RelOIPool over each pair's span + predicate head: sigmoid logits [P,K]."""
+        return ops.span_predicate(feats, pairs, spans, self.cw, self.cb)
+
+    def span_relations(self, feats, pairs, sp, clog, topk_per_span, topk_per_seg):
+        return ops.decode_span_relations(feats, pairs, sp["span"], sp["score"], sp["count"], self.cw, self.cb, clog,
+                                         topk_per_span=topk_per_span, topk_per_seg=topk_per_seg, check_pairs=False)
+
+
+class _ScorerBf16:
+    """_ScorerF32 for bf16 'tracklet_feats': the bf16-operand kernels (BASELINE config 3) and their semantics
+    (DESIGN.md §2); a group with an explicit pair table goes through the pair-list stage.  No conv algorithm to choose;
+    the packed weights are still made on first use, where the fused sites have always made them."""
+    dtype = torch.bfloat16
+
+    def __init__(self, model, dev, d):
+        if d % 16:
+            raise ValueError(f"the bf16 path needs D % 16 == 0 (D={d})")
+        self.model, self.dev = model, dev
+        self.K = model.classifier.rel_predictor.weight.shape[0]
+
+    @functools.cached_property
+    def _fused(self):
+        return self.model.relpn.duration_proposal_network._bf16_weights(self.dev) + self.model._cls_bf16(self.dev)
+
+    @property
+    def rows(self):
+        return self._fused[3].numel()
+
+    def workspace_bytes(self, nm, n, t, d, P, canonical):
+        return ops.fused_bf16_workspace_bytes(nm, n, t, d, self.rows // 3, self.K, P, canonical_pairs=canonical)
+
+    def run(self, feats, pairs, nm, n, workspace, canonical, conv_events, logits_event, out_heads=None, out_logits=None):
+        return ops.forward_fused_bf16(feats, pairs, nm, n, *self._fused, workspace=workspace, conv_events=conv_events,
+                                      logits_event=logits_event, out_heads=out_heads, out_logits=out_logits,
+                                      canonical_pairs=canonical, check_pairs=False)
+
+    def span_logits(self, feats, pairs, spans):
+        return ops.span_predicate_bf16(feats, pairs, spans, *self.model._span_cls_bf16(self.dev), self.K)
+
+    def span_relations(self, feats, pairs, sp, clog, topk_per_span, topk_per_seg):
+        return ops.decode_span_relations_bf16(feats, pairs, sp["span"], sp["score"], sp["count"],
+                                              *self.model._span_cls_bf16(self.dev), self.K, clog,
+                                              topk_per_span=topk_per_span, topk_per_seg=topk_per_seg, check_pairs=False)
+
+
+def _scorer_kind(feats):
+    """The scorer class of a segment's 'tracklet_feats': bf16 features select the bf16 operand set, anything else fp32."""
+    return _ScorerBf16 if isinstance(feats, torch.Tensor) and feats.dtype == torch.bfloat16 else _ScorerF32
+
+
+_LogitsToken = namedtuple("_LogitsToken", ["device", "logits", "stream", "host_ids"], defaults=[None])
+_LogitsToken.__doc__ = """The last single-group fused pass, for `decode`: device index, its batched logits tensor (kept
+alive here: its address cannot be handed to another tensor while the token stands), the caller's stream, and `host_ids` =
+(data_ptr, version) of the host tensors handed out for them, or None when the pass returned views of `logits` itself."""
+
+
 class BaseModel(_CachedWeightsMixin, nn.Module):
     """RelPN -> RelOIPool -> predicate classifier (reference lib/modeling/model.py:7-65)."""
 
@@ -838,8 +959,7 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
         # stream before their results are handed out, so the caller sees ordinary stream semantics.
         self.overlap_tail = bool(getattr(cfg.RELPN, "OVERLAP_TAIL", True))
         self._side = {}              # device index -> (side stream, logits-ready event)
-        self._logits_token = None    # (device index, the last fused pass's batched logits tensor, caller stream[, ids of
-        #                              the host tensors handed out for them])
+        self._logits_token = None    # _LogitsToken of the last fused pass that had a single group
         # host-resident inputs (predict.py hands CPU PairLists): videos per pipelined chunk, see _HostPipeline
         self.host_chunk_videos = int(getattr(cfg.RELPN.DPN, "HOST_CHUNK_VIDEOS", 4))
         self._host_pipes = {}
@@ -915,12 +1035,6 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
         if not self._winograd(d, dev):
             return "direct"
         return "f16x3" if self.conv_promoted else "wino63"
-
-    def _conv_guard(self, dpn, dev, winograd):
-        """(raw conv.weight, rows) for the fused pass's spot check, or (None, 0)."""
-        if winograd and self.conv_check_rows > 0:
-            return dpn._conv_raw(dev), self.conv_check_rows
-        return None, 0
 
     # ------------------------------------------------------------------ train
     def _forward_train(self, pair_list, target_list):
@@ -1052,26 +1166,24 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
         if cls.in_features != 2 * d_feat:
             raise ValueError(f"PREDICT.FEATURE_DIM must equal 2*D = {2 * d_feat} on the temporal path "
                              f"(got {cls.in_features})")
-        hw, hb = dpn._head_weights(dev)
-        cw, cb = self.classifier._cache.get("cls", (cls.weight, cls.bias), dev, lambda ts: ts)
-
         main = torch.cuda.current_stream(dev)
         overlap = self.overlap_tail and all(p.get_field("tracklet_feats").is_cuda for p in pair_list)
         side, ev_logits = self._side_stream(dev) if overlap else (None, None)
+        customs = [_pairs_field(p) for p in pair_list]
+        groups = {}
+        for i, plist in enumerate(pair_list):
+            f = plist.get_field("tracklet_feats")
+            # segments with an explicit pair table are scored on their own
+            groups.setdefault((tuple(f.shape), i + 1 if customs[i] is not None else 0, _scorer_kind(f)), []).append(i)
         if side is not None:
             # everything the side stream reads that THIS call may build lazily is built here, on the caller's stream,
             # before the side stream is made to wait for it: the PPN weight copies and the canonical pair tables of
             # every group (read by the pair-geometry launch here and by `decode` later)
             if self.use_ppn:
                 self.relpn.pair_proposal_network.device_weights(dev)
-            shapes = {}
-            for p in pair_list:
-                f = p.get_field("tracklet_feats")
-                if not (p.has_field("tracklet_pairs") and p.get_field("tracklet_pairs") is not None):
-                    k = (tuple(f.shape), f.dtype == torch.bfloat16)
-                    shapes[k] = shapes.get(k, 0) + 1
-            for (shape, _), cnt in shapes.items():
-                self._canonical_pairs(dev, cnt, shape[0])
+            for (shape, custom_key, _), members in groups.items():
+                if custom_key == 0:
+                    self._canonical_pairs(dev, len(members), shape[0])
             side.wait_stream(main)                 # class logits / boxes may have been produced on the caller's stream
         pair_proposals = None
         if self.use_ppn:
@@ -1087,89 +1199,36 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
 
         n_seg = len(pair_list)
         durations, logits = [None] * n_seg, [None] * n_seg
-        def custom_pairs(plist):
-            if not plist.has_field("tracklet_pairs"):
-                return None
-            p = plist.get_field("tracklet_pairs")
-            if p is None:
-                return None
-            if isinstance(p, torch.Tensor):
-                return p.detach().cpu().long()
-            return torch.as_tensor(np.asarray(p)).long()
-
-        groups = {}
-        for i, plist in enumerate(pair_list):
-            f = plist.get_field("tracklet_feats")
-            # segments with an explicit pair table are scored on their own
-            key = (tuple(f.shape), i + 1 if custom_pairs(plist) is not None else 0, f.dtype == torch.bfloat16)
-            groups.setdefault(key, []).append(i)
-        for (shape, custom_key, bf16), members in groups.items():
+        track = len(groups) == 1                   # the logits-ready event and the token stand for ONE fused pass
+        for (shape, custom_key, kind), members in groups.items():
             n, t, d = shape
             nm = len(members)
-            per = n * (n - 1)
             src = [pair_list[i].get_field("tracklet_feats") for i in members]
-            if (self.host_chunk_videos > 0 and custom_key == 0 and not self.pool_top_span and per > 0
-                    and (d % 16 == 0 if bf16 else True)
+            scorer = kind(self, dev, d)
+            if (self.host_chunk_videos > 0 and custom_key == 0 and not self.pool_top_span and n * (n - 1) > 0
                     and all(isinstance(x, torch.Tensor) and not x.is_cuda for x in src)):
                 # host-resident features, canonical pair table: chunked upload / compute / download pipeline
-                self._forward_host_group(pair_list, members, shape, bf16, dev, (hw, hb, cw, cb), durations, logits,
-                                         track_token=len(groups) == 1)
+                self._forward_host_group(pair_list, members, shape, scorer, dev, durations, logits, track_token=track)
                 continue
-            if bf16:
-                # bf16 tracklet features select the bf16-operand kernels (BASELINE config 3); a member with its own
-                # 'tracklet_pairs' sends the group through the pair-list stage
-                if d % 16:
-                    raise ValueError(f"the bf16 path needs D % 16 == 0 (D={d})")
-                feats = _batch_rows(src, dev, torch.bfloat16)
-                allp, counts, canonical = self._group_pair_table([custom_pairs(pair_list[i]) for i in members], dev, n)
-                if not canonical and side is not None and self.pair_geometry_in_forward:
-                    side.wait_stream(main)     # the geometry launch on the side stream reads this table
-                packed, cbias, hpk, hb16 = dpn._bf16_weights(dev)
-                cw16, cb16 = self.classifier._cache.get(
-                    "cls_bf16", (cls.weight, cls.bias), dev,
-                    lambda ts: tuple(ops.cast_bf16(x.contiguous()).float() for x in ts))
-                need = ops.fused_bf16_workspace_bytes(nm, n, t, d, hb16.numel() // 3, cw16.shape[0], allp.shape[0],
-                                                      canonical_pairs=canonical)
-                heads, lg = ops.forward_fused_bf16(feats, allp, nm, n, packed, cbias, hpk, hb16, cw16, cb16,
-                                                   workspace=self._workspace(dev, need), conv_events=self._conv_events,
-                                                   logits_event=ev_logits if (overlap and len(groups) == 1) else None,
-                                                   canonical_pairs=canonical, check_pairs=False)
-                if self.pool_top_span and allp.shape[0]:
-                    # RelOIPool over each pair's best span, bf16 semantics: canonical and custom tables alike
-                    top = ops.decode_spans(heads, self.anchor_sizes(t), top_k=1)["span"][:, 0].contiguous()
-                    cpk, cb16s = self._span_cls_bf16(dev)
-                    lg = ops.span_predicate_bf16(feats, allp, top, cpk, cb16s, cls.weight.shape[0])
-            else:
-                feats = _batch_rows(src, dev)
-                allp, counts, canonical = self._group_pair_table([custom_pairs(pair_list[i]) for i in members], dev, n)
-                if not canonical and side is not None and self.pair_geometry_in_forward:
-                    side.wait_stream(main)     # the geometry launch on the side stream reads this table
-                # temporal conv algorithm: RELPN.DPN.CONV_ALGO = "auto" (Winograd F(6,3) when D % 32 == 0: 4/9 of the
-                # MFMA work; its fp32 error bound is in DESIGN.md §4) or "direct" (the k=3 taps as one implicit GEMM)
-                algo = self._conv_algo(d, dev)
-                wino = algo != "direct"
-                packed, cbias = dpn._conv_packed(dev, algo)
-                craw, crows = self._conv_guard(dpn, dev, wino)
-                need = ops.fused_workspace_bytes(nm, n, t, d, hb.numel() // 3, cw.shape[0], allp.shape[0],
-                                                 conv_algo=_abi.CONV_WINOGRAD63_F16X3 if algo == "f16x3" else 0)
-                heads, lg = ops.forward_fused(feats, allp, nm, n, packed, cbias, hw, hb, cw, cb,
-                                              workspace=self._workspace(dev, need), check_pairs=False,
-                                              canonical_pairs=canonical, conv_events=self._conv_events,
-                                              conv_weight=craw, conv_check=crows,
-                                              logits_event=ev_logits if (overlap and len(groups) == 1) else None)
-                if self.pool_top_span and allp.shape[0]:
-                    # RelOIPool over each pair's best span (decode + NMS, top-1) instead of the whole segment
-                    top = ops.decode_spans(heads, self.anchor_sizes(t), top_k=1)["span"][:, 0].contiguous()
-                    lg = ops.span_predicate(feats, allp, top, cw, cb)
-            if overlap and len(groups) == 1 and not self.pool_top_span:
+            feats = _batch_rows(src, dev, scorer.dtype)
+            allp, counts, canonical = self._group_pair_table(
+                [None if customs[i] is None else customs[i].cpu() for i in members], dev, n)
+            if not canonical and side is not None and self.pair_geometry_in_forward:
+                side.wait_stream(main)     # the geometry launch on the side stream reads this table
+            need = scorer.workspace_bytes(nm, n, t, d, allp.shape[0], canonical)
+            heads, lg = scorer.run(feats, allp, nm, n, self._workspace(dev, need), canonical, self._conv_events,
+                                   ev_logits if track else None)
+            if self.pool_top_span and allp.shape[0]:
+                # RelOIPool over each pair's best span (decode + NMS, top-1) instead of the whole segment, in the
+                # group's own semantics: canonical and custom tables alike
+                top = ops.decode_spans(heads, self.anchor_sizes(t), top_k=1)["span"][:, 0].contiguous()
+                lg = scorer.span_logits(feats, allp, top)
+            if overlap and track and not self.pool_top_span:
                 # `decode` may start behind the logits-ready event of THIS pass (same logits tensor, same caller stream)
-                # (the token keeps `lg` alive: its address cannot be handed to another tensor while the token stands)
-                self._logits_token = (dev.index, lg, main.cuda_stream)
+                self._logits_token = _LogitsToken(dev.index, lg, main.cuda_stream)
             geom = None
             if self.pair_geometry_in_forward:
-                boxes_on_dev = all(pair_list[i].has_field("tracklet_boxes") and isinstance(pair_list[i].get_field("tracklet_boxes"), torch.Tensor)
-                                   and pair_list[i].get_field("tracklet_boxes").is_cuda for i in members)
-                if side is not None and boxes_on_dev:
+                if side is not None and _have_boxes(pair_list, members, on_device=True):
                     # the bbox half of the pair builder needs the boxes only: second stream, under the encoder
                     with torch.cuda.stream(side):
                         geom = self._pair_geometry_batch(pair_list, members, allp, dev)
@@ -1196,14 +1255,12 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
         """Video ranges the host-input pipeline scores one after the other (bench.py reads the last one)."""
         return _HostPipeline.schedule(nm, chunk)
 
-    def _forward_host_group(self, pair_list, members, shape, bf16, dev, weights, durations, logits, track_token):
+    def _forward_host_group(self, pair_list, members, shape, scorer, dev, durations, logits, track_token):
         """One group of equal-shape segments whose `tracklet_feats` are HOST tensors (the reference's predict.py:50-57
         hands CPU PairLists): upload, fused pass and download run as a three-stage pipeline over chunks of videos
         (_HostPipeline); results are pinned host tensors, complete when this returns (same device as the inputs,
         reference model.py:53-65).  Same kernels, same per-video results as the resident path."""
         dpn = self.relpn.duration_proposal_network
-        cls = self.classifier.rel_predictor
-        hw, hb, cw, cb = weights
         n, t, d = shape
         nm, per = len(members), n * (n - 1)
         src = [pair_list[i].get_field("tracklet_feats") for i in members]
@@ -1211,37 +1268,20 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
         if pipe is None:
             pipe = self._host_pipes[dev.index] = _HostPipeline(dev)
         main = torch.cuda.current_stream(dev)
-        if bf16:
-            packed, cbias, hpk, hb16 = dpn._bf16_weights(dev)
-            cw16, cb16 = self.classifier._cache.get(
-                "cls_bf16", (cls.weight, cls.bias), dev,
-                lambda ts: tuple(ops.cast_bf16(x.contiguous()).float() for x in ts))
-            a3, k_out = hb16.numel(), cw16.shape[0]
-        else:
-            algo = self._conv_algo(d, dev)
-            wino = algo != "direct"
-            packed, cbias = dpn._conv_packed(dev, algo)
-            craw, crows = self._conv_guard(dpn, dev, wino)
-            a3, k_out = hb.numel(), cw.shape[0]
+        a3, k_out = scorer.rows, scorer.K
         chunks = pipe.schedule(nm, self.host_chunk_videos)
-        feats = pipe.begin(src, torch.bfloat16 if bf16 else torch.float32)
+        feats = pipe.begin(src, scorer.dtype)
         heads_dev = torch.empty((nm * per, a3, t), dtype=torch.float32, device=dev)
         lg_dev = torch.empty((nm * per, k_out), dtype=torch.float32, device=dev)
         heads_host = torch.empty((nm * per, a3, t), dtype=torch.float32, pin_memory=True)
         lg_host = torch.empty((nm * per, k_out), dtype=torch.float32, pin_memory=True)
-        want_geom = self.pair_geometry_in_forward and all(
-            pair_list[i].has_field("tracklet_boxes") and pair_list[i].get_field("tracklet_boxes") is not None for i in members)
+        want_geom = self.pair_geometry_in_forward and _have_boxes(pair_list, members)
         geom_host = torch.empty((nm * per, 8, t), dtype=torch.float32, pin_memory=True) if want_geom else None
         # like heads_dev / lg_dev: lives until finish() has synchronised the download stream (a per-chunk temporary
         # would go back to the caller stream's pool while d2h still reads it)
         geom_dev = torch.empty((nm * per, 8, t), dtype=torch.float32, device=dev) if want_geom else None
         cmax = max(hi - lo for lo, hi in chunks)
-        if bf16:
-            need = ops.fused_bf16_workspace_bytes(cmax, n, t, d, a3 // 3, k_out, cmax * per)
-        else:
-            need = ops.fused_workspace_bytes(cmax, n, t, d, a3 // 3, k_out, cmax * per,
-                                             conv_algo=_abi.CONV_WINOGRAD63_F16X3 if algo == "f16x3" else 0)
-        ws = self._workspace(dev, need)
+        ws = self._workspace(dev, scorer.workspace_bytes(cmax, n, t, d, cmax * per, True))
         # the small side inputs go up NOW, while the caller's stream is empty: a blocking .to(device) issued after a
         # pass has been queued would wait for that pass and stall the pipeline
         boxes_dev = _batch_rows([pair_list[i].get_field("tracklet_boxes") for i in members], dev) if want_geom else None
@@ -1251,15 +1291,8 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
             main.wait_event(ready)
             allp, _ = self._canonical_pairs(dev, c, n)
             rows = slice(lo * per, hi * per)
-            if bf16:
-                ops.forward_fused_bf16(feats[lo * n:hi * n], allp, c, n, packed, cbias, hpk, hb16, cw16, cb16, workspace=ws,
-                                       conv_events=self._conv_events if k == len(chunks) - 1 else None,
-                                       out_heads=heads_dev[rows], out_logits=lg_dev[rows])
-            else:
-                ops.forward_fused(feats[lo * n:hi * n], allp, c, n, packed, cbias, hw, hb, cw, cb, workspace=ws,
-                                  check_pairs=False, canonical_pairs=True, conv_weight=craw, conv_check=crows,
-                                  conv_events=self._conv_events if k == len(chunks) - 1 else None,
-                                  out_heads=heads_dev[rows], out_logits=lg_dev[rows])
+            scorer.run(feats[lo * n:hi * n], allp, c, n, ws, True, self._conv_events if k == len(chunks) - 1 else None, None,
+                       out_heads=heads_dev[rows], out_logits=lg_dev[rows])
             back = [(heads_host[rows], heads_dev[rows]), (lg_host[rows], lg_dev[rows])]
             if want_geom:
                 ops.pair_gather(None, boxes_dev[lo * n:hi * n], allp, want_feat=False, check_pairs=False,
@@ -1275,16 +1308,15 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
             logits[i] = lg_host[sl]
         if track_token:
             # `decode` on these very host tensors reads the device copy instead of uploading them again
-            self._logits_token = (dev.index, lg_dev, main.cuda_stream,
-                                  tuple((logits[i].data_ptr(), logits[i]._version) for i in members))
+            self._logits_token = _LogitsToken(dev.index, lg_dev, main.cuda_stream,
+                                              tuple((logits[i].data_ptr(), logits[i]._version) for i in members))
 
     @staticmethod
     def _pair_geometry_batch(pair_list, members, allp, dev):
         """The bbox half of the N^2 pair builder for one group of equal-shape segments, ONE launch: relative
         box geometry [P_total, 8, T] of every scored pair (pair_geometry_kernel: one lane per (pair, frame),
         the motion channels through a wavefront shuffle).  None unless every segment carries 'tracklet_boxes'."""
-        if not all(pair_list[i].has_field("tracklet_boxes") and pair_list[i].get_field("tracklet_boxes") is not None
-                   for i in members) or allp.shape[0] == 0:
+        if not _have_boxes(pair_list, members) or allp.shape[0] == 0:
             return None
         boxes = _batch_rows([pair_list[i].get_field("tracklet_boxes") for i in members], dev)
         _, geom = ops.pair_gather(None, boxes, allp, want_feat=False, check_pairs=False)   # allp was validated above
@@ -1323,73 +1355,54 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
             dev = _compute_device(*[rel_logits[i] for i in members])
             nm = len(members)
             tok = self._logits_token
-            if (tok is not None and len(tok) == 4 and tok[0] == dev.index and tok[1].numel() == nm * lshape[0] * lshape[1]
-                    and tok[2] == torch.cuda.current_stream(dev).cuda_stream
-                    and tok[3] == tuple((rel_logits[i].data_ptr(), rel_logits[i]._version) for i in members)):
+            if (tok is not None and tok.host_ids is not None and tok.device == dev.index
+                    and tok.logits.numel() == nm * lshape[0] * lshape[1]
+                    and tok.stream == torch.cuda.current_stream(dev).cuda_stream
+                    and tok.host_ids == tuple((rel_logits[i].data_ptr(), rel_logits[i]._version) for i in members)):
                 # the host tensors the last forward handed out, untouched: their device copy is still there
-                lg = tok[1].view(nm, lshape[0], lshape[1])
+                lg = tok.logits.view(nm, lshape[0], lshape[1])
             else:
                 lg = _batch_rows([rel_logits[i] for i in members], dev).view(nm, lshape[0], lshape[1])
             # these are the logits of the last fused forward, still on the stream that produced them: decode on the
             # side stream behind their ready-event, i.e. UNDER that forward's encoder, and join afterwards
             main = torch.cuda.current_stream(dev)
-            custom = [pair_list[i].has_field("tracklet_pairs") and pair_list[i].get_field("tracklet_pairs") is not None
-                      for i in members]
-            side, tok = None, self._logits_token
-            if (overlap and self.overlap_tail and tok is not None and len(tok) == 3 and tok[0] == dev.index and tok[2] == main.cuda_stream
-                    and tok[1].data_ptr() == lg.data_ptr() and tok[1].numel() == lg.numel() and not quirk
-                    and not any(custom) and all(pair_list[i].get_field("track_cls_logits").is_cuda for i in members)):
+            custom = [_pairs_field(pair_list[i]) for i in members]
+            explicit = any(p is not None for p in custom)
+            side = None
+            if (overlap and self.overlap_tail and tok is not None and tok.host_ids is None and tok.device == dev.index
+                    and tok.stream == main.cuda_stream and tok.logits.data_ptr() == lg.data_ptr()
+                    and tok.logits.numel() == lg.numel() and not quirk and not explicit
+                    and all(pair_list[i].get_field("track_cls_logits").is_cuda for i in members)):
                 side, ev_logits = self._side_stream(dev)
                 side.wait_event(ev_logits)
                 self._logits_token = None          # one decode per forward rides the event
-            if not any(custom):
-                for i in members:
-                    if n * (n - 1) != rel_logits[i].shape[0]:
-                        raise ValueError(f"decode: segment {i}: rel_logits has {rel_logits[i].shape[0]} rows but "
-                                         f"{n} tracklets give {n * (n - 1)} pairs and no 'tracklet_pairs' field is set")
+            for i, p in zip(members, custom):
+                rows = rel_logits[i].shape[0]
+                if p is None and n * (n - 1) != rows:
+                    raise ValueError(f"decode: segment {i}: rel_logits has {rows} rows but "
+                                     f"{n} tracklets give {n * (n - 1)} pairs and no 'tracklet_pairs' field is set")
+                if p is not None and tuple(p.shape) != (rows, 2):
+                    raise ValueError(f"decode: segment {i}: 'tracklet_pairs' must be [P,2] with one row per "
+                                     f"rel_logits row (P={rows}), got {tuple(p.shape)}")
+            if explicit:
+                pairs = torch.stack([ops.pair_index(n, dev) if p is None else p.to(dev) for p in custom]).contiguous()
+            else:
                 pairs = self._canonical_pairs(dev, nm, n)[1]
-                trusted = True
-            else:
-                pairs = []
-                for i in members:
-                    plist = pair_list[i]
-                    if plist.has_field("tracklet_pairs") and plist.get_field("tracklet_pairs") is not None:
-                        p = plist.get_field("tracklet_pairs")
-                        p = p.detach().long() if isinstance(p, torch.Tensor) else torch.as_tensor(np.asarray(p)).long()
-                        if tuple(p.shape) != (rel_logits[i].shape[0], 2):
-                            raise ValueError(f"decode: segment {i}: 'tracklet_pairs' must be [P,2] with one row per "
-                                             f"rel_logits row (P={rel_logits[i].shape[0]}), got {tuple(p.shape)}")
-                        pairs.append(p.to(dev))
-                    else:
-                        if n * (n - 1) != rel_logits[i].shape[0]:
-                            raise ValueError(f"decode: segment {i}: rel_logits has {rel_logits[i].shape[0]} rows but "
-                                             f"{n} tracklets give {n * (n - 1)} pairs and no 'tracklet_pairs' field is set")
-                        pairs.append(ops.pair_index(n, dev))
-                pairs = torch.stack(pairs).contiguous()
-                trusted = False
             if quirk:
-                fshape = tuple(pair_list[members[0]].features.shape)
-                cls = _batch_rows([pair_list[i].features for i in members], dev).view((nm,) + fshape)
-                res = ops.decode_topk(lg, pairs, cls, row_mul=n - 1, num_obj=num_obj,
-                                      topk_per_pair=topk_per_pair, topk_per_seg=topk_per_seg, check_pairs=not trusted)
+                cls_src, row_mul = [pair_list[i].features for i in members], n - 1
             else:
-                cshape = tuple(pair_list[members[0]].get_field("track_cls_logits").shape)
-                cls_src = [pair_list[i].get_field("track_cls_logits") for i in members]
-                if side is not None:
-                    with torch.cuda.stream(side):
-                        # the class logits are batched UNDER the side stream: when they are not consecutive slices of
-                        # one allocation this is a cat / cast kernel, which on the caller's stream would sit behind the
-                        # whole encoder while the decode launch on the side stream read its (unwritten) result
-                        cls = _batch_rows(cls_src, dev).view((nm,) + cshape)
-                        res = ops.decode_topk(lg, pairs, cls, row_mul=1, num_obj=num_obj, topk_per_pair=topk_per_pair,
-                                              topk_per_seg=topk_per_seg, check_pairs=not trusted)
-                        for r in res:
-                            r.record_stream(main)      # allocated under the side stream, consumed on the caller's
-                    main.wait_stream(side)             # the caller's stream sees complete results from here on
-                else:
-                    cls = _batch_rows(cls_src, dev).view((nm,) + cshape)
-                    res = ops.decode_topk(lg, pairs, cls, row_mul=1, num_obj=num_obj, topk_per_pair=topk_per_pair,
-                                          topk_per_seg=topk_per_seg, check_pairs=not trusted)
+                cls_src, row_mul = [pair_list[i].get_field("track_cls_logits") for i in members], 1
+            with torch.cuda.stream(side) if side is not None else contextlib.nullcontext():
+                # on the side stream the class logits are batched UNDER it: when they are not consecutive slices of
+                # one allocation this is a cat / cast kernel, which on the caller's stream would sit behind the
+                # whole encoder while the decode launch on the side stream read its (unwritten) result
+                cls = _batch_rows(cls_src, dev).view((nm,) + tuple(cls_src[0].shape))
+                res = ops.decode_topk(lg, pairs, cls, row_mul=row_mul, num_obj=num_obj, topk_per_pair=topk_per_pair,
+                                      topk_per_seg=topk_per_seg, check_pairs=explicit)
+            if side is not None:
+                for r in res:
+                    r.record_stream(main)          # allocated under the side stream, consumed on the caller's
+                main.wait_stream(side)             # the caller's stream sees complete results from here on
             for k, i in enumerate(members):
                 tgt = rel_logits[i].device
                 out[i] = tuple(r[k].to(tgt) for r in res)
@@ -1420,6 +1433,12 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
             out.append({k: v.to(heads.device) for k, v in res.items()})
         return out
 
+    def _cls_bf16(self, dev):
+        """(classifier weight, bias) of the bf16 fused pass: fp32 tensors holding bf16-rounded values."""
+        cls = self.classifier.rel_predictor
+        return self.classifier._cache.get("cls_bf16", (cls.weight, cls.bias), dev,
+                                          lambda ts: tuple(ops.cast_bf16(x.contiguous()).float() for x in ts))
+
     def _span_cls_bf16(self, dev):
         """(packed bf16 classifier of the bf16 span entries, its bias rounded to bf16 as fp32), cached beside "cls_bf16"."""
         cls = self.classifier.rel_predictor
@@ -1433,28 +1452,16 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
         RelOIPool.__call__(feats, duration_proposals) (reference model.py:68-73) + RelationPredictor.  A segment whose
         'tracklet_feats' are bf16 (D % 16 == 0) is pooled and classified with the bf16 semantics of `forward`
         (DESIGN.md §2): its logits equal forward's RELPN.DPN.POOL_TOP_SPAN logits for the same spans, bit for bit."""
-        cls = self.classifier.rel_predictor
         out = []
         with torch.no_grad():
             for plist, sp in zip(pair_list, spans):
                 f = plist.get_field("tracklet_feats")
-                dev = _compute_device(f, cls.weight)
-                cw, cb = self.classifier._cache.get("cls", (cls.weight, cls.bias), dev, lambda ts: ts)
-                n = f.shape[0]
-                if plist.has_field("tracklet_pairs") and plist.get_field("tracklet_pairs") is not None:
-                    p = plist.get_field("tracklet_pairs")
-                    p = (p.detach() if isinstance(p, torch.Tensor) else torch.as_tensor(np.asarray(p))).long().to(dev)
-                else:
-                    p = ops.pair_index(n, dev)
+                dev = _compute_device(f, self.classifier.rel_predictor.weight)
+                scorer = _scorer_kind(f)(self, dev, f.shape[2])
+                p = _pairs_field(plist)
+                p = ops.pair_index(f.shape[0], dev) if p is None else p.to(dev)
                 sp = (sp if isinstance(sp, torch.Tensor) else torch.as_tensor(np.asarray(sp))).long().to(dev)
-                if isinstance(f, torch.Tensor) and f.dtype == torch.bfloat16:
-                    if f.shape[2] % 16:
-                        raise ValueError(f"the bf16 path needs D % 16 == 0 (D={f.shape[2]})")
-                    cpk, cb16 = self._span_cls_bf16(dev)
-                    out.append(ops.span_predicate_bf16(f.to(dev).contiguous(), p.contiguous(), sp.contiguous(), cpk, cb16,
-                                                       cls.weight.shape[0]).to(f.device))
-                    continue
-                out.append(ops.span_predicate(_f32(f, dev), p.contiguous(), sp.contiguous(), cw, cb).to(f.device))
+                out.append(scorer.span_logits(_batch_rows([f], dev, scorer.dtype), p.contiguous(), sp.contiguous()).to(f.device))
         return out
 
     def decode_span_relations(self, pair_list, duration_proposals, spans_per_pair=4, topk_per_span=20, topk_per_seg=200,
@@ -1486,14 +1493,11 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                 c = plist.get_field("track_cls_logits")
                 if tuple(c.shape) != (n, num_obj):
                     raise ValueError(f"decode_span_relations: segment {i}: 'track_cls_logits' must be [{n},{num_obj}], got {tuple(c.shape)}")
-                bf16 = isinstance(f, torch.Tensor) and f.dtype == torch.bfloat16
-                if bf16 and f.shape[2] % 16:
-                    raise ValueError(f"the bf16 path needs D % 16 == 0 (D={f.shape[2]})")
-                groups.setdefault((tuple(f.shape), tuple(heads.shape), bf16), []).append(i)
-            for (fshape, hshape, bf16), members in groups.items():
+                groups.setdefault((tuple(f.shape), tuple(heads.shape), _scorer_kind(f)), []).append(i)
+            for (fshape, hshape, kind), members in groups.items():
                 n, nm = fshape[0], len(members)
                 dev = _compute_device(*[pair_list[i].get_field("tracklet_feats") for i in members], cls.weight)
-                cw, cb = self.classifier._cache.get("cls", (cls.weight, cls.bias), dev, lambda ts: ts)
+                scorer = kind(self, dev, fshape[2])
                 pairs = []
                 for i in members:
                     p = _segment_pairs(pair_list[i], n, dev)
@@ -1505,18 +1509,9 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                 heads = _batch_rows([duration_proposals[i].heads for i in members], dev)
                 sz = sizes if sizes is not None else self.anchor_sizes(hshape[2])
                 sp = ops.decode_spans(heads, sz, top_k=spans_per_pair, nms_threshold=nms_threshold)
-                feats = _batch_rows([pair_list[i].get_field("tracklet_feats") for i in members], dev,
-                                    torch.bfloat16 if bf16 else torch.float32)
+                feats = _batch_rows([pair_list[i].get_field("tracklet_feats") for i in members], dev, scorer.dtype)
                 clog = _batch_rows([pair_list[i].get_field("track_cls_logits") for i in members], dev).view(nm, n, num_obj)
-                if bf16:
-                    cpk, cb16 = self._span_cls_bf16(dev)
-                    res = ops.decode_span_relations_bf16(feats, pairs, sp["span"], sp["score"], sp["count"], cpk, cb16,
-                                                         cls.weight.shape[0], clog, topk_per_span=topk_per_span,
-                                                         topk_per_seg=topk_per_seg, check_pairs=False)
-                else:
-                    res = ops.decode_span_relations(feats, pairs, sp["span"], sp["score"], sp["count"], cw, cb, clog,
-                                                    topk_per_span=topk_per_span, topk_per_seg=topk_per_seg,
-                                                    check_pairs=False)
+                res = scorer.span_relations(feats, pairs, sp, clog, topk_per_span, topk_per_seg)
                 valid = res[5].tolist()
                 for k, i in enumerate(members):
                     tgt = pair_list[i].get_field("tracklet_feats").device

@@ -836,3 +836,75 @@ def test_in_place_data_edits_need_invalidate_or_verify_weights(tspn, device, mon
     m.classifier.rel_predictor.weight.data.mul_(2.0)              # back to the original values, again in place
     again = m([plist], None)[2][0]
     assert torch.equal(again, base)                                 # seen without invalidate_caches()
+
+
+def _same(a, b):
+    """Bit-equal tensors on the same device (tuples and dicts of tensors member by member)."""
+    if isinstance(a, dict):
+        return a.keys() == b.keys() and all(_same(a[k], b[k]) for k in a)
+    if isinstance(a, (tuple, list)):
+        return len(a) == len(b) and all(_same(x, y) for x, y in zip(a, b))
+    return a.device == b.device and a.dtype == b.dtype and torch.equal(a, b)
+
+
+def test_forward_mixed_groups_equal_each_segment_alone(tspn, device):
+    """One list that takes every dispatch of the eval path in one call -- fp32 and bf16 groups, canonical and explicit
+    pair tables (a numpy one that repeats a pair, a device tensor), a two-member batch, a second N, and two host
+    segments that make two pipeline chunks -- in interleaved order: per segment `forward`, `decode`, `classify_spans`
+    and `decode_span_relations` give exactly what the call on that segment alone gives, on the segment's own device;
+    with `pool_top_span` the logits are `classify_spans` on the top-1 spans, bit for bit."""
+    D, T = 32, 30
+    sd = tspn.synth.make_weights(21, c=2 * D, bias_std=0.05)
+    sd = {k: (v * 40 if "relness_pred" in k or "duration_pred" in k else v) for k, v in sd.items()}   # real spans
+    model = tspn.BaseModel(cases.baseline_cfg(**{"RELPN.USE_PPN": True, "RELPN.USE_DPN": True, "RELPN.DPN.IN_CHANNELS": 2 * D,
+                                                 "PREDICT.FEATURE_DIM": 2 * D, "RELPN.DPN.PAIR_GEOMETRY": True,
+                                                 "RELPN.DPN.HOST_CHUNK_VIDEOS": 1}))
+    load(model, sd)
+    model.eval()
+    allp = oracle.pair_index(5).numpy()
+    repeat = np.ascontiguousarray(allp[[11, 2, 19, 2, 7, 0, 14]])                     # 7 rows, pair 2 twice
+    on_dev = t(np.ascontiguousarray(allp[[5, 18, 1, 9, 12, 3]])).to(device)
+    spec = [(5, False, device, None), (5, True, device, None), (5, False, device, repeat), (5, False, device, None),
+            (5, True, device, on_dev), (3, False, device, None), (4, False, "cpu", None), (4, False, "cpu", None)]
+    pls = []
+    for k, (n, bf16, where, pairs) in enumerate(spec):
+        v = tspn.synth.make_video(940 + k, n, T, D)
+        f = t(v["tracklet_feats"])
+        pls.append(tspn.PairList.from_tracklets((f.to(torch.bfloat16) if bf16 else f).to(where), t(v["tracklet_boxes"]).to(where),
+                                                (8.0 * t(v["track_cls_logits"])).to(where), tracklet_pairs=pairs))
+    kw = dict(spans_per_pair=3, topk_per_span=6, topk_per_seg=50)
+    rows = [len(p) if p is not None else n * (n - 1) for n, _, _, p in spec]
+
+    pp, dp, lg = model(pls, None)
+    dec = model.decode(pls, lg)
+    top = [s["span"][:, 0] for s in model.decode_spans(dp, top_k=1)]
+    cs = model.classify_spans(pls, top)
+    rel = model.decode_span_relations(pls, dp, **kw)
+    torch.cuda.synchronize()
+    alone = []
+    for i, pl in enumerate(pls):
+        want = torch.device(spec[i][2])
+        pp1, dp1, lg1 = model([pl], None)
+        assert lg[i].shape[0] == rows[i] and lg[i].device.type == want.type and dp[i].heads.device.type == want.type
+        assert dp[i].geom.device.type == want.type and pp[i].device.type == want.type
+        assert _same(dp[i].heads, dp1[0].heads), f"heads of segment {i}"
+        assert _same(dp[i].geom, dp1[0].geom), f"geom of segment {i}"
+        assert _same(lg[i], lg1[0]), f"rel_logits of segment {i}"
+        assert _same(pp[i], pp1[0]), f"pair proposals of segment {i}"
+        assert _same(dec[i], model.decode([pl], lg1)[0]), f"decode of segment {i}"
+        assert dec[i][0].device.type == want.type and dec[i][0].shape[0] > 0
+        top1 = model.decode_spans(dp1, top_k=1)[0]["span"][:, 0]
+        assert _same(top[i], top1)
+        assert _same(cs[i], model.classify_spans([pl], [top1])[0]), f"classify_spans of segment {i}"
+        assert cs[i].device.type == want.type and tuple(cs[i].shape) == tuple(lg[i].shape)
+        assert _same(rel[i], model.decode_span_relations([pl], dp1, **kw)[0]), f"decode_span_relations of segment {i}"
+        assert rel[i][0].device.type == want.type and rel[i][0].shape[0] > 0
+        alone.append(dp1[0].heads)
+    assert all(((s[:, 0] >= 0) & (s[:, 1] - s[:, 0] < T)).any() for s in top)           # real spans, not whole segments
+
+    model.pool_top_span = True
+    _, dp2, lg2 = model(pls, None)
+    torch.cuda.synchronize()
+    for i in range(len(pls)):
+        assert _same(dp2[i].heads, alone[i]), f"POOL_TOP_SPAN heads of segment {i}"
+        assert _same(lg2[i], cs[i]), f"POOL_TOP_SPAN logits of segment {i}"
