@@ -71,21 +71,7 @@ def test_list_rows_equal_the_grid_rows(tspn, device, shape, order):
 
 
 # ------------------------------------------------------------------------------------------------ arbitrary tables
-def _triple():
-    tab = np.tile(ref.among([0, 2, 5]), (3, 1))
-    return tab[np.random.RandomState(3).permutation(len(tab))]
-
-
-SCATTERED17 = [0, 2, 3, 7, 8, 12, 15, 16, 19, 23, 24, 28, 31, 33, 36, 38, 39]
-# name -> (B, N, T, C, table)
-TABLES = {
-    "single_pair": (1, 5, 18, 32, np.array([[3, 1]])),
-    "diagonal_rows": (1, 5, 18, 32, np.array([[0, 0], [2, 2], [4, 4], [1, 3], [2, 2]])),
-    "every_row_three_times": (1, 6, 18, 32, _triple()),
-    "among_17_scattered_of_40": (1, 40, 20, 32, ref.among(SCATTERED17)),        # two ragged tiles per axis
-    "no_row_for_the_middle_video": (3, 5, 18, 32, np.concatenate([ref.among([0, 1, 3]), ref.among([2, 4], base=10)])),
-    "empty": (2, 5, 18, 32, np.zeros((0, 2), np.int64)),
-}
+TABLES, SCATTERED17 = ref.TABLES, ref.SCATTERED17
 
 
 @pytest.mark.parametrize("name", list(TABLES))
@@ -104,7 +90,7 @@ def test_plan_equals_the_numpy_restatement(tspn, device, name):
     if name in TABLES:
         B, N, _, _, table = TABLES[name]
     else:
-        B, N, table = 3, 4, np.array([[9, 8], [1, 2], [1, 5], [-1, 2], [2, 12], [11, 8], [1, 2]])
+        B, N, table = ref.CROSS_VIDEO
     plan = tspn.ops.pair_plan(torch.as_tensor(table, dtype=torch.int64).reshape(-1, 2).to(device), B, N)
     assert all(v.dtype == torch.int32 for v in plan.values())
     ref.check_plan({k: v.cpu().numpy() for k, v in plan.items()}, table, B, N)

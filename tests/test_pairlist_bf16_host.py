@@ -172,3 +172,133 @@ def test_tables_of_the_reference_module():
     out = ref.heads_list_ref64(y, [[0, 1], [1, 1]], hw, hb)
     # (0, 1): relu([-3, -2] + [3, 4]) = [0, 2] -> 4.5; (1, 1): relu([1, 2] + [3, 4]) = [4, 6] -> 16.5
     assert out.shape == (2, 1, 1) and out.flatten().tolist() == [4.5, 16.5]
+
+
+# ------------------------------------------------------------------------------------------- the vectorised plan check
+def _random_table(rs):
+    """A small table with bad rows: B in 1..3, N in 1..20, repeated rows, ids below 0, past B*N and in two videos."""
+    B, N = int(rs.randint(1, 4)), int(rs.randint(1, 21))
+    P = int(rs.randint(0, 60))
+    pool = rs.randint(0, N, size=(max(int(rs.randint(1, 8)), 1), 2))                 # few distinct pairs: real chains
+    table = pool[rs.randint(0, len(pool), size=P)] + N * rs.randint(0, B, size=(P, 1))
+    bad = rs.rand(P) < 0.2
+    table[bad] = rs.randint(-3, B * N + 3, size=(int(bad.sum()), 2))
+    return B, N, table.astype(np.int64)
+
+
+def test_fast_plan_check_accepts_what_the_walk_accepts():
+    """On plans written in numpy from plan_np, chains in sorted and in shuffled order: every table the GPU tests score,
+    the cross-video table, and 300 random small tables with bad rows pass both checks; the slots agree with plan_np."""
+    cases = [(B, N, tab) for B, N, _, _, tab in ref.TABLES.values()] + [ref.CROSS_VIDEO]
+    rs = np.random.RandomState(11)
+    cases += [_random_table(rs) for _ in range(300)]
+    for B, N, table in cases:
+        for order in (None, rs):
+            plan = ref.plan_arrays(table, B, N, rs=order)
+            want = ref.check_plan(plan, table, B, N)
+            slot = ref.check_plan_fast(plan, table, B, N)
+            Np = (N + 15) // 16 * 16
+            by_slot = {}
+            for p, k in enumerate(slot.tolist()):
+                if k >= 0:
+                    by_slot.setdefault((k // (Np * Np), k // Np % Np, k % Np), set()).add(p)
+            assert by_slot == want["chains"]
+
+
+def _mutation_base():
+    """B = 2, N = 5: video 0 has pairs (0,1) x3 [rows 0, 3, 6], (0,4) [1], (2,1) x2 [2, 7]; video 1 has (7,5) [4];
+    row 5 joins two videos, row 8 is out of range."""
+    table = np.array([[0, 1], [0, 4], [2, 1], [0, 1], [7, 5], [1, 7], [0, 1], [2, 1], [10, 3]], dtype=np.int64)
+    plan = ref.plan_arrays(table, 2, 5)
+    assert plan["head"][0, 0, 0] == 0 and plan["next"].tolist() == [3, -1, 7, 6, -1, -1, -1, -1, -1]
+    assert plan["head"][0, 1, 0] == 2 and plan["head"][0, 0, 1] == 1 and plan["head"][1, 0, 0] == 4
+    return table, plan
+
+
+def _swap_list_entries(p):
+    p["s_list"][0, [0, 1]] = p["s_list"][0, [1, 0]]
+
+
+def _count_off_by_one(p):
+    p["counts"][0, 1] += 1
+
+
+def _row_dropped_from_a_chain(p):
+    p["next"][0] = 6                    # 0 -> 6: row 3 is on no chain
+
+
+def _row_linked_into_the_neighbouring_chain(p):
+    p["next"][0], p["next"][7] = 6, 3   # (0,1): 0 -> 6; row 3 of (0,1) hangs at the end of the chain of (2,1): 2 -> 7 -> 3
+    p["next"][3] = -1                   # every row is still pointed at exactly once, each slot pair has one terminal row
+
+
+def _two_row_cycle_off_no_head(p):
+    p["head"][0, 0, 0] = 0
+    p["next"][0] = -1                   # head -> 0 ends at once
+    p["next"][3], p["next"][6] = 6, 3   # 3 <-> 6: in-degree one each, one terminal row (0) in the slot pair
+
+
+def _skipped_row_given_a_next(p):
+    p["next"][5] = -1
+    p["next"][8] = 1
+
+
+def _head_on_an_unnamed_slot_pair(p):
+    p["head"][0, 1, 1] = 1              # (2, 4) is in no row
+
+
+MUTATIONS = [_swap_list_entries, _count_off_by_one, _row_dropped_from_a_chain, _row_linked_into_the_neighbouring_chain,
+             _two_row_cycle_off_no_head, _skipped_row_given_a_next, _head_on_an_unnamed_slot_pair]
+
+
+def test_fast_plan_check_accepts_the_mutation_base():
+    table, plan = _mutation_base()
+    ref.check_plan(plan, table, 2, 5)
+    ref.check_plan_fast(plan, table, 2, 5)
+
+
+@pytest.mark.parametrize("mutate", MUTATIONS, ids=lambda f: f.__name__.strip("_"))
+def test_fast_plan_check_refuses_a_mutated_plan(mutate):
+    """Each hand-made defect alone, on a plan both checks accept: the vectorised check must raise."""
+    table, plan = _mutation_base()
+    mutate(plan)
+    with pytest.raises(AssertionError):
+        ref.check_plan_fast(plan, table, 2, 5)
+
+
+def test_fast_plan_check_catches_a_cycle_by_pointer_doubling_alone():
+    """The two-row cycle passes every local test (in-degrees, slots, one terminal row): only the doubling sees it."""
+    table, plan = _mutation_base()
+    _two_row_cycle_off_no_head(plan)
+    with pytest.raises(AssertionError, match="a cycle"):
+        ref.check_plan_fast(plan, table, 2, 5)
+
+
+def test_fast_plan_check_is_fast_at_the_sizes_the_gpu_tests_use():
+    """N = 2048 with every tracklet and a million-row table of 380 pairs: the shapes the walk cannot do."""
+    N = 2048
+    table = np.stack([np.arange(N), (np.arange(N) * 7 + 1) % N], axis=1)
+    plan = {"s_list": np.arange(N, dtype=np.int32)[None], "o_list": np.arange(N, dtype=np.int32)[None],
+            "counts": np.array([[N, N]], np.int32), "head": np.full((1, N, N), -1, np.int32),
+            "next": np.full((N,), -1, np.int32)}
+    plan["head"][0, table[:, 0], table[:, 1]] = np.arange(N)
+    ref.check_plan_fast(plan, table, 1, N)
+    table, plan = ref.long_chain_table(), None
+    assert table.shape == (256 * 4096 + 300, 2)
+    # chains written by a stable sort: row i of a pair points at row i + 1 of the same pair
+    _, slot, _, _ = ref.row_slots(table, 1, 20)
+    order = np.argsort(slot, kind="stable")
+    same = slot[order][1:] == slot[order][:-1]
+    nxt = np.full(len(table), -1, np.int32)
+    nxt[order[:-1][same]] = order[1:][same]
+    first = order[np.concatenate([[True], ~same])]
+    head = np.full(32 * 32, -1, np.int32)
+    head[slot[first]] = first
+    lists = np.zeros((1, 32), np.int32)
+    lists[0, :20] = np.arange(20)
+    plan = {"s_list": lists, "o_list": lists.copy(), "counts": np.array([[20, 20]], np.int32),
+            "head": head.reshape(1, 32, 32), "next": nxt}
+    ref.check_plan_fast(plan, table, 1, 20)
+    nxt[order[-1]] = order[-3]                                 # a cycle at the end of a 2760-row chain
+    with pytest.raises(AssertionError):
+        ref.check_plan_fast(plan, table, 1, 20)
