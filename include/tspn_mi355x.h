@@ -840,6 +840,48 @@ int tspn_eval_viou_f64(const double* boxes, const int64_t* traj, const double* v
 int tspn_eval_greedy_match_f64(const double* ov, const int64_t* groups, int64_t n_groups, int64_t max_group_gt,
                                double viou_threshold, uint8_t* det_ws, int8_t* hit, int32_t* match, void* stream);
 
+/* ---- training the span heads: anchor targets and losses (csrc/spanloss/tspn_span_loss.hip) ----------------------
+ * Build-defined (the reference's make_dpn_loss_evaluator, relpn/dpn_anchor.py:50-70, does not exist): the
+ * RPN scheme in one dimension, on the parametrisation tspn_decode_spans_f32 decodes.  One call serves one segment of P
+ * pairs, A anchors per frame, T frames.  Float64 arithmetic on the fp32 heads, the fp32 widths `sizes_host` (HOST
+ * pointer, A values > 0, copied into the launch) and the integer spans, one operation per step, no contraction.
+ *   heads fp32 [P, 3A, T]: rows [0, A) relationness logits, row A+2a / A+2a+1 = d_c / d_w of anchor a.
+ *   gt int64 [P, G, 2]: frames [start, end) per pair; a row with end <= start is padding (anywhere among the G rows);
+ *   a pair with only padding has no ground truth.
+ *   Anchor (t, a): lo = t - size_a/2, hi = t + size_a/2, unclipped (candidate index c = t*A + a of the decode).
+ *   IoU with a row [gs, ge): inter = max(0, min(hi, ge) - max(lo, gs)); union = (hi - lo) + (ge - gs) - inter;
+ *   iou = inter / union.
+ * tspn_span_anchor_labels:
+ *   matched int8 [P, A, T]: the ground-truth row of the largest IoU, the lower g on ties; -1 for a pair without
+ *   ground truth.  label int8 [P, A, T]: 1 if the matched IoU >= pos_iou, 0 if it is < neg_iou, else -1 (ignored);
+ *   low-quality rule: for every ground-truth row whose largest IoU over the pair's A*T anchors is > 0, every anchor
+ *   whose IoU with that row equals that maximum gets label 1 (its matched entry stays its own best row); every
+ *   anchor of a pair without ground truth is 0.
+ * tspn_span_loss_f32 (mask uint8 [P, A, T] or NULL: an anchor with mask 0 is ignored by the loss, not by the matching):
+ *   relationness, over anchors with label y in {0, 1}: l = max(x, 0) - x*y + log1p(exp(-|x|)), dl/dx = sigmoid(x) - y;
+ *   regression, over anchors with label 1 and matched row [gs, ge): t_c = ((gs + ge)/2 - t)/size_a,
+ *   t_w = log((ge - gs)/size_a) (the inverses of the decode), smooth L1 with beta on d = head - target:
+ *   |d| < beta: 0.5*d*d/beta, gradient d/beta; else |d| - 0.5*beta, gradient sign(d).
+ *   partials double [P, 4] = per pair (sum l, n_lab, sum (sl1(d_c) + sl1(d_w)), n_pos), reduced in a fixed lane order
+ *   and tree; dheads fp32 [P, 3A, T] = the un-normalised gradient, exactly 0 where an element enters no loss; every
+ *   element of both is written.
+ * tspn_span_loss_finish: out double [4] = (loss_relationness = sum l / max(1, n_lab), loss_duration_proposal =
+ *   sum sl1 / max(1, n_pos), n_lab, n_pos), the pairs' partials added in a fixed order by one workgroup; a second
+ *   launch divides rows [0, A) of dheads by max(1, n_lab) and rows [A, 3A) by max(1, n_pos), read from `out` on the
+ *   device: no host synchronisation.  n_lab and n_pos count the segment's anchors after the mask.
+ * A NaN head at an anchor that enters a loss makes that loss (and that gradient element) NaN; one at an ignored or
+ * masked anchor is not read.  Results are bit-equal from run to run.
+ * label, matched, partials, out and dheads are caller-owned outputs; the entries use no other scratch.
+ * Limits: G <= 8, A <= 16, A*T < 2^31; 0 <= neg_iou <= pos_iou <= 1; beta > 0.  P == 0 launches nothing, except that
+ * tspn_span_loss_finish still writes out = 0.  G == 0 is served: every anchor negative. */
+int tspn_span_anchor_labels(const int64_t* gt, const float* sizes_host, int64_t P, int64_t G, int64_t A, int64_t T,
+                            double pos_iou, double neg_iou, int8_t* label, int8_t* matched, void* stream);
+int tspn_span_loss_f32(const float* heads, const int64_t* gt, const float* sizes_host, const int8_t* label,
+                       const int8_t* matched, const uint8_t* mask, int64_t P, int64_t G, int64_t A, int64_t T,
+                       double beta, double* partials, float* dheads, void* stream);
+int tspn_span_loss_finish(const double* partials, int64_t P, int64_t A, int64_t T, double* out, float* dheads,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

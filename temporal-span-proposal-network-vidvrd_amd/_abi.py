@@ -181,6 +181,11 @@ PROTOTYPES = {
     "tspn_decode_span_relations_bf16_workspace_bytes": (_sz, [_i64] * 8),
     "tspn_decode_span_relations_bf16": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64,
                                                _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tspn_span_anchor_labels": (_int, [_vp, ctypes.POINTER(ctypes.c_float), _i64, _i64, _i64, _i64, ctypes.c_double,
+                                      ctypes.c_double, _vp, _vp, _vp]),
+    "tspn_span_loss_f32": (_int, [_vp, _vp, ctypes.POINTER(ctypes.c_float), _vp, _vp, _vp, _i64, _i64, _i64, _i64,
+                                 ctypes.c_double, _vp, _vp, _vp]),
+    "tspn_span_loss_finish": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
     "tspn_eval_traj_volume_f64": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "tspn_eval_viou_f64": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "tspn_eval_greedy_match_f64": (_int, [_vp, _vp, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _vp]),

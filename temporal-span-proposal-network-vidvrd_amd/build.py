@@ -20,6 +20,7 @@ CSRC_EVAL = os.path.join(CSRC, "eval")   # evaluation kernels (their variant tab
 CSRC_REL = os.path.join(CSRC, "relations")   # span relation decode (its variant table: tests/relations_kernel_variants.py)
 CSRC_PAIRLIST = os.path.join(CSRC, "pairlist")   # bf16 pair-list stage (its variant table: tests/pairlist_kernel_variants.py)
 CSRC_SPANBF16 = os.path.join(CSRC, "spanbf16")   # bf16 span pooling / span relations (its variant table: tests/spanbf16_kernel_variants.py)
+CSRC_SPANLOSS = os.path.join(CSRC, "spanloss")   # span anchor targets and losses (its variant table: tests/spanloss_kernel_variants.py)
 LIB_NAME = "libtspn_mi355x.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 ARCH = "gfx950"
@@ -49,13 +50,13 @@ NO_SPILL_KERNELS = ("conv3_wino63_kernel", "heads_pairgrid4_kernel", "heads_pair
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC_EVAL, "*.hip")) +
                   glob.glob(os.path.join(CSRC_REL, "*.hip")) + glob.glob(os.path.join(CSRC_PAIRLIST, "*.hip")) +
-                  glob.glob(os.path.join(CSRC_SPANBF16, "*.hip")))
+                  glob.glob(os.path.join(CSRC_SPANBF16, "*.hip")) + glob.glob(os.path.join(CSRC_SPANLOSS, "*.hip")))
 
 
 def _headers():
     return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC_EVAL, "*.h")) + \
         glob.glob(os.path.join(CSRC_REL, "*.h")) + glob.glob(os.path.join(CSRC_PAIRLIST, "*.h")) + \
-        glob.glob(os.path.join(CSRC_SPANBF16, "*.h")) + \
+        glob.glob(os.path.join(CSRC_SPANBF16, "*.h")) + glob.glob(os.path.join(CSRC_SPANLOSS, "*.h")) + \
         glob.glob(os.path.join(ROOT, "include", "*.h")) + \
         [os.path.abspath(__file__)]
 

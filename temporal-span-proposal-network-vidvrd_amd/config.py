@@ -81,7 +81,11 @@ _DEFAULTS = {
                 "CONV_F16X3_AFTER": 4,
                 # build extension: tracklet features handed over in HOST memory (predict.py:50-57) go to the device in
                 # chunks of this many videos, pipelined under the encoder (model._HostPipeline)
-                "HOST_CHUNK_VIDEOS": 4},
+                "HOST_CHUNK_VIDEOS": 4,
+                # build extension: training the span heads from ground-truth spans (target field 'spans'):
+                # an anchor is positive from POS_IOU on, negative below NEG_IOU, ignored in between; SMOOTH_L1_BETA is the
+                # width of the quadratic zone of the regression loss
+                "SPAN_LOSS": {"POS_IOU": 0.7, "NEG_IOU": 0.3, "SMOOTH_L1_BETA": 1.0 / 9.0}},
     },
     "ETC": {"RANDOM_SEED": 0, "MODEL_DUMP_FILE": "baseline_weights_epoch_100.pt"},
 }

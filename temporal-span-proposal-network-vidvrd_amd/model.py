@@ -369,6 +369,29 @@ class _TemporalHeadsTrackletFn(torch.autograd.Function):
         return None, None, d_conv_w, du.sum((0, 2)), d_head_w, g.sum((0, 2))
 
 
+class _SpanLossFn(torch.autograd.Function):
+    """(loss_relationness, loss_duration_proposal) of one segment from its heads [P,3A,T] and ground-truth spans
+    [P,G,2]: anchor labels, both losses and their gradient in three HIP entries (ops.span_anchor_labels,
+    ops.span_loss), nothing synchronised.  The forward already holds the gradient of each loss with respect to its own
+    rows of the heads; the backward multiplies the two row groups by the upstream gradients."""
+
+    @staticmethod
+    def forward(ctx, heads, gt, sizes, pos_iou, neg_iou, beta):
+        heads = heads.contiguous()
+        label, matched = ops.span_anchor_labels(gt, sizes, heads.shape[2], pos_iou=pos_iou, neg_iou=neg_iou)
+        out, dheads = ops.span_loss(heads, gt, sizes, label, matched, beta=beta)
+        ctx.save_for_backward(dheads)
+        ctx.num_anchors = len(sizes)
+        return out[0].float(), out[1].float()
+
+    @staticmethod
+    def backward(ctx, g_rel, g_reg):
+        dheads, = ctx.saved_tensors
+        a = ctx.num_anchors
+        scale = torch.cat([g_rel.reshape(1).expand(a), g_reg.reshape(1).expand(2 * a)]).to(dheads.dtype)
+        return dheads * scale.view(1, 3 * a, 1), None, None, None, None, None
+
+
 class RelationPredictor(nn.Module):
     """Predicate-classification head (reference lib/modeling/model.py:76-88)."""
 
@@ -550,6 +573,24 @@ class DPN(nn.Module):
         self.dpn_head = DPNHead(in_channels, num_windows)
         self.top_k_proposals = cfg.RELPN.DPN.NUM_DURATION_PROPOSALS  # RelNMS stub: rel_nms.py:11
         self._cache = _DeviceCache()
+        self._anchor_sizes_cfg = getattr(cfg.RELPN.DPN, "ANCHOR_SIZES", None)
+        # build extension: training from ground-truth spans (target field 'spans')
+        sl = getattr(cfg.RELPN.DPN, "SPAN_LOSS", None)
+        self.span_pos_iou = float(getattr(sl, "POS_IOU", 0.7))
+        self.span_neg_iou = float(getattr(sl, "NEG_IOU", 0.3))
+        self.span_beta = float(getattr(sl, "SMOOTH_L1_BETA", 1.0 / 9.0))
+
+    def anchor_sizes(self, num_frames):
+        """Anchor widths (frames) of the A anchors per location.  cfg.RELPN.DPN.ANCHOR_SIZES when it
+        is a sequence of length A; the reference ships a placeholder int there (defaults.py:66), so
+        the default is the proportions of its own example (anchor_generator.py:116-123:
+        sizes (15,30,45,60) on T=60): size_a = (a+1)*T/A.  The one rule for decoding (BaseModel.anchor_sizes) and for
+        training from spans."""
+        a = self.dpn_head.num_windows
+        cfg_sizes = self._anchor_sizes_cfg
+        if isinstance(cfg_sizes, (list, tuple)) and len(cfg_sizes) == a:
+            return [float(v) for v in cfg_sizes]
+        return [(i + 1) * float(num_frames) / a for i in range(a)]
 
     # packed device weights -------------------------------------------------
     def _head_weights(self, dev):
@@ -649,9 +690,15 @@ class DPN(nn.Module):
         duration_proposals = dpn_head(pair feats); loss_duration = BCEWithLogits(duration_proposals,
         target.get_field('duration')), summed over the segments like loss_rel (model.py:62-64).  A target
         field 'relness' [P,A,T], when present, adds `loss_relationness` on the relationness head (loss name
-        from relpn/dpn_anchor.py:62-65)."""
+        from relpn/dpn_anchor.py:62-65).  Targets with a field 'spans' instead take _forward_train_spans."""
         if target_list is None:
-            raise ValueError("DPN training needs target_list with a 'duration' field [P,2A,T]")
+            raise ValueError("DPN training needs target_list with a 'duration' field [P,2A,T] or a 'spans' field [P,G,2]")
+        with_spans = [tlist.has_field("spans") for tlist in target_list]
+        if any(with_spans):
+            if not all(with_spans) or any(tlist.has_field("duration") for tlist in target_list):
+                raise ValueError("DPN training takes either 'spans' [P,G,2] (anchor targets and losses, DESIGN.md §2) or "
+                                 "'duration' [P,2A,T] (+ 'relness') in every target of a batch, not both")
+            return self._forward_train_spans(pair_list, target_list)
         props, loss_dur, loss_rel = [], 0, None
         for plist, tlist in zip(pair_list, target_list):
             tp = self._wrap(self._train_heads(plist))
@@ -670,6 +717,24 @@ class DPN(nn.Module):
         if loss_rel is not None:
             losses["loss_relationness"] = loss_rel
         return props, losses
+
+    def _forward_train_spans(self, pair_list, target_list):
+        """Targets with a field 'spans' int64 [P,G,2] (ground-truth frames [start, end) per pair, end <= start =
+        padding): the RPN scheme in one dimension the reference intends (relpn/dpn_anchor.py:50-70) -- anchors labelled by
+        IoU, `loss_relationness` on the labelled anchors, `loss_duration_proposal` on the positive ones, on the
+        parametrisation decode_spans decodes; both summed over the segments like loss_rel."""
+        props, loss_rel, loss_reg = [], 0, 0
+        for plist, tlist in zip(pair_list, target_list):
+            heads = self._train_heads(plist)
+            gt = tlist.get_field("spans")
+            gt = (gt if isinstance(gt, torch.Tensor) else torch.as_tensor(np.asarray(gt))).to(heads.device, torch.int64)
+            if gt.dim() != 3 or gt.shape[0] != heads.shape[0] or gt.shape[2] != 2:
+                raise ValueError(f"target field 'spans' must be [P,G,2] with P = {heads.shape[0]}, got {tuple(gt.shape)}")
+            l_rel, l_reg = _SpanLossFn.apply(heads, gt.contiguous(), self.anchor_sizes(heads.shape[2]), self.span_pos_iou,
+                                             self.span_neg_iou, self.span_beta)
+            loss_rel, loss_reg = loss_rel + l_rel, loss_reg + l_reg
+            props.append(self._wrap(heads))
+        return props, {"loss_relationness": loss_rel, "loss_duration_proposal": loss_reg}
 
     def forward(self, pair_list, target_list=None):
         if self.training:
@@ -944,7 +1009,6 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
         self.classifier = RelationPredictor(in_channels=cfg.PREDICT.FEATURE_DIM,
                                             out_channels=cfg.PREDICT.PREDICATE_NUM,
                                             fuse_preprocess=getattr(cfg.PREDICT, "FUSE_PREPROCESS", False))
-        self._anchor_sizes_cfg = getattr(cfg.RELPN.DPN, "ANCHOR_SIZES", None)
         self.pool_top_span = bool(getattr(cfg.RELPN.DPN, "POOL_TOP_SPAN", False))
         # build extension: also return the bbox half of the pair builder (relative geometry [P,8,T]) from the
         # eval forward.  Nothing downstream of forward consumes it, so it is off unless asked for
@@ -1409,15 +1473,9 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
         return out
 
     def anchor_sizes(self, num_frames):
-        """Anchor widths (frames) of the A anchors per location.  cfg.RELPN.DPN.ANCHOR_SIZES when it
-        is a sequence of length A; the reference ships a placeholder int there (defaults.py:66), so
-        the default is the proportions of its own example (anchor_generator.py:116-123:
-        sizes (15,30,45,60) on T=60): size_a = (a+1)*T/A."""
-        a = self.relpn.duration_proposal_network.dpn_head.num_windows
-        cfg_sizes = getattr(self, "_anchor_sizes_cfg", None)
-        if isinstance(cfg_sizes, (list, tuple)) and len(cfg_sizes) == a:
-            return [float(v) for v in cfg_sizes]
-        return [(i + 1) * float(num_frames) / a for i in range(a)]
+        """Anchor widths (frames) of the A anchors per location (DPN.anchor_sizes: the rule lives with the heads it
+        parametrises, so that training from spans and decoding cannot disagree)."""
+        return self.relpn.duration_proposal_network.anchor_sizes(num_frames)
 
     def decode_spans(self, duration_proposals, sizes=None, top_k=None, nms_threshold=0.5):
         """Temporal span proposals per pair from `forward`'s duration_proposals (span decode +

@@ -16,6 +16,7 @@ __all__ = [
     "predicate_head", "feature_preprocess_", "ppn_pair_matrix_topk", "traj_iou", "traj_iou_tail", "pair_index",
     "pair_gather", "pack_conv3", "conv3", "conv3_tc", "pack_conv3_wino63", "conv3_tc_wino63", "pack_conv3_wino63_f16x3", "conv3_tc_wino63_f16x3", "heads", "heads_pairgrid", "temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
     "forward_fused", "temporal_encoder_heads", "fused_workspace_bytes", "fused_bf16_workspace_bytes", "decode_topk", "decode_spans", "decode_span_relations",
+    "span_anchor_labels", "span_loss",
     "cast_bf16", "pack_conv3_bf16", "pack_heads_bf16", "conv3_tc_bf16", "heads_pairgrid_bf16",
     "pair_plan", "heads_pairlist_bf16",
     "transpose_cast_bf16", "temporal_encoder_heads_bf16",
@@ -682,6 +683,68 @@ def decode_spans(heads, sizes, top_k=64, nms_threshold=0.5, pre_nms=1024):
                                                 _p(out["anchor"]), _p(out["span"]), _p(out["span_f"]),
                                                 _p(out["score"]), _p(out["count"]), _stream()))
     return out
+
+
+def _span_gt(gt, P, who):
+    """gt int64 [P,G,2] of the span-loss entries -> G."""
+    _dev(gt, f"{who}: gt", torch.int64)
+    if gt.dim() != 3 or gt.shape[2] != 2 or (P is not None and gt.shape[0] != P):
+        raise ValueError(f"{who}: gt must be [P,G,2]" + ("" if P is None else f" with P = {P}") + f", got {tuple(gt.shape)}")
+    return gt.shape[1]
+
+
+def _anchor_sizes(sizes, who):
+    sizes = [float(v) for v in sizes]
+    if not sizes:
+        raise ValueError(f"{who}: no anchor sizes")
+    return (ctypes.c_float * len(sizes))(*sizes), len(sizes)
+
+
+def span_anchor_labels(gt, sizes, num_frames, pos_iou=0.7, neg_iou=0.3):
+    """Training targets of the span heads (tspn_span_anchor_labels): gt int64 [P,G,2] frames [start, end)
+    per pair (end <= start = padding), `sizes` the A anchor widths -> (label int8 [P,A,T] in {1, 0, -1 = ignored},
+    matched int8 [P,A,T] = the ground-truth row of the largest IoU, -1 for a pair without ground truth)."""
+    who = "span_anchor_labels"
+    G = _span_gt(gt, None, who)
+    P, T = gt.shape[0], int(num_frames)
+    sz, A = _anchor_sizes(sizes, who)
+    label = torch.empty((P, A, T), dtype=torch.int8, device=gt.device)
+    matched = torch.empty_like(label)
+    _abi.check(_abi.lib().tspn_span_anchor_labels(_p(gt), sz, P, G, A, T, float(pos_iou), float(neg_iou), _p(label),
+                                                  _p(matched), _stream()))
+    return label, matched
+
+
+def span_loss(heads, gt, sizes, label, matched, mask=None, beta=1.0 / 9.0):
+    """Relationness and span-regression losses of one segment with their gradient (tspn_span_loss_f32 +
+    tspn_span_loss_finish): heads fp32 [P,3A,T], gt int64 [P,G,2], label / matched int8 [P,A,T] from
+    span_anchor_labels, mask uint8 [P,A,T] or None (0 = the loss ignores the anchor).  Returns (losses float64 [4] =
+    (loss_relationness, loss_duration_proposal, n_lab, n_pos), dheads fp32 [P,3A,T] = the gradient of each loss with
+    respect to its own rows, normalised).  Nothing is synchronised."""
+    who = "span_loss"
+    _dev(heads, f"{who}: heads")
+    if heads.dim() != 3:
+        raise ValueError(f"{who}: heads must be [P,3A,T], got {tuple(heads.shape)}")
+    P, H, T = heads.shape
+    sz, A = _anchor_sizes(sizes, who)
+    if H != 3 * A:
+        raise ValueError(f"{who}: heads has {H} channels, expected 3*A = {3 * A}")
+    G = _span_gt(gt, P, who)
+    for name, o, dt in (("label", label, torch.int8), ("matched", matched, torch.int8), ("mask", mask, torch.uint8)):
+        if o is None and name == "mask":
+            continue
+        _dev(o, f"{who}: {name}", dt)
+        if tuple(o.shape) != (P, A, T):
+            raise ValueError(f"{who}: {name} must be [P,A,T] = {(P, A, T)}, got {tuple(o.shape)}")
+    dev = heads.device
+    partials = torch.empty((P, 4), dtype=torch.float64, device=dev)
+    out = torch.empty((4,), dtype=torch.float64, device=dev)
+    dheads = torch.empty_like(heads)
+    lib, stream = _abi.lib(), _stream()
+    _abi.check(lib.tspn_span_loss_f32(_p(heads), _p(gt), sz, _p(label), _p(matched), _p(mask), P, G, A, T, float(beta),
+                                      _p(partials), _p(dheads), stream))
+    _abi.check(lib.tspn_span_loss_finish(_p(partials), P, A, T, _p(out), _p(dheads), stream))
+    return out, dheads
 
 
 def _fused_desc(feats, pairs, B, N, conv_packed, conv_bias, head_w, head_b, cls_w, cls_b):
