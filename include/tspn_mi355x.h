@@ -59,7 +59,8 @@ extern "C" {
  * Still 7 (additive, no layout or signature changed): tspn_pair_plan_i32, tspn_heads_pairlist_bf16 (+ _workspace_bytes),
  * tspn_forward_fused_bf16_pairs (+ _workspace_bytes): the bf16 path on an arbitrary pair table;
  * tspn_pack_span_cls_bf16, tspn_span_predicate_bf16, tspn_decode_span_relations_bf16 (+ _workspace_bytes): span pooling and
- * the relations with their spans on bf16 segments. */
+ * the relations with their spans on bf16 segments;
+ * tspn_heads_pairgrid_f16x3 (+ _split_bytes, _set_force_exact): the fp32 path's pair stage on split-fp16 MFMAs. */
 #define TSPN_ABI_VERSION 7
 
 enum {
@@ -332,6 +333,23 @@ int tspn_heads_f32(int mode, const float* a, const float* b, int64_t lda,
 int tspn_heads_pairgrid_f32(const float* y, int64_t B, int64_t N, int64_t C, int64_t T,
                             const float* Wh, const float* bh, int64_t H, float* out,
                             void* stream);
+
+/* The same pair stage on split-fp16 MFMAs (csrc/pairf16): relu(U[s] + V[o]) is formed in fp32 and split into two fp16
+ * pieces, the head weights likewise (scaled per head by a power of two), three f16 MFMAs per product block; every
+ * product is carried to about 2^-21 of its size, the sums are fp32.  y[B*N, 2C, ldt] with ldt >= T frames per row.
+ * Needs C % 32 == 0, even T, ldt % 4 == 0, y 16-byte and out 8-byte aligned, a video's projections below 2 GB
+ * (TSPN_EUNSUPPORTED otherwise); H <= 16.  A workgroup tile (8 subjects x 8 objects x 32 frames) in which some
+ * |U[s] + V[o]| of a written output is not <= 2^15 (NaN and infinities included), and every tile when a head's weights
+ * are non-finite or all below 2^-100, is computed by one fp32 fmaf chain in channel order per output instead.
+ * split_buf: split_bytes >= tspn_heads_pairgrid_f16x3_split_bytes(C, H) bytes of 16-byte aligned scratch, every byte of
+ * which the call writes before it reads it (0 bytes for a C or H the entry refuses).
+ * tspn_heads_pairgrid_f16x3_set_force_exact(1) sends every tile of later calls (this entry and the fused pass) through
+ * the fp32 chain, process-wide, for tests; returns the previous setting.                                           */
+size_t tspn_heads_pairgrid_f16x3_split_bytes(int64_t C, int64_t H);
+int tspn_heads_pairgrid_f16x3_set_force_exact(int on);
+int tspn_heads_pairgrid_f16x3(const float* y, int64_t ldt, int64_t B, int64_t N, int64_t C, int64_t T,
+                              const float* Wh, const float* bh, int64_t H, void* split_buf, size_t split_bytes,
+                              float* out, void* stream);
 
 /* ---- a3: RelOIPool over time --------------------------------------------
  * mean over t of x[R, T, D] -> out[R, D]   (layout_tc = 1, tracklet layout)

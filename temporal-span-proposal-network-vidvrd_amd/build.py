@@ -20,6 +20,7 @@ CSRC_EVAL = os.path.join(CSRC, "eval")   # evaluation kernels (their variant tab
 CSRC_REL = os.path.join(CSRC, "relations")   # span relation decode (its variant table: tests/relations_kernel_variants.py)
 CSRC_PAIRLIST = os.path.join(CSRC, "pairlist")   # bf16 pair-list stage (its variant table: tests/pairlist_kernel_variants.py)
 CSRC_SPANBF16 = os.path.join(CSRC, "spanbf16")   # bf16 span pooling / span relations (its variant table: tests/spanbf16_kernel_variants.py)
+CSRC_PAIRF16 = os.path.join(CSRC, "pairf16")   # fp32 path's pair stage on split-fp16 MFMAs (its variant table: tests/pairf16_kernel_variants.py)
 CSRC_SPANLOSS = os.path.join(CSRC, "spanloss")   # span anchor targets and losses (its variant table: tests/spanloss_kernel_variants.py)
 LIB_NAME = "libtspn_mi355x.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
@@ -41,7 +42,7 @@ RES_PATH = os.path.join(HERE, "kernel_resources.json")   # next to the .so (git-
 NO_SPILL_KERNELS = ("conv3_wino63_kernel", "heads_pairgrid4_kernel", "heads_pairgrid3_kernel",
                     "conv2d_nhwc_frag_kernel", "conv2d_nhwc_bf16_kernel", "conv2d_nhwc_cin4_kernel",
                     "bottleneck_bf16_kernel", "bottleneck_pipe_bf16_kernel", "conv3_bf16_big_kernel", "heads_pairgrid_bf16_kernel",
-                    "heads_pairlist_bf16_kernel",
+                    "heads_pairlist_bf16_kernel", "heads_pair_f16x3_kernel",
                     #  254 - 256 and 233 - 234 VGPRs, hand-counted s_waitcnt vmcnt(N) and the "keep the store data
                     # registers live" hazard fence: a spill would change the VMEM counts and could defeat the fence
                     "tail_io_bf16_kernel", "bottleneck_block_bf16_kernel")
@@ -50,13 +51,15 @@ NO_SPILL_KERNELS = ("conv3_wino63_kernel", "heads_pairgrid4_kernel", "heads_pair
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC_EVAL, "*.hip")) +
                   glob.glob(os.path.join(CSRC_REL, "*.hip")) + glob.glob(os.path.join(CSRC_PAIRLIST, "*.hip")) +
-                  glob.glob(os.path.join(CSRC_SPANBF16, "*.hip")) + glob.glob(os.path.join(CSRC_SPANLOSS, "*.hip")))
+                  glob.glob(os.path.join(CSRC_SPANBF16, "*.hip")) + glob.glob(os.path.join(CSRC_SPANLOSS, "*.hip")) +
+                  glob.glob(os.path.join(CSRC_PAIRF16, "*.hip")))
 
 
 def _headers():
     return glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(CSRC_EVAL, "*.h")) + \
         glob.glob(os.path.join(CSRC_REL, "*.h")) + glob.glob(os.path.join(CSRC_PAIRLIST, "*.h")) + \
         glob.glob(os.path.join(CSRC_SPANBF16, "*.h")) + glob.glob(os.path.join(CSRC_SPANLOSS, "*.h")) + \
+        glob.glob(os.path.join(CSRC_PAIRF16, "*.h")) + \
         glob.glob(os.path.join(ROOT, "include", "*.h")) + \
         [os.path.abspath(__file__)]
 

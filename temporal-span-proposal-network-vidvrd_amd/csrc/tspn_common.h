@@ -124,6 +124,12 @@ int wino63_f16x3_contract(void* workspace, size_t workspace_bytes, int64_t B, in
                           void* stream);
 int heads_pairgrid(const float* y, int64_t ldt, int64_t B, int64_t N, int64_t C, int64_t T,
                    const float* Wh, const float* bh, int64_t H, float* out, void* stream, float* Wp12 = nullptr);
+// The canonical pair stage on split-fp16 MFMAs (pairf16/tspn_heads_pair_f16x3.hip).  `split_buf`: the call's split head
+// weights and flag word, heads_pair_f16x3_split_bytes(C, H) bytes (0 where C or H is refused), all written by the call.
+size_t heads_pair_f16x3_split_bytes(int64_t C, int64_t H);
+bool heads_pair_f16x3_supported(const float* y, int64_t ldt, int64_t N, int64_t C, int64_t T, int64_t H, const float* out);
+int heads_pair_f16x3(const float* y, int64_t ldt, int64_t B, int64_t N, int64_t C, int64_t T, const float* Wh,
+                     const float* bh, int64_t H, void* split_buf, size_t split_bytes, float* out, void* stream);
 inline size_t align_up(size_t a, size_t b) { return (a + b - 1) / b * b; }
 int linear(const float* x, int64_t P, int64_t F, int64_t ldx, const float* W, int64_t ldw,
            const float* b, int64_t K, float* out, int apply_sigmoid, void* workspace,

@@ -20,8 +20,9 @@
 namespace {
 
 struct FusedLayout {
-  size_t xt, y, bias2, fbar, pooled, lin, vt, hwp, hot, total;
+  size_t xt, y, bias2, fbar, pooled, lin, vt, hwp, hot, psplit, total;
   size_t vt_bytes;
+  size_t psplit_bytes;
   size_t lin_bytes;
 };
 
@@ -49,7 +50,11 @@ FusedLayout layout_of(const tspn_fused_desc* d) {
     L.vt_bytes = tspn::wino63_f16x3_workspace_bytes((int64_t)NT, (int64_t)T, (int64_t)D, (int64_t)(2 * C));
   L.vt = take(L.vt_bytes);
   L.hwp = take(C * 12 * sizeof(float));   // head weights packed [C][12] for the scalar-weight pair stage (H == 12)
-  L.hot = take(TSPN_CONV_CHECK_SCRATCH_BYTES);   // accuracy guard: scratch of tspn_conv3_spot_check_f32 (tspn_conv_guard.hip)
+  // split-fp16 pair stage of the promoted path (H == 12): its split head weights and flag word, written by every call
+  L.psplit_bytes = (d->conv_algo == TSPN_CONV_WINOGRAD63_F16X3 && 3 * d->A == 12)
+                       ? tspn::heads_pair_f16x3_split_bytes((int64_t)C, 12) : 0;
+  L.psplit = take(L.psplit_bytes);
+  L.hot = take(TSPN_CONV_CHECK_SCRATCH_BYTES);   // accuracy guard: scratch of tspn_conv3_spot_check_f32 (tspn_conv_guard.hip); stays LAST
   L.total = off;
   return L;
 }
@@ -171,9 +176,16 @@ extern "C" int tspn_forward_fused_f32(const tspn_fused_desc* d, void* stream) {
   if (d->canonical_pairs) {
     TSPN_REQUIRE(d->P == d->B * d->N * (d->N - 1), TSPN_EINVAL,
                  "tspn_forward_fused: canonical_pairs needs P == B*N*(N-1) (P=%lld)", (long long)d->P);
-    if ((rc = tspn::heads_pairgrid(y, ldy, d->B, d->N, C, T, d->head_w, d->head_b, H, d->out_heads,
-                                   stream, reinterpret_cast<float*>(ws + L.hwp))))
-      return rc;
+    // behind the split-fp16 conv (the form BaseModel promotes to) the pair stage runs on split-fp16 MFMAs as well;
+    // every other call keeps the fp32 chain of heads_pairgrid4_kernel bit for bit
+    if (f16x3 && H == 12 && L.psplit_bytes > 0 &&
+        tspn::heads_pair_f16x3_supported(y, ldy, d->N, C, T, H, d->out_heads))
+      rc = tspn::heads_pair_f16x3(y, ldy, d->B, d->N, C, T, d->head_w, d->head_b, H, ws + L.psplit, L.psplit_bytes,
+                                  d->out_heads, stream);
+    else
+      rc = tspn::heads_pairgrid(y, ldy, d->B, d->N, C, T, d->head_w, d->head_b, H, d->out_heads, stream,
+                                reinterpret_cast<float*>(ws + L.hwp));
+    if (rc) return rc;
   } else if ((rc = tspn_heads_f32(1, y, y + C * T, 2 * C, d->pairs, d->pairs + 1, 2, nullptr,
                                   d->head_w, d->head_b, H, d->P, C, T, d->out_heads, stream))) {
     return rc;

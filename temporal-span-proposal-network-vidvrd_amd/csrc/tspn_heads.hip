@@ -160,19 +160,7 @@ constexpr int PG_S = 8, PG_O = 8, PG_CK = 16, PG_T = 32;
 constexpr int PG_ROWS = PG_S + PG_O;
 constexpr int PG_STAGE = PG_ROWS * PG_CK * PG_T;  // floats per LDS buffer (32 KB)
 
-// Pair-stage map: workgroup -> (group = (video, frame block), subject block sb, object block ob).  The nsb * nob
-// workgroups of one group read the same tracklet rows and walk the channels in step, so they are placed on ONE XCD
-// (ids congruent mod 8 share an XCD) and dispatched back to back: each row chunk then comes from HBM once and from that
-// XCD's L2 for the other blocks.  The grid is rounded up to whole rounds of 8 groups: a kernel returns where the
-// group number is >= its ngroups (uniform per workgroup, before any barrier).
-__device__ __forceinline__ int64_t pair_stage_group(int id, int nsb, int nob, int& sb, int& ob) {
-  const int per_group = nsb * nob;
-  const int xcd = id & 7, k = id >> 3;
-  const int member = k % per_group;
-  sb = member / nob;
-  ob = member - sb * nob;
-  return (int64_t)(k / per_group) * 8 + xcd;
-}
+// (the workgroup -> (group, subject block, object block) map of the pair-stage kernels: pair_stage_group, tspn_device.h)
 
 template <bool VEC2>
 __global__ __launch_bounds__(256, 2) void heads_pairgrid_kernel(

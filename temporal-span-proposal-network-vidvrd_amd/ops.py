@@ -14,7 +14,8 @@ from . import _abi
 
 __all__ = [
     "predicate_head", "feature_preprocess_", "ppn_pair_matrix_topk", "traj_iou", "traj_iou_tail", "pair_index",
-    "pair_gather", "pack_conv3", "conv3", "conv3_tc", "pack_conv3_wino63", "conv3_tc_wino63", "pack_conv3_wino63_f16x3", "conv3_tc_wino63_f16x3", "heads", "heads_pairgrid", "temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
+    "pair_gather", "pack_conv3", "conv3", "conv3_tc", "pack_conv3_wino63", "conv3_tc_wino63", "pack_conv3_wino63_f16x3", "conv3_tc_wino63_f16x3", "heads", "heads_pairgrid", "heads_pairgrid_f16x3", "heads_pairgrid_f16x3_split_bytes",
+    "heads_pairgrid_f16x3_set_force_exact", "temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
     "forward_fused", "temporal_encoder_heads", "fused_workspace_bytes", "fused_bf16_workspace_bytes", "decode_topk", "decode_spans", "decode_span_relations",
     "span_anchor_labels", "span_loss",
     "cast_bf16", "pack_conv3_bf16", "pack_heads_bf16", "conv3_tc_bf16", "heads_pairgrid_bf16",
@@ -571,6 +572,38 @@ def heads_pairgrid(y, B, N, head_w, head_b):
     out = torch.empty((B * N * max(N - 1, 0), H, T), dtype=torch.float32, device=y.device)
     _abi.check(_abi.lib().tspn_heads_pairgrid_f32(_p(y), B, N, C, T, _p(head_w), _p(head_b), H, _p(out),
                                                   _stream()))
+    return out
+
+
+def heads_pairgrid_f16x3_split_bytes(C, H):
+    """Bytes of scratch heads_pairgrid_f16x3 needs for C channels and H heads (0 for a C or H it refuses)."""
+    return int(_abi.lib().tspn_heads_pairgrid_f16x3_split_bytes(int(C), int(H)))
+
+
+def heads_pairgrid_f16x3_set_force_exact(on):
+    """1 = every tile of the split-fp16 pair stage takes its fp32 chain (tests), 0 = default.  Process-wide; returns the
+    previous setting."""
+    prev = _abi.lib().tspn_heads_pairgrid_f16x3_set_force_exact(int(on))
+    if prev < 0:
+        _abi.check(prev)
+    return prev
+
+
+def heads_pairgrid_f16x3(y, B, N, head_w, head_b, T=None, split_buf=None, out=None):
+    """The canonical pair stage on split-fp16 MFMAs: y[B*N, 2C, ldt] (the first T frames of a row are used, T = ldt by
+    default) -> out[B*N*(N-1), H, T].  `split_buf`: uint8 scratch of heads_pairgrid_f16x3_split_bytes(C, H) bytes."""
+    _dev(y, "y"); _dev(head_w, "head_w")
+    NT, C2, ldt = y.shape
+    T = ldt if T is None else int(T)
+    C, H = C2 // 2, head_w.shape[0]
+    if NT != B * N or head_w.shape[1] != C:
+        raise ValueError("heads_pairgrid_f16x3: shape mismatch")
+    if split_buf is None:
+        split_buf = torch.empty(max(heads_pairgrid_f16x3_split_bytes(C, H), 16), dtype=torch.uint8, device=y.device)
+    if out is None:
+        out = torch.empty((B * N * max(N - 1, 0), H, T), dtype=torch.float32, device=y.device)
+    _abi.check(_abi.lib().tspn_heads_pairgrid_f16x3(_p(y), ldt, B, N, C, T, _p(head_w), _p(head_b), H, _p(split_buf),
+                                                    split_buf.numel(), _p(out), _stream()))
     return out
 
 
