@@ -336,11 +336,15 @@ int tspn_heads_pairgrid_f32(const float* y, int64_t B, int64_t N, int64_t C, int
 
 /* The same pair stage on split-fp16 MFMAs (csrc/pairf16): relu(U[s] + V[o]) is formed in fp32 and split into two fp16
  * pieces, the head weights likewise (scaled per head by a power of two), three f16 MFMAs per product block; every
- * product is carried to about 2^-21 of its size, the sums are fp32.  y[B*N, 2C, ldt] with ldt >= T frames per row.
+ * product is carried to about 2^-21 of its size, the sums are fp32: with u = 2^-24 and S = |b_h| + sum_c |w_hc| a_c an
+ * output is within (20 + C / 32) u S + 2^-35 (max_c |w_hc| sum_c a_c + sum_c |w_hc|) of the exact sum, the second term
+ * being fp16's subnormal spacing on the low pieces (tests/test_gpu_pair_stage_f16x3_bound.py).
+ * y[B*N, 2C, ldt] with ldt >= T frames per row; frames [T, ldt) reach no output, whatever they hold.
  * Needs C % 32 == 0, even T, ldt % 4 == 0, y 16-byte and out 8-byte aligned, a video's projections below 2 GB
- * (TSPN_EUNSUPPORTED otherwise); H <= 16.  A workgroup tile (8 subjects x 8 objects x 32 frames) in which some
- * |U[s] + V[o]| of a written output is not <= 2^15 (NaN and infinities included), and every tile when a head's weights
- * are non-finite or all below 2^-100, is computed by one fp32 fmaf chain in channel order per output instead.
+ * (TSPN_EUNSUPPORTED otherwise); H <= 16.  A workgroup tile (8 subjects x 8 objects x 32 frames) in which some |U[s]|
+ * or some |V[o]| of a written output is not <= 2^14 -- each half on its own, whatever their sum is; NaN and infinities
+ * included -- and every tile when a head's weights are non-finite, all below 2^-100 or reach 2^100, is computed by one
+ * fp32 fmaf chain in channel order per output instead.
  * split_buf: split_bytes >= tspn_heads_pairgrid_f16x3_split_bytes(C, H) bytes of 16-byte aligned scratch, every byte of
  * which the call writes before it reads it (0 bytes for a C or H the entry refuses).
  * tspn_heads_pairgrid_f16x3_set_force_exact(1) sends every tile of later calls (this entry and the fused pass) through

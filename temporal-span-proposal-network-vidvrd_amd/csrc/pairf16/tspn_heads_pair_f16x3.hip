@@ -9,12 +9,17 @@
 // split the same way once per call (pairf16_pack_kernel).  Three v_mfma_f32_16x16x32_f16 per 16 frames x 32 channels,
 //     acc_hi += wh * ah,     acc_lo += wh * al + wl * ah,
 // and  (acc_hi + 2^-11 acc_lo) / scale_h + bh[h]  in the epilogue: every product is carried to about 2^-21 of |w a|
-// (the wl * al term, 2^-22 relative, is dropped), the sums are fp32.
+// (the wl * al term, 2^-22 relative, is dropped), the sums are fp32.  Held to a relative bound against float64 by
+// tests/test_gpu_pair_stage_f16x3_bound.py: (20 + C / 32) 2^-24 S with S = |bh| + sum_c |w| a, plus the floor of fp16's
+// subnormal spacing on the lo pieces (a lo piece below 2^-14 rounds to 2^-25 absolute: 2^-36 per activation and 2^-36
+// of the head's scale per weight; fp16 subnormals themselves are kept by every instruction on the path); the
+// derivation is tests/pairf16_reference.py.
 //
 // Range: fp16 holds ah up to 65504.  Wave w keeps the largest |U| of its subject row and the largest |V| of object
 // row w over the frames whose output is written (NaN-propagating maximum, so NaN and both infinities count).  After the
-// k-loop the workgroup votes: if any such value of a real tracklet is not <= 2^14 (so that relu(u + v) <= 2^15), or the
-// pack kernels flagged the weights (non-finite, or all below 2^-100 in a head), the MFMA sums of the tile are discarded
+// k-loop the workgroup votes: if any such value of a real tracklet is not <= 2^14 -- the rule is per half, |u| <= 2^14
+// and |v| <= 2^14, which gives relu(u + v) <= 2^15; a large u that v cancels is out of range all the same -- or the
+// pack kernels flagged the weights (non-finite, all below 2^-100 in a head, or 2^100 and above), the MFMA sums of the tile are discarded
 // and the tile is recomputed by exact_tile(): one fmaf chain in channel order per (pair, head, frame), the sum
 // heads_pairgrid4_kernel forms.  Rare by construction, untuned.
 //

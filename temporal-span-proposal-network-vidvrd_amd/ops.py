@@ -599,7 +599,7 @@ def heads_pairgrid_f16x3(y, B, N, head_w, head_b, T=None, split_buf=None, out=No
     if NT != B * N or head_w.shape[1] != C:
         raise ValueError("heads_pairgrid_f16x3: shape mismatch")
     if split_buf is None:
-        split_buf = torch.empty(max(heads_pairgrid_f16x3_split_bytes(C, H), 16), dtype=torch.uint8, device=y.device)
+        split_buf = _ws(heads_pairgrid_f16x3_split_bytes(C, H), y.device)
     if out is None:
         out = torch.empty((B * N * max(N - 1, 0), H, T), dtype=torch.float32, device=y.device)
     _abi.check(_abi.lib().tspn_heads_pairgrid_f16x3(_p(y), ldt, B, N, C, T, _p(head_w), _p(head_b), H, _p(split_buf),

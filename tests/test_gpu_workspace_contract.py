@@ -17,7 +17,9 @@ the same entry on other inputs and other weights of the same shape left there.  
     workspace change.  The memory behind the short view is the full view: an entry that fails to refuse runs on valid
     memory and trips a guard band.
 One test scores videos of different shapes one after the other through a BaseModel whose persistent workspace starts as
-0xFF -- the production pattern: every piece of a layout holds what another layout left there."""
+0xFF -- the production pattern: every piece of a layout holds what another layout left there.  The split buffer of
+tspn_heads_pairgrid_f16x3 is no `void* workspace` but promises the same (workspace_contracts.OTHER_SCRATCH): it is held
+the same way, and one buffer is carried from a call to the next with other weights, H and C."""
 
 import numpy as np
 import pytest
@@ -25,6 +27,7 @@ import torch
 
 import cases
 import oracle
+import pairf16_reference as pfref
 import pairlist_reference as plref
 import sentinel_buffers as sb
 import span_bf16_reference as sbref
@@ -784,6 +787,125 @@ def test_model_workspace_reused_across_videos(tspn, device, path):
         assert wsc.same_bits(logits, want[name][1]), f"call {k} (video {name}): the logits depend on what the workspace held"
     if path in ("wino63", "f16x3"):
         assert not model.conv_fallback
+
+
+# ------------------------------------------------------------------------------------------------ the split buffer
+def case_heads_pairgrid_f16x3(tspn, device, B, N, C, T, H):
+    """tspn_heads_pairgrid_f16x3's `split_buf` (workspace_contracts.OTHER_SCRATCH: not a `void* workspace`, the same
+    contract).  tests/test_gpu_pair_stage_f16x3_bound.py's `unit` distribution, reference and relative bound
+    (tests/pairf16_reference.py).  The stale run's weights hold an Inf: it leaves a raised flag word behind."""
+    ldt = (T + 3) // 4 * 4
+    a = pfref.make_case(tspn.hashrng, "unit", B, N, C, T, H, seed=75)
+    b = pfref.make_case(tspn.hashrng, "unit", B, N, C, T, H, seed=76)
+    b[1][H // 2, C - 1] = np.inf
+
+    def run(inp, helds):
+        y, w, bias = inp
+        yp = torch.full((B * N, 2 * C, ldt), float("nan"))
+        yp[:, :, :T] = t(y)
+        ho = sb.held((B * N * (N - 1), H, T), device)
+        helds.append((*ho, None))
+        return (tspn.ops.heads_pairgrid_f16x3(yp.to(device), B, N, t(w).to(device), t(bias).to(device), T=T, out=ho[1]),)
+
+    prev = tspn.ops.heads_pairgrid_f16x3_set_force_exact(1)
+    try:
+        chain = run(a, [])[0].cpu()                                   # outside the guarded runs
+    finally:
+        tspn.ops.heads_pairgrid_f16x3_set_force_exact(prev)
+
+    def check(outs):
+        got = outs[0].cpu()
+        act = pfref.activations(a[0], B, N)
+        err = np.abs(got.numpy().astype(np.float64) - pfref.ref64(act, a[1], a[2]))
+        assert bool((err <= pfref.bound(act, a[1], a[2])).all()), "heads_pairgrid_f16x3 misses its relative bound"
+        assert not wsc.same_bits(got, chain), "the MFMA path did not run"
+    return run, a, b, check
+
+
+@pytest.mark.parametrize("B,N,C,T,H", [(2, 9, 64, 30, 12), (1, 17, 96, 36, 5), (1, 3, 32, 4, 16)])
+def test_heads_pairgrid_f16x3_split_buf(tspn, device, B, N, C, T, H):
+    """One, two and three k-steps; H = 5 and 16: rows H .. 15 of the weight fragments are the pack kernel's to zero."""
+    need = tspn.ops.heads_pairgrid_f16x3_split_bytes(C, H)
+    assert need == 256 + C // 32 * 2048
+    hold(tspn, f"heads_pairgrid_f16x3 {(B, N, C, T, H)}", *case_heads_pairgrid_f16x3(tspn, device, B, N, C, T, H))
+
+
+def test_heads_pairgrid_f16x3_refuses_a_short_null_or_misaligned_split_buf(tspn, device):
+    """need - 1 bytes: TSPN_EWORKSPACE; no buffer: TSPN_EINVAL; a buffer 8 bytes off a 16-byte boundary: TSPN_EINVAL.
+    Each before any device work: the sentinel-filled output and the 0xFF buffer keep every byte."""
+    E = tspn._abi
+    B, N, C, T, H = 2, 9, 64, 30, 12
+    run, a, _, _ = case_heads_pairgrid_f16x3(tspn, device, B, N, C, T, H)
+    refused_untouched(tspn, "tspn_heads_pairgrid_f16x3", run, a)
+    need = tspn.ops.heads_pairgrid_f16x3_split_bytes(C, H)
+    buf, view = wsc.guarded_ws(need + 16, device, "ones")
+    y, w, bias = a
+    yp = torch.zeros((B * N, 2 * C, 32))
+    yp[:, :, :T] = t(y)
+    hbuf, out = sb.held((B * N * (N - 1), H, T), device)
+    with pytest.raises(E.TspnError) as e:
+        tspn.ops.heads_pairgrid_f16x3(yp.to(device), B, N, t(w).to(device), t(bias).to(device), T=T, split_buf=view[8:8 + need],
+                                      out=out)
+    assert e.value.code == E.TSPN_EINVAL, e.value
+    torch.cuda.synchronize(device)
+    sb.assert_untouched(hbuf, "misaligned split_buf")
+    wsc.assert_all_ones(view, "misaligned split_buf")
+    wsc.assert_guards_intact(buf, "misaligned split_buf")
+
+
+@pytest.mark.parametrize("first,second", [("inf_weight", "clean"), ("H=12", "H=5"), ("C=96", "C=32")])
+def test_heads_pairgrid_f16x3_split_buf_carries_no_state(tspn, device, first, second):
+    """One caller-held buffer (0xFF at first) serves two calls: flagged weights and then clean ones (the flag word must be
+    rewritten), H = 12 and then H = 5 (rows 5 .. 15 of the fragments must be zeroed again), C = 96 and then C = 32 (the
+    k-steps past the first hold the other call's fragments).  The second call equals, bit for bit, the same call on a
+    fresh zeroed buffer, and it ran on MFMAs."""
+    B, N, T = 2, 9, 30
+    shape = {"inf_weight": (64, 12), "clean": (64, 12), "H=12": (64, 12), "H=5": (64, 5), "C=96": (96, 12), "C=32": (32, 12)}
+
+    def operands(name, seed):
+        C, H = shape[name]
+        y, w, b = pfref.make_case(tspn.hashrng, "unit", B, N, C, T, H, seed=seed)
+        if name == "inf_weight":
+            w[3, 17] = np.inf
+        return y, w, b
+
+    def call(inp, view):
+        y, w, b = inp
+        yp = torch.full((B * N, y.shape[1], 32), float("nan"))
+        yp[:, :, :T] = t(y)
+        hbuf, out = sb.held((B * N * (N - 1), w.shape[0], T), device)
+        tspn.ops.heads_pairgrid_f16x3(yp.to(device), B, N, t(w).to(device), t(b).to(device), T=T, split_buf=view, out=out)
+        sb.assert_written_inside_only(hbuf, out, f"{first} -> {second}")
+        return out.clone()
+
+    need = max(tspn.ops.heads_pairgrid_f16x3_split_bytes(*shape[n]) for n in (first, second))
+    buf, view = wsc.guarded_ws(need, device, "ones")
+    one, two = operands(first, 77), operands(second, 78)
+    call(one, view)
+    got = call(two, view)
+    wsc.assert_guards_intact(buf, f"{first} -> {second}")
+    # what the second call left: no flag, a zero header tail, and zero rows H .. 15 in every fragment (the MFMA computes
+    # those rows too; no output shows them, so the buffer is the only place to see that the pack kernel wrote them)
+    C_, H_ = shape[second]
+    raw = view[:256 + C_ // 32 * 2048].cpu()
+    hdr = raw[:256].view(torch.int32)
+    assert int(hdr[0]) == 0 and bool((hdr[17:] == 0).all()), "the flag word or the header's tail was not rewritten"
+    frag = raw[256:].view(C_ // 32, 2, 64, 16)           # [k-step][hi | lo][lane][16 bytes], head row = lane & 15
+    assert bool((frag[:, :, torch.arange(64) % 16 >= H_] == 0).all()), "rows H .. 15 of the weight fragments are not zero"
+    assert bool((frag[:, 0, torch.arange(64) % 16 < H_] != 0).any())
+    zbuf, zview = wsc.guarded_ws(tspn.ops.heads_pairgrid_f16x3_split_bytes(*shape[second]), device, "zero")
+    want = call(two, zview)
+    wsc.assert_guards_intact(zbuf, f"{second} on a zeroed buffer")
+    assert wsc.same_bits(got, want), f"{second} after {first}: the output depends on what the split buffer held"
+    prev = tspn.ops.heads_pairgrid_f16x3_set_force_exact(1)
+    try:
+        chain = call(two, zview)
+    finally:
+        tspn.ops.heads_pairgrid_f16x3_set_force_exact(prev)
+    assert not wsc.same_bits(got, chain), f"{second} after {first}: the MFMA path did not run"
+    act = pfref.activations(two[0], B, N)
+    err = np.abs(got.cpu().numpy().astype(np.float64) - pfref.ref64(act, two[1], two[2]))
+    assert bool((err <= pfref.bound(act, two[1], two[2])).all())
 
 
 # ------------------------------------------------------------------------------------------------ caller-zeroed scratch

@@ -76,6 +76,19 @@ def test_caller_zeroed_scratch_is_what_the_header_says():
     assert "zeroed\n *   by the caller" in text and "one zeroed byte per" in text
 
 
+def test_other_scratch_is_what_the_header_says(tspn):
+    fns = header_functions()
+    lib = tspn._abi.lib()
+    for entry, param, helper, tests in wc.OTHER_SCRATCH:
+        assert re.search(r"\bvoid\s*\*\s*%s\b" % param, fns[entry]) and helper in fns and tests, entry
+        assert not re.search(r"\bvoid\s*\*\s*workspace\b", fns[entry]) and not helper.endswith("_workspace_bytes"), entry
+    assert [c[0] for c in wc.OTHER_SCRATCH] == ["tspn_heads_pairgrid_f16x3"]
+    split_bytes = lib.tspn_heads_pairgrid_f16x3_split_bytes
+    assert split_bytes(64, 12) == 256 + 2 * 2048 and split_bytes(32, 1) == split_bytes(32, 16) == 256 + 2048
+    assert split_bytes(48, 12) == 0 and split_bytes(64, 17) == 0          # a C and an H the entry refuses
+    assert "every byte of\n * which the call writes before it reads it" in open(HEADER).read()
+
+
 def test_every_named_test_exists():
     defined = {}
     for path in sorted(glob.glob(os.path.join(ROOT, "tests", "test_*.py"))):
@@ -83,7 +96,8 @@ def test_every_named_test_exists():
         defined[f"tests/{os.path.basename(path)}"] = {
             n.name for n in tree.body if isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef)) and n.name.startswith("test")}
     missing = []
-    for entry, nodes in [(r["entry"], r["tests"]) for r in wc.ROWS] + [(c[0], c[3]) for c in wc.CALLER_ZEROED]:
+    for entry, nodes in ([(r["entry"], r["tests"]) for r in wc.ROWS] + [(c[0], c[3]) for c in wc.CALLER_ZEROED] +
+                         [(c[0], c[3]) for c in wc.OTHER_SCRATCH]):
         for node in nodes:
             path, _, name = node.partition("::")
             if name.split("[")[0] not in defined.get(path, ()):

@@ -13,7 +13,8 @@ One row per entry.  Fields:
   tests    pytest node ids that hold the entry to the contract
 
 CALLER_ZEROED lists the two scratch arguments that are documented as zeroed BY THE CALLER; they take no part in the
-"any contents" tests and are checked for writes outside their bytes only.
+"any contents" tests and are checked for writes outside their bytes only.  OTHER_SCRATCH lists scratch that keeps the
+workspace contract under another parameter name and size helper (the split buffer of the split-fp16 pair stage).
 
 tests/test_workspace_contract_table.py keeps the table equal to the header and pins, without a device, that helper and
 entry agree; tests/test_gpu_workspace_contract.py is the GPU side."""
@@ -53,7 +54,8 @@ ROWS = [
     _row("tspn_forward_fused_f32", "tspn_forward_fused_workspace_bytes", "ops.forward_fused",
          "xt (transposed feats, D % 16 != 0 only), y [NT][2C][ldy] (ldy = ceil4(T) on the blocked pair stage), bias2 [2C], "
          "fbar [NT][D], pooled (unused), the predicate head's slabs + rs / ro [NT][K], V of the F(6,3) forms, hwp [C][12], "
-         "hot (the accuracy guard's scratch)",
+         "psplit (the split buffer of tspn_heads_pairgrid_f16x3: flag word, inverse scales, split head weights; only "
+         "behind the split-fp16 conv with 3A = 12), hot (the accuracy guard's scratch)",
          "library: hipMemsetAsync of bias2[C, 2C) (tspn_fused.hip; the object half carries no bias) and, with conv_check "
          "> 0 on an F(6,3) form, of the TSPN_CONV_CHECK_SCRATCH_BYTES of `hot`.  The pad frames [T, ldy) of y reach no "
          "output, whatever they hold",
@@ -105,4 +107,12 @@ CALLER_ZEROED = [
      [WC + "test_caller_zeroed_scratch_is_not_overrun"]),
     ("tspn_conv3_spot_check_f32", "scratch", "TSPN_CONV_CHECK_SCRATCH_BYTES, all zero before the conv it belongs to",
      [WC + "test_caller_zeroed_scratch_is_not_overrun"]),
+]
+
+# scratch under the same contract as a workspace ("every byte of which the call writes before it reads it", a short one
+# refused) that is not a `void* workspace` with a `*_workspace_bytes` helper: (entry, parameter, size helper, tests)
+OTHER_SCRATCH = [
+    ("tspn_heads_pairgrid_f16x3", "split_buf", "tspn_heads_pairgrid_f16x3_split_bytes",
+     [WC + "test_heads_pairgrid_f16x3_split_buf", WC + "test_heads_pairgrid_f16x3_refuses_a_short_null_or_misaligned_split_buf",
+      WC + "test_heads_pairgrid_f16x3_split_buf_carries_no_state"]),
 ]
