@@ -9,6 +9,7 @@ PL = "tests/test_gpu_pairlist_bf16.py::"
 SCAN = "tests/test_gpu_pairplan_scan.py::"
 TILES = "tests/test_gpu_pairlist_tiles.py::"
 HH = "tests/test_gpu_bf16_heads_h.py::"
+BND = "tests/test_gpu_bf16_bound.py::"
 
 
 def _row(kernel, inst, entry, when, tests, align="no alignment requirement"):
@@ -29,7 +30,9 @@ VARIANTS = [
          [PL + "test_list_rows_equal_the_grid_rows", PL + "test_arbitrary_tables_vs_fp64",
           TILES + "test_unequal_axes_small_form", TILES + "test_one_local_table_on_both_sides_of_the_form_switch",
           TILES + "test_a_nonfinite_activation_in_the_v_half_stays_in_its_object_rows_and_frame",
-          HH + "test_heads_pairlist_bf16_vs_fp64_and_the_grid_rows_for_every_h"],
+          HH + "test_heads_pairlist_bf16_vs_fp64_and_the_grid_rows_for_every_h",
+          BND + "test_heads_pairlist_bf16_rows_off_the_benign_distribution",
+          BND + "test_fused_bf16_passes_equal_their_stages_at_cfg3_depth"],
          align="y and head_packed 16-byte aligned, ldm % 4 == 0, C % 32 == 0"),
     _row("heads_pairlist_bf16_kernel", "8, 16, 2", "tspn_heads_pairlist_bf16", "N > 12 && P > 0",
          [PL + "test_list_rows_equal_the_grid_rows", PL + "test_arbitrary_tables_vs_fp64",
