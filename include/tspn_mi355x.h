@@ -682,10 +682,17 @@ int tspn_temporal_encoder_heads_bf16(const uint16_t* x_tc, int64_t P, int64_t C,
  * channels-last (NHWC) fp32 tensors; `temporal-span-proposal-network-vidvrd_amd/roi_head.py`
  * assembles them and hands [N,T,2048] straight to the pair builder.
  *
+ * Non-finite values, every entry of this section and of the three f4 sections below: on inputs that are
+ * finite except for NaN / +-Inf values (either sign, any payload) in x, a feature map or a residual, every output is NaN,
+ * +Inf or -Inf exactly where a float64 evaluation's is.  relu is torch's (relu(NaN) = NaN, relu(-Inf) = 0), a max pool
+ * with a NaN in its window gives NaN, a padding tap is not read (never 0 * Inf), and a bad value reaches exactly the
+ * outputs whose receptive field holds it: every other output has the bits of a launch without it.  Box coordinates of
+ * RoIAlign are not part of this (see there).  tests/test_gpu_nonfinite_frontend.py.
+ *
  * tspn_pack_conv2d_f32: Conv2d weight [Cout][Cin][KH][KW] -> [KH*KW][Cin][Cout] (KH*KW <= 64).
  * tspn_conv2d_nhwc_f32: out[NB,OH,OW,Cout] = act( conv(x[NB,H,W,Cin]) + bias[Cout] + residual[NB,OH,OW,Cout] ),
  *   zero padding `pad`, `stride`, OH = (H + 2 pad - KH) / stride + 1; bias / residual may be NULL;
- *   relu != 0 applies max(.,0).  BatchNorm is folded into (packed, bias) by the caller.  Implicit GEMM
+ *   relu != 0 applies torch's relu (a NaN stays a NaN).  BatchNorm is folded into (packed, bias) by the caller.  Implicit GEMM
  *   on fp32 MFMA.  Needs Cin % 16 == 0, Cout % 4 == 0, 16-byte aligned tensors (else TSPN_EUNSUPPORTED).
  *   A kernel larger than the padded map (H + 2 pad < KH or W + 2 pad < KW) has no output: TSPN_EINVAL, whatever the
  *   stride -- in this entry and in tspn_conv2d_nhwc_frag_f32, tspn_conv2d_nhwc_cin4_f32 and tspn_conv2d_nhwc_bf16. */
@@ -737,7 +744,8 @@ int tspn_conv2d_nhwc_bf16(const uint16_t* x, int64_t NB, int64_t H, int64_t W, i
  *   The map index (rois[r][0], truncated towards zero) is CLAMPED to [0, NF): an index below 0 reads map 0, an index
  *   of NF or more reads map NF - 1 -- never memory outside feat (tests/test_gpu_frontend_edges.py pins it).  The
  *   adaptive grid makes a workgroup's trip count grow with the box (ceil(roi size / P) samples per bin and axis): box
- *   coordinates are the caller's to keep finite and of the image's order of magnitude. */
+ *   coordinates are the caller's to keep finite and of the image's order of magnitude.  Non-finite FEATURE values follow
+ *   the contract above: they reach the bins one of whose samples reads them (with whatever bilinear weight, zero included). */
 int tspn_roi_align_nhwc_f32(const float* feat, int64_t NF, int64_t H, int64_t W, int64_t C,
                             const float* rois, int64_t R, int64_t P, float spatial_scale,
                             int sampling_ratio, int aligned, int bin_stride, float* out, void* stream);
@@ -751,7 +759,8 @@ int tspn_roi_align_nhwc_f32_bf16out(const float* feat, int64_t NF, int64_t H, in
                                     int sampling_ratio, int aligned, int bin_stride, uint16_t* out, void* stream);
 
 /* max_pool2d(k, stride, pad) on a channels-last fp32 map x[NB,H,W,C] -> out[NB,OH,OW,C], fp32 (out_bf16 == 0)
- * or bf16 (rounded once); padding positions do not take part.  detectron2 BasicStem uses 3 / 2 / 1.
+ * or bf16 (rounded once); padding positions do not take part, a NaN in the window gives NaN (torch), a window of only
+ * -Inf gives -Inf.  detectron2 BasicStem uses 3 / 2 / 1.
  * Needs C % 4 == 0.  A window larger than the padded map (H + 2 pad < k or W + 2 pad < k) has no output: TSPN_EINVAL. */
 int tspn_max_pool_nhwc_f32(const float* x, int64_t NB, int64_t H, int64_t W, int64_t C, int64_t k,
                            int64_t stride, int64_t pad, void* out, int out_bf16, void* stream);
@@ -762,7 +771,9 @@ int tspn_max_pool_nhwc_f32(const float* x, int64_t NB, int64_t H, int64_t W, int
  * h1 bf16 [NB,H,W,CM] (conv1's output), residual / out bf16 [NB,H,W,4 CM] (the block input or its projection
  * shortcut); CM = 64, 128 or 256.  frag2 = tspn_pack_conv2d_frag_bf16(W2 [CM,CM,3,3]), frag3 =
  * tspn_pack_conv2d_frag_bf16(W3 [4 CM,CM,1,1]); biases fp32.  Same rounding points and contraction order as
- * tspn_conv2d_nhwc_bf16 applied twice (h2 rounded to bf16 once): bit-identical results, one launch, h2 never in HBM. */
+ * tspn_conv2d_nhwc_bf16 applied twice (h2 rounded to bf16 once): bit-identical results, one launch, h2 never in HBM.
+ * Both ReLUs keep a NaN; a non-finite h1 value reaches its 3 x 3 neighbourhood inside its own image, a non-finite
+ * residual element its own output element (this entry and its role-split, persistent and next-conv1 forms alike). */
 int tspn_bottleneck_tail_bf16(const uint16_t* h1, int64_t NB, int64_t H, int64_t W, int64_t CM,
                               const uint16_t* frag2, const float* bias2, const uint16_t* frag3,
                               const float* bias3, const uint16_t* residual, uint16_t* out, void* stream);
@@ -782,7 +793,8 @@ int tspn_bottleneck_tail_io_bf16(const uint16_t* h1, int64_t NB, int64_t H, int6
  * x, out bf16 channels-last [NB, H, W, 4 CM]; frag1 / frag2 / frag3 = tspn_pack_conv2d_frag_bf16 of the folded
  * 1x1 (4 CM -> CM), 3x3 (CM -> CM) and 1x1 (CM -> 4 CM) weights; fp32 biases.  CM = 64 or 128 (the memory-bound stages
  * res2 / res3): the 4 CM-channel map is read once and h1 / h2 stay on the CU.  Bit-identical to tspn_conv2d_nhwc_bf16
- * (conv1) followed by tspn_bottleneck_tail_bf16.  out must not alias x; one image's map below 2 GB. */
+ * (conv1) followed by tspn_bottleneck_tail_bf16, non-finite values included (the recomputed halo of a tile does not
+ * widen a bad pixel's 3 x 3 reach).  out must not alias x; one image's map below 2 GB. */
 int tspn_bottleneck_block_bf16(const uint16_t* x, int64_t NB, int64_t H, int64_t W, int64_t CM,
                                const uint16_t* frag1, const float* bias1, const uint16_t* frag2, const float* bias2,
                                const uint16_t* frag3, const float* bias3, uint16_t* out, void* stream);
@@ -833,11 +845,14 @@ int tspn_bottleneck_tail_pipe_bf16(const uint16_t* h1, int64_t NB, int64_t H, in
  * caller into w / bias) + ReLU with bf16 operands: image and weights rounded to bf16, exact products, fp32
  * accumulation, relu(acc + bias) rounded to bf16 once.  x fp32 [NB,H,W,3] -> out bf16 [NB,OH,OW,Cout],
  * OH = (H - 1) / 2 + 1.  Cout = 32 or 64.  `frag` = tspn_pack_stem_bf16(w fp32 [Cout,3,7,7]) (Cout * 256 bf16);
- * `workspace` (tspn_stem_bf16_workspace_bytes) holds the 2x2 space-to-depth image the conv kernel streams.
- * tspn_max_pool_nhwc_bf16: max_pool2d(k, stride, pad) on a bf16 channels-last map (C % 8 == 0).
+ * `workspace` (tspn_stem_bf16_workspace_bytes) holds the 2x2 space-to-depth image the conv kernel streams.  The ReLU keeps
+ * a NaN, and a NaN / Inf pixel reaches exactly the outputs whose 7 x 7 window holds it (the eighth tap row and column of
+ * the space-to-depth form are cleared in the operand, not multiplied by their zero weights).
+ * tspn_max_pool_nhwc_bf16: max_pool2d(k, stride, pad) on a bf16 channels-last map (C % 8 == 0); NaN in the window -> NaN.
  * tspn_stem_pool_bf16: BasicStem.forward whole (conv + FrozenBN + ReLU, then max_pool2d(3, 2, 1)) in one conv
  * launch: out bf16 [NB,PH,PW,Cout], PH = (OH - 1) / 2 + 1; bit-identical to tspn_max_pool_nhwc_bf16(3, 2, 1) of
- * tspn_stem_conv_bf16, whose map it never writes.  Same operands and workspace as tspn_stem_conv_bf16. */
+ * tspn_stem_conv_bf16, whose map it never writes (with NaN == NaN: its maxima propagate NaN at the accumulator level
+ * and in the column pool).  Same operands and workspace as tspn_stem_conv_bf16. */
 size_t tspn_stem_bf16_workspace_bytes(int64_t NB, int64_t H, int64_t W);
 int tspn_pack_stem_bf16(const float* w, int64_t Cout, uint16_t* frag, void* stream);
 int tspn_stem_conv_bf16(const float* x, int64_t NB, int64_t H, int64_t W, const uint16_t* frag, int64_t Cout,

@@ -174,10 +174,10 @@ __global__ __launch_bounds__(THREADS, 2) void bottleneck_block_bf16_kernel(
 #pragma unroll
       for (int pj = 0; pj < NPB1; ++pj) {
         bf16x4 v;
-        v[0] = (__bf16)fmaxf(acc[pj][4 * q] + bv.x, 0.f);
-        v[1] = (__bf16)fmaxf(acc[pj][4 * q + 1] + bv.y, 0.f);
-        v[2] = (__bf16)fmaxf(acc[pj][4 * q + 2] + bv.z, 0.f);
-        v[3] = (__bf16)fmaxf(acc[pj][4 * q + 3] + bv.w, 0.f);
+        v[0] = (__bf16)tspn::relu_f32(acc[pj][4 * q] + bv.x);
+        v[1] = (__bf16)tspn::relu_f32(acc[pj][4 * q + 1] + bv.y);
+        v[2] = (__bf16)tspn::relu_f32(acc[pj][4 * q + 2] + bv.z);
+        v[3] = (__bf16)tspn::relu_f32(acc[pj][4 * q + 3] + bv.w);
         if (!((inmask >> pj) & 1u)) v = bf16x4{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
         *reinterpret_cast<bf16x4*>(Bs + ((ch >> 3) * SL1 + pj * 32 + li) * 16 + 8 * kh) = v;
       }
@@ -246,10 +246,10 @@ __global__ __launch_bounds__(THREADS, 2) void bottleneck_block_bf16_kernel(
 #pragma unroll
         for (int pj = 0; pj < PB; ++pj) {
           bf16x4 v;
-          v[0] = (__bf16)fmaxf(acc[mi][pj][4 * q] + bv.x, 0.f);
-          v[1] = (__bf16)fmaxf(acc[mi][pj][4 * q + 1] + bv.y, 0.f);
-          v[2] = (__bf16)fmaxf(acc[mi][pj][4 * q + 2] + bv.z, 0.f);
-          v[3] = (__bf16)fmaxf(acc[mi][pj][4 * q + 3] + bv.w, 0.f);
+          v[0] = (__bf16)tspn::relu_f32(acc[mi][pj][4 * q] + bv.x);
+          v[1] = (__bf16)tspn::relu_f32(acc[mi][pj][4 * q + 1] + bv.y);
+          v[2] = (__bf16)tspn::relu_f32(acc[mi][pj][4 * q + 2] + bv.z);
+          v[3] = (__bf16)tspn::relu_f32(acc[mi][pj][4 * q + 3] + bv.w);
           if (!inimg[pj]) v = bf16x4{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
           *reinterpret_cast<bf16x4*>(Bs + ((ch >> 3) * SL1 + (PB * wn + pj) * 32 + li) * 16 + 8 * kh) = v;
         }
@@ -301,10 +301,10 @@ __global__ __launch_bounds__(THREADS, 2) void bottleneck_block_bf16_kernel(
 #pragma unroll
       for (int pj = 0; pj < PB; ++pj) {
         bf16x4 v;
-        v[0] = (__bf16)fmaxf(acc[pj][4 * q] + bv.x, 0.f);
-        v[1] = (__bf16)fmaxf(acc[pj][4 * q + 1] + bv.y, 0.f);
-        v[2] = (__bf16)fmaxf(acc[pj][4 * q + 2] + bv.z, 0.f);
-        v[3] = (__bf16)fmaxf(acc[pj][4 * q + 3] + bv.w, 0.f);
+        v[0] = (__bf16)tspn::relu_f32(acc[pj][4 * q] + bv.x);
+        v[1] = (__bf16)tspn::relu_f32(acc[pj][4 * q + 1] + bv.y);
+        v[2] = (__bf16)tspn::relu_f32(acc[pj][4 * q + 2] + bv.z);
+        v[3] = (__bf16)tspn::relu_f32(acc[pj][4 * q + 3] + bv.w);
         *reinterpret_cast<bf16x4*>(Bs + ((ch >> 3) * SL2 + (PB * wn + pj) * 32 + li) * 16 + 8 * kh) = v;
       }
     }
@@ -477,7 +477,7 @@ __global__ __launch_bounds__(THREADS, 2) void bottleneck_block_bf16_kernel(
               bf16x8 o;
 #pragma unroll
               for (int j = 0; j < 8; ++j)
-                o[j] = (__bf16)fmaxf((acc[ms][pj][8 * h + j] + bv[8 * h + j]) + (float)res[PROJ ? 0 : (g & 1)][ms][pj][h][j], 0.f);
+                o[j] = (__bf16)tspn::relu_f32((acc[ms][pj][8 * h + j] + bv[8 * h + j]) + (float)res[PROJ ? 0 : (g & 1)][ms][pj][h][j]);
               o2[h] = __builtin_bit_cast(u32x4, o);
             }
             __builtin_amdgcn_raw_buffer_store_b128(o2[0], rs_o, (int)(pofs == OOB ? OOB : pofs), (mbA + ms) * 64, 0);

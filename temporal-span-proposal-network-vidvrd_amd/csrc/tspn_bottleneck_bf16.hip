@@ -385,10 +385,10 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni) {
         bf16x4 v;
-        v[0] = (__bf16)fmaxf(acc[mi][ni][4 * q] + bv.x, 0.f);
-        v[1] = (__bf16)fmaxf(acc[mi][ni][4 * q + 1] + bv.y, 0.f);
-        v[2] = (__bf16)fmaxf(acc[mi][ni][4 * q + 2] + bv.z, 0.f);
-        v[3] = (__bf16)fmaxf(acc[mi][ni][4 * q + 3] + bv.w, 0.f);
+        v[0] = (__bf16)tspn::relu_f32(acc[mi][ni][4 * q] + bv.x);
+        v[1] = (__bf16)tspn::relu_f32(acc[mi][ni][4 * q + 1] + bv.y);
+        v[2] = (__bf16)tspn::relu_f32(acc[mi][ni][4 * q + 2] + bv.z);
+        v[3] = (__bf16)tspn::relu_f32(acc[mi][ni][4 * q + 3] + bv.w);
         *reinterpret_cast<bf16x4*>(Bs + ((ch >> 3) * SLP + (wn * NI + ni) * 32 + li) * 16 + 8 * kh) = v;
       }
     }
@@ -546,7 +546,7 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
     const bf16x8 rv = rres[slot][h];
     bf16x8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) o[j] = (__bf16)fmaxf(v[j] + (float)rv[j], 0.f);
+    for (int j = 0; j < 8; ++j) o[j] = (__bf16)tspn::relu_f32(v[j] + (float)rv[j]);
     if constexpr (NEXT) {
       // the sub-pass's chunk image (buffer e & 1): channel group (channel - 256 pass) / 8, slot = pixel of its 64
       const int g8 = ((32 * (sub_rb(e) + ms)) & 255) / 8 + 2 * kh + h;
@@ -750,8 +750,8 @@ __global__ __launch_bounds__(THREADS, (NEXT ? 1 : (CM == 64 ? 3 : 2))) void bott
         bf16x8 o0, o1;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          o0[j] = (__bf16)fmaxf(acc1[mi][ni][j] + bv[j], 0.f);
-          o1[j] = (__bf16)fmaxf(acc1[mi][ni][8 + j] + bv[8 + j], 0.f);
+          o0[j] = (__bf16)tspn::relu_f32(acc1[mi][ni][j] + bv[j]);
+          o1[j] = (__bf16)tspn::relu_f32(acc1[mi][ni][8 + j] + bv[8 + j]);
         }
         if ((okmask >> ni) & 1u) {
           char* hp = reinterpret_cast<char*>(h1n + (n0 + ni * 32 + li) * CM + chb);

@@ -238,10 +238,10 @@ __device__ __forceinline__ void team_a(const __bf16* __restrict__ h1, const __bf
 #pragma unroll
         for (int ni = 0; ni < NI; ++ni) {
           bf16x4 v;
-          v[0] = (__bf16)fmaxf(acc[mi][ni][4 * q] + bv.x, 0.f);
-          v[1] = (__bf16)fmaxf(acc[mi][ni][4 * q + 1] + bv.y, 0.f);
-          v[2] = (__bf16)fmaxf(acc[mi][ni][4 * q + 2] + bv.z, 0.f);
-          v[3] = (__bf16)fmaxf(acc[mi][ni][4 * q + 3] + bv.w, 0.f);
+          v[0] = (__bf16)tspn::relu_f32(acc[mi][ni][4 * q] + bv.x);
+          v[1] = (__bf16)tspn::relu_f32(acc[mi][ni][4 * q + 1] + bv.y);
+          v[2] = (__bf16)tspn::relu_f32(acc[mi][ni][4 * q + 2] + bv.z);
+          v[3] = (__bf16)tspn::relu_f32(acc[mi][ni][4 * q + 3] + bv.w);
           *reinterpret_cast<bf16x4*>(Bs + H2_OFF + ((ch >> 3) * SLP + ni * 32 + li) * 16 + 8 * kh) = v;
         }
       }
@@ -344,7 +344,7 @@ __device__ __forceinline__ void team_b(const __bf16* __restrict__ Wf3, const flo
       const bf16x8 rv = rres[slot][h];
       bf16x8 o;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) o[j] = (__bf16)fmaxf(v[j] + (float)rv[j], 0.f);
+      for (int j = 0; j < 8; ++j) o[j] = (__bf16)tspn::relu_f32(v[j] + (float)rv[j]);
       if constexpr (h == 0) {
         ohold = o;
       } else {

@@ -52,6 +52,8 @@ __host__ __device__ inline int64_t next_pow2(int64_t n) {
 // ---- non-finite contract
 // ReLU as torch's F.relu: NaN in -> NaN out (fmaxf(v, 0) would return 0).  One v_maximum3_f32 on gfx950.
 __device__ __forceinline__ float relu_f32(float v) { return __builtin_elementwise_maximum(v, 0.f); }
+// The maximum of a pool window as torch's F.max_pool2d: a NaN operand -> NaN (fmaxf would return the other operand).
+__device__ __forceinline__ float maximum_f32(float a, float b) { return __builtin_elementwise_maximum(a, b); }
 
 // torch's descending sort order as an unsigned key: larger value -> larger key, every NaN (any sign, any payload)
 // -> 0xffffffff above +Inf (0xff800000), -0 == +0.  Real values never map to 0, which is left for padding.

@@ -204,7 +204,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv2d_nhwc_kernel(
           v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
         }
         if (relu) {
-          v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+          v.x = tspn::relu_f32(v.x); v.y = tspn::relu_f32(v.y); v.z = tspn::relu_f32(v.z); v.w = tspn::relu_f32(v.w);
         }
         *reinterpret_cast<float4*>(orow + m) = v;
       }
@@ -400,7 +400,7 @@ __global__ __launch_bounds__(THREADS, 2) void conv2d_nhwc_frag_kernel(
         v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
       }
       if (relu) {
-        v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f);
+        v.x = tspn::relu_f32(v.x); v.y = tspn::relu_f32(v.y); v.z = tspn::relu_f32(v.z); v.w = tspn::relu_f32(v.w);
       }
       *reinterpret_cast<float4*>(orow + m) = v;
     }
@@ -512,7 +512,8 @@ __global__ __launch_bounds__(256) void max_pool_nhwc_kernel(const float* __restr
         const int iw = ow * stride - pad + b;
         if (iw < 0 || iw >= W) continue;
         const float4 v = *reinterpret_cast<const float4*>(x + ((nb * H + ih) * (int64_t)W + iw) * C + 4 * cg);
-        m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+        m.x = tspn::maximum_f32(m.x, v.x); m.y = tspn::maximum_f32(m.y, v.y);      // a NaN in the window stays (torch)
+        m.z = tspn::maximum_f32(m.z, v.z); m.w = tspn::maximum_f32(m.w, v.w);
       }
     }
     const int64_t oo = pix * C + 4 * cg;

@@ -420,7 +420,7 @@ __global__ __launch_bounds__(THREADS, (MI == 1 ? TSPN_ROI_BF16_MI1_WAVES : 2)) v
           }
           bf16x8 o;
 #pragma unroll
-          for (int k = 0; k < 8; ++k) o[k] = (__bf16)(relu ? fmaxf(v[k], 0.f) : v[k]);
+          for (int k = 0; k < 8; ++k) o[k] = (__bf16)(relu ? tspn::relu_f32(v[k]) : v[k]);
           *reinterpret_cast<bf16x8*>(out + n * Cout + mc) = o;
         }
       }

@@ -8,7 +8,8 @@
 // resnet_c4_bf16):
 //   1. stem_s2d_bf16_kernel: 2 x 2 space-to-depth of the zero-padded image, fp32 -> bf16:
 //        S[nb][r][c][(ra, rb, ch)] = x[nb][2 r + ra - 3][2 c + rb - 3][ch]   (12 values + 4 zeros = one 32-byte pixel)
-//      so the 7 x 7 / 2 conv becomes a VALID 4 x 4 / 1 conv with 16 channels: K = 16 taps x 16 = 256, no masks.
+//      so the 7 x 7 / 2 conv becomes a VALID 4 x 4 / 1 conv with 16 channels: K = 16 taps x 16 = 256, no tap masks (the
+//      eighth tap row and column, which the 7 x 7 kernel does not have, are cleared in the fragment: clear_eighth_taps).
 //   2. stem_conv_bf16_kernel: persistent workgroups, a tile = 128 consecutive output pixels of one row.  Its
 //      whole operand -- 4 rows x 131 s2d pixels = 16.8 KB, CONTIGUOUS per row -- is staged by LDS-DMA one tile ahead
 //      (double buffer); every (tap, channel half) fragment is a conflict-free 16-byte LDS read at a pixel offset.
@@ -17,6 +18,7 @@
 //      + bias, ReLU, transposed through LDS so that a lane stores 8 consecutive channels (16 bytes) of a pixel.
 //   3. max_pool_nhwc_bf16_kernel: the 3 x 3 / 2 max pool on the bf16 map (max commutes with the rounding, so
 //      "round, then pool" equals the oracle's "pool, then round").
+// Every ReLU and every maximum here propagates NaN as torch's do (tspn::relu_f32, tspn::maximum_f32).
 #include <algorithm>
 
 #include "tspn_common.h"
@@ -72,6 +74,21 @@ __global__ void pack_stem_bf16_kernel(const float* __restrict__ w, int Cout, __b
     const bool ok = c16 < 12 && a < KS && b < KS;
     frag[o] = (__bf16)(ok ? w[((row * 3 + ch) * KS + a) * KS + b] : 0.f);
   }
+}
+
+// The 4 x 4 form has 8 x 8 taps where the stem has 7 x 7: tap row a = 7 (a' = 3, ra = 1) and tap column b = 7 (b' = 3,
+// rb = 1) carry zero WEIGHTS, but the image pixels under them are real, and 0 * Inf = 0 * NaN = NaN would reach an output
+// whose 7 x 7 window does not hold the pixel (non-finite values).  Those pixels are cleared in the B
+// fragment instead: s2d channel k = (2 ra + rb) * 3 + ch, lane half kh holds k = 8 kh .. 8 kh + 7, so ra = 1 is
+// k = 6 .. 11 and rb = 1 is k = 3 .. 5 and 9 .. 11.  For finite pixels the products were zeros: the sums keep their bits.
+// (ks is a constant of the unrolled k-step loop: nine of the sixteen k-steps keep their fragment as it is)
+__device__ __forceinline__ bf16x8 clear_eighth_taps(bf16x8 b, int ks, int kh) {
+  const bool row = (ks >> 2) == 3, col = (ks & 3) == 3;
+  if (!row && !col) return b;
+  u32x4 m = {~0u, ~0u, ~0u, ~0u};
+  if (row) m &= kh ? u32x4{0u, 0u, ~0u, ~0u} : u32x4{~0u, ~0u, ~0u, 0u};
+  if (col) m &= kh ? u32x4{0x0000ffffu, 0u, ~0u, ~0u} : u32x4{~0u, 0x0000ffffu, 0u, ~0u};
+  return __builtin_bit_cast(bf16x8, __builtin_bit_cast(u32x4, b) & m);
 }
 
 template <int MB>
@@ -138,7 +155,8 @@ __global__ __launch_bounds__(256, 2) void stem_conv_bf16_kernel(const __bf16* __
     const char* Bb = stage + buf * STAGE_BYTES + (32 * wave + li) * 32 + 16 * kh;
 #pragma unroll
     for (int ks = 0; ks < 16; ++ks) {
-      const bf16x8 b = *reinterpret_cast<const bf16x8*>(Bb + ((ks >> 2) * SROW + (ks & 3)) * 32);
+      const bf16x8 braw = *reinterpret_cast<const bf16x8*>(Bb + ((ks >> 2) * SROW + (ks & 3)) * 32);
+      const bf16x8 b = clear_eighth_taps(braw, ks, kh);
 #pragma unroll
       for (int mi = 0; mi < MB; ++mi)
         acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[ks][mi]), b, acc[mi], 0, 0, 0);
@@ -169,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void stem_conv_bf16_kernel(const __bf16* __
         const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
         bf16x8 o;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (__bf16)fmaxf(v[k], 0.f);
+        for (int k = 0; k < 8; ++k) o[k] = (__bf16)tspn::relu_f32(v[k]);
         *reinterpret_cast<bf16x8*>(out + (rowi * OW + ow0 + px) * COUT + 8 * cg) = o;
       }
     }
@@ -187,9 +205,9 @@ __global__ __launch_bounds__(256, 2) void stem_conv_bf16_kernel(const __bf16* __
 //     at the start of a row;
 //   * a lane takes the maximum of columns 2 i - 1, 2 i, 2 i + 1 for 8 channels and stores 16 bytes: a pooled pixel
 //     leaves as one 128-byte line.
-// x + bias, ReLU and the rounding are monotonic, so "max first, then bias / ReLU / round" gives bit for bit
-// pool(round(relu(conv + bias))).  Every odd conv row is computed twice (1.5x the MFMAs of the stem, which are 2 % of
-// the backbone's); 69.3 KB of LDS, two workgroups per CU.
+// x + bias, ReLU and the rounding are monotonic (and keep a NaN, as the maxima do), so "max first, then bias / ReLU /
+// round" gives bit for bit pool(round(relu(conv + bias))), NaN for NaN.  Every odd conv row is computed twice (1.5x the
+// MFMAs of the stem, which are 2 % of the backbone's); 69.3 KB of LDS, two workgroups per CU.
 constexpr int PROWS = 6;
 constexpr int PSTAGE_BYTES = PROWS * SROW * 32;
 
@@ -267,7 +285,8 @@ __global__ __launch_bounds__(256, 2) void stem_pool_bf16_kernel(const __bf16* __
       const char* Bb = stage + buf * PSTAGE_BYTES + (rr * SROW + 32 * wave + li) * 32 + 16 * kh;
 #pragma unroll
       for (int ks = 0; ks < 16; ++ks) {
-        const bf16x8 b = *reinterpret_cast<const bf16x8*>(Bb + ((ks >> 2) * SROW + (ks & 3)) * 32);
+        const bf16x8 braw = *reinterpret_cast<const bf16x8*>(Bb + ((ks >> 2) * SROW + (ks & 3)) * 32);
+      const bf16x8 b = clear_eighth_taps(braw, ks, kh);
 #pragma unroll
         for (int mi = 0; mi < MB; ++mi)
           acc[mi] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[ks][mi]), b, acc[mi], 0, 0, 0);
@@ -280,7 +299,7 @@ __global__ __launch_bounds__(256, 2) void stem_pool_bf16_kernel(const __bf16* __
 #pragma unroll
         for (int mi = 0; mi < MB; ++mi)
 #pragma unroll
-          for (int e = 0; e < 16; ++e) vmax[mi][e] = fmaxf(vmax[mi][e], acc[mi][e]);
+          for (int e = 0; e < 16; ++e) vmax[mi][e] = tspn::maximum_f32(vmax[mi][e], acc[mi][e]);
       }
     }
 
@@ -294,10 +313,10 @@ __global__ __launch_bounds__(256, 2) void stem_pool_bf16_kernel(const __bf16* __
         const int ch = mi * 32 + 8 * q + 4 * kh;
         const float4 bv = *reinterpret_cast<const float4*>(bias + ch);
         bf16x4 v;
-        v[0] = (__bf16)(colok ? fmaxf(vmax[mi][4 * q] + bv.x, 0.f) : 0.f);
-        v[1] = (__bf16)(colok ? fmaxf(vmax[mi][4 * q + 1] + bv.y, 0.f) : 0.f);
-        v[2] = (__bf16)(colok ? fmaxf(vmax[mi][4 * q + 2] + bv.z, 0.f) : 0.f);
-        v[3] = (__bf16)(colok ? fmaxf(vmax[mi][4 * q + 3] + bv.w, 0.f) : 0.f);
+        v[0] = (__bf16)(colok ? tspn::relu_f32(vmax[mi][4 * q] + bv.x) : 0.f);
+        v[1] = (__bf16)(colok ? tspn::relu_f32(vmax[mi][4 * q + 1] + bv.y) : 0.f);
+        v[2] = (__bf16)(colok ? tspn::relu_f32(vmax[mi][4 * q + 2] + bv.z) : 0.f);
+        v[3] = (__bf16)(colok ? tspn::relu_f32(vmax[mi][4 * q + 3] + bv.w) : 0.f);
         *reinterpret_cast<bf16x4*>(sp + ch * 2) = v;
       }
     __syncthreads();
@@ -319,7 +338,8 @@ __global__ __launch_bounds__(256, 2) void stem_pool_bf16_kernel(const __bf16* __
       if (pw < PW) {
         bf16x8 o;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (__bf16)fmaxf(fmaxf((float)l[k], (float)m[k]), (float)r[k]);
+        for (int k = 0; k < 8; ++k)
+          o[k] = (__bf16)tspn::maximum_f32(tspn::maximum_f32((float)l[k], (float)m[k]), (float)r[k]);
         *reinterpret_cast<bf16x8*>(out + (row * PW + pw) * COUT + 8 * cg) = o;
       }
     }
@@ -352,7 +372,7 @@ __global__ __launch_bounds__(256) void max_pool_nhwc_bf16_kernel(const __bf16* _
         if (iw < 0 || iw >= W) continue;
         const bf16x8 v = *reinterpret_cast<const bf16x8*>(x + ((nb * H + ih) * (int64_t)W + iw) * C + 8 * cg);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) m[j] = fmaxf(m[j], (float)v[j]);
+        for (int j = 0; j < 8; ++j) m[j] = tspn::maximum_f32(m[j], (float)v[j]);
       }
     }
     bf16x8 ob;

@@ -194,7 +194,7 @@ __global__ __launch_bounds__(THREADS, 1) void tail_io_bf16_kernel(
         for (int t = 0; t < 8; ++t) {
           bf16x8 o;
 #pragma unroll
-          for (int j = 0; j < 8; ++j) o[j] = (__bf16)fmaxf((sv[t][j >> 2][j & 3] + bv[j]) + (float)res[u][t][j], 0.f);
+          for (int j = 0; j < 8; ++j) o[j] = (__bf16)tspn::relu_f32((sv[t][j >> 2][j & 3] + bv[j]) + (float)res[u][t][j]);
           const u32x4 o4 = __builtin_bit_cast(u32x4, o);
           if ((u & 1) == 0) {
             held[t] = o4;
@@ -347,10 +347,10 @@ __global__ __launch_bounds__(THREADS, 1) void tail_io_bf16_kernel(
 #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
           bf16x4 v;
-          v[0] = (__bf16)fmaxf(acc[mi][ni][4 * q] + bv.x, 0.f);
-          v[1] = (__bf16)fmaxf(acc[mi][ni][4 * q + 1] + bv.y, 0.f);
-          v[2] = (__bf16)fmaxf(acc[mi][ni][4 * q + 2] + bv.z, 0.f);
-          v[3] = (__bf16)fmaxf(acc[mi][ni][4 * q + 3] + bv.w, 0.f);
+          v[0] = (__bf16)tspn::relu_f32(acc[mi][ni][4 * q] + bv.x);
+          v[1] = (__bf16)tspn::relu_f32(acc[mi][ni][4 * q + 1] + bv.y);
+          v[2] = (__bf16)tspn::relu_f32(acc[mi][ni][4 * q + 2] + bv.z);
+          v[3] = (__bf16)tspn::relu_f32(acc[mi][ni][4 * q + 3] + bv.w);
           *reinterpret_cast<bf16x4*>(Bs + ((ch >> 3) * SLP + ni * 32 + li) * 16 + 8 * kh) = v;
         }
       }
