@@ -926,6 +926,29 @@ int tspn_span_loss_f32(const float* heads, const int64_t* gt, const float* sizes
 int tspn_span_loss_finish(const double* partials, int64_t P, int64_t A, int64_t T, double* out, float* dheads,
                           void* stream);
 
+/* ---- a balanced mini-batch of span anchors (csrc/spansample/tspn_span_sample.hip) ------------------------------
+ * Build-defined (DESIGN.md 2 "span anchor sampling"; the quota rule of the reference's
+ * BalancedPositiveNegativePairSampler, lib/modeling/relpn/sampler.py): selects the anchors of one segment that enter the
+ * span losses, as the `mask` of tspn_span_loss_f32.
+ *   label int8 [n]: the flat [P, A, T] labels of tspn_span_anchor_labels; >= 1 positive, 0 negative, < 0 never selected.
+ *   key(i) = splitmix64(stream_key + i * 0x9E3779B97F4A7C15) >> (64 - key_bits), i the flat index, wrapping 64-bit
+ *   integer arithmetic (the words of hashrng.bits for a stream whose key is stream_key); 1 <= key_bits <= 32.
+ *   The anchors of a class are ordered by (key, i) ascending: equal keys go to the lower index.
+ *   n_pos, n_neg = the class sizes; sel_pos = min(n_pos, want_pos); sel_neg = min(n_neg, batch - sel_pos).
+ *   mask uint8 [n]: 1 for the sel_pos first positives and the sel_neg first negatives, 0 elsewhere; every element is
+ *   written.  counts int64 [4] = (n_pos, n_neg, sel_pos, sel_neg), written by the device: the quotas are never read back.
+ *   partials uint32 [tspn_span_anchor_sample_partials(n)]: the per-chunk digit histograms, the chunk offsets among the
+ *   threshold-equal anchors and the select state, a caller-owned output: the call writes every element before it reads
+ *   it.  4-byte aligned; counts 8-byte aligned; label and mask at any address (16-byte aligned ones take vector forms).
+ * A radix select over 8-bit digits, ceil(key_bits / 8) rounds of two launches, then two more: no host synchronisation,
+ * no global atomic, no memset; the results do not depend on what partials, counts and mask held and are bit-equal from
+ * run to run.  Limits: 0 <= n < 2^31; batch >= 0; 0 <= want_pos <= batch.  n == 0 writes counts = 0 and nothing else
+ * (label, partials and mask may be NULL then); batch == 0 is served, the mask all zeros.
+ * tspn_span_anchor_sample_partials: the number of uint32 elements of `partials`; 0 for an n the entry refuses. */
+int64_t tspn_span_anchor_sample_partials(int64_t n);
+int tspn_span_anchor_sample(const int8_t* label, int64_t n, uint64_t stream_key, int key_bits, int64_t batch,
+                            int64_t want_pos, uint32_t* partials, int64_t* counts, uint8_t* mask, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -189,6 +189,8 @@ PROTOTYPES = {
     "tspn_span_loss_f32": (_int, [_vp, _vp, ctypes.POINTER(ctypes.c_float), _vp, _vp, _vp, _i64, _i64, _i64, _i64,
                                  ctypes.c_double, _vp, _vp, _vp]),
     "tspn_span_loss_finish": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _vp]),
+    "tspn_span_anchor_sample_partials": (_i64, [_i64]),
+    "tspn_span_anchor_sample": (_int, [_vp, _i64, ctypes.c_uint64, _int, _i64, _i64, _vp, _vp, _vp, _vp]),
     "tspn_eval_traj_volume_f64": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "tspn_eval_viou_f64": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "tspn_eval_greedy_match_f64": (_int, [_vp, _vp, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _vp]),

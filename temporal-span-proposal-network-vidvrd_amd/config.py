@@ -85,7 +85,12 @@ _DEFAULTS = {
                 # build extension: training the span heads from ground-truth spans (target field 'spans'):
                 # an anchor is positive from POS_IOU on, negative below NEG_IOU, ignored in between; SMOOTH_L1_BETA is the
                 # width of the quadratic zone of the regression loss
-                "SPAN_LOSS": {"POS_IOU": 0.7, "NEG_IOU": 0.3, "SMOOTH_L1_BETA": 1.0 / 9.0}},
+                # BATCH_SIZE_PER_SEGMENT > 0: the losses take a balanced mini-batch of that many anchors per segment, up to
+                # POSITIVE_FRACTION of it positive, negatives filling the rest (the RPN scheme, sampled on the device:
+                # ops.span_anchor_sample); 0 = every labelled anchor.  SAMPLE_SEED seeds the sampler's hashed keys
+                # (DPN.reseed_span_sampler; one seed per rank under DDP)
+                "SPAN_LOSS": {"POS_IOU": 0.7, "NEG_IOU": 0.3, "SMOOTH_L1_BETA": 1.0 / 9.0,
+                              "BATCH_SIZE_PER_SEGMENT": 0, "POSITIVE_FRACTION": 0.5, "SAMPLE_SEED": 0}},
     },
     "ETC": {"RANDOM_SEED": 0, "MODEL_DUMP_FILE": "baseline_weights_epoch_100.pt"},
 }

@@ -40,6 +40,12 @@ def _key(seed, tag):
     return int(_splitmix64(np.array([k], dtype=np.uint64))[0])
 
 
+def stream_key(seed, tag):
+    """The 64-bit key of stream (seed, tag): word ``i`` of the stream is ``splitmix64(key + i * GOLDEN)``.  What a device
+    kernel needs to regenerate the stream's words (ops.span_anchor_sample)."""
+    return _key(seed, tag)
+
+
 def bits(seed, tag, n, offset=0):
     """``n`` raw uint64 words of stream (seed, tag), starting at ``offset``."""
     k = _key(seed, tag)

@@ -30,7 +30,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import _abi, ops
+from . import _abi, hashrng, ops
 from .sampler import BalancedPositiveNegativePairSampler
 
 TemporalProposals = namedtuple("TemporalProposals", ["relness", "duration", "heads", "geom"], defaults=[None])
@@ -372,14 +372,17 @@ class _TemporalHeadsTrackletFn(torch.autograd.Function):
 class _SpanLossFn(torch.autograd.Function):
     """(loss_relationness, loss_duration_proposal) of one segment from its heads [P,3A,T] and ground-truth spans
     [P,G,2]: anchor labels, both losses and their gradient in three HIP entries (ops.span_anchor_labels,
-    ops.span_loss), nothing synchronised.  The forward already holds the gradient of each loss with respect to its own
+    ops.span_loss; with `sample`, ops.span_anchor_sample between them), nothing synchronised.  The forward already holds the gradient of each loss with respect to its own
     rows of the heads; the backward multiplies the two row groups by the upstream gradients."""
 
     @staticmethod
-    def forward(ctx, heads, gt, sizes, pos_iou, neg_iou, beta):
+    def forward(ctx, heads, gt, sizes, pos_iou, neg_iou, beta, sample=None):
         heads = heads.contiguous()
         label, matched = ops.span_anchor_labels(gt, sizes, heads.shape[2], pos_iou=pos_iou, neg_iou=neg_iou)
-        out, dheads = ops.span_loss(heads, gt, sizes, label, matched, beta=beta)
+        mask = None
+        if sample is not None:                # (batch, positive_fraction, stream_key): the balanced mini-batch of this segment
+            mask, _ = ops.span_anchor_sample(label, *sample)
+        out, dheads = ops.span_loss(heads, gt, sizes, label, matched, mask=mask, beta=beta)
         ctx.save_for_backward(dheads)
         ctx.num_anchors = len(sizes)
         return out[0].float(), out[1].float()
@@ -389,7 +392,7 @@ class _SpanLossFn(torch.autograd.Function):
         dheads, = ctx.saved_tensors
         a = ctx.num_anchors
         scale = torch.cat([g_rel.reshape(1).expand(a), g_reg.reshape(1).expand(2 * a)]).to(dheads.dtype)
-        return dheads * scale.view(1, 3 * a, 1), None, None, None, None, None
+        return dheads * scale.view(1, 3 * a, 1), None, None, None, None, None, None
 
 
 class RelationPredictor(nn.Module):
@@ -579,6 +582,24 @@ class DPN(nn.Module):
         self.span_pos_iou = float(getattr(sl, "POS_IOU", 0.7))
         self.span_neg_iou = float(getattr(sl, "NEG_IOU", 0.3))
         self.span_beta = float(getattr(sl, "SMOOTH_L1_BETA", 1.0 / 9.0))
+        # 0 = every labelled anchor enters the losses; > 0 = a balanced mini-batch per segment, sampled on the device
+        self.span_batch = int(getattr(sl, "BATCH_SIZE_PER_SEGMENT", 0))
+        self.span_positive_fraction = float(getattr(sl, "POSITIVE_FRACTION", 0.5))
+        self.reseed_span_sampler(int(getattr(sl, "SAMPLE_SEED", 0)))
+
+    def reseed_span_sampler(self, seed, start=0):
+        """The c-th segment sampled from here on draws its keys from stream (seed, "span_sample/{start + c}").  The
+        counter is a plain attribute, not part of the state dict: a resumed run reseeds with the count it stopped at,
+        and every rank of a data-parallel run takes its own seed."""
+        self._span_sample_seed, self._span_sample_count = int(seed), int(start)
+
+    def _next_span_sample(self):
+        """The `sample` argument of _SpanLossFn for the next segment, or None when sampling is off."""
+        if self.span_batch <= 0:
+            return None
+        key = hashrng.stream_key(self._span_sample_seed, f"span_sample/{self._span_sample_count}")
+        self._span_sample_count += 1
+        return (self.span_batch, self.span_positive_fraction, key)
 
     def anchor_sizes(self, num_frames):
         """Anchor widths (frames) of the A anchors per location.  cfg.RELPN.DPN.ANCHOR_SIZES when it
@@ -722,7 +743,9 @@ class DPN(nn.Module):
         """Targets with a field 'spans' int64 [P,G,2] (ground-truth frames [start, end) per pair, end <= start =
         padding): the RPN scheme in one dimension the reference intends (relpn/dpn_anchor.py:50-70) -- anchors labelled by
         IoU, `loss_relationness` on the labelled anchors, `loss_duration_proposal` on the positive ones, on the
-        parametrisation decode_spans decodes; both summed over the segments like loss_rel."""
+        parametrisation decode_spans decodes; both summed over the segments like loss_rel.  With
+        RELPN.DPN.SPAN_LOSS.BATCH_SIZE_PER_SEGMENT > 0 the losses of a segment take the balanced mini-batch of
+        ops.span_anchor_sample instead of every labelled anchor."""
         props, loss_rel, loss_reg = [], 0, 0
         for plist, tlist in zip(pair_list, target_list):
             heads = self._train_heads(plist)
@@ -731,7 +754,7 @@ class DPN(nn.Module):
             if gt.dim() != 3 or gt.shape[0] != heads.shape[0] or gt.shape[2] != 2:
                 raise ValueError(f"target field 'spans' must be [P,G,2] with P = {heads.shape[0]}, got {tuple(gt.shape)}")
             l_rel, l_reg = _SpanLossFn.apply(heads, gt.contiguous(), self.anchor_sizes(heads.shape[2]), self.span_pos_iou,
-                                             self.span_neg_iou, self.span_beta)
+                                             self.span_neg_iou, self.span_beta, self._next_span_sample())
             loss_rel, loss_reg = loss_rel + l_rel, loss_reg + l_reg
             props.append(self._wrap(heads))
         return props, {"loss_relationness": loss_rel, "loss_duration_proposal": loss_reg}

@@ -17,7 +17,7 @@ __all__ = [
     "pair_gather", "pack_conv3", "conv3", "conv3_tc", "pack_conv3_wino63", "conv3_tc_wino63", "pack_conv3_wino63_f16x3", "conv3_tc_wino63_f16x3", "heads", "heads_pairgrid", "heads_pairgrid_f16x3", "heads_pairgrid_f16x3_split_bytes",
     "heads_pairgrid_f16x3_set_force_exact", "temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
     "forward_fused", "temporal_encoder_heads", "fused_workspace_bytes", "fused_bf16_workspace_bytes", "decode_topk", "decode_spans", "decode_span_relations",
-    "span_anchor_labels", "span_loss",
+    "span_anchor_labels", "span_loss", "span_anchor_sample",
     "cast_bf16", "pack_conv3_bf16", "pack_heads_bf16", "conv3_tc_bf16", "heads_pairgrid_bf16",
     "pair_plan", "heads_pairlist_bf16",
     "transpose_cast_bf16", "temporal_encoder_heads_bf16",
@@ -778,6 +778,38 @@ def span_loss(heads, gt, sizes, label, matched, mask=None, beta=1.0 / 9.0):
                                       _p(partials), _p(dheads), stream))
     _abi.check(lib.tspn_span_loss_finish(_p(partials), P, A, T, _p(out), _p(dheads), stream))
     return out, dheads
+
+
+def span_anchor_sample(label, batch, positive_fraction, stream_key, key_bits=32, mask=None):
+    """A balanced mini-batch of span anchors (tspn_span_anchor_sample): label int8 of any shape (the [P,A,T]
+    labels of span_anchor_labels; taken flat), at most `batch` anchors selected, up to int(batch * positive_fraction) of them
+    positive and negatives for the rest, in the order of the hashed keys of `stream_key` (hashrng.stream_key(seed, tag))
+    shortened to `key_bits`, ties to the lower flat index.  Returns (mask uint8 of label's shape -- `mask` itself when one
+    is passed -- and counts int64 [4] = (n_pos, n_neg, sel_pos, sel_neg)).  Nothing is synchronised."""
+    who = "span_anchor_sample"
+    if isinstance(label, torch.Tensor) and label.is_cuda and label.dtype == torch.int8:
+        label = label.contiguous()
+    _dev(label, f"{who}: label", torch.int8)
+    batch, key_bits = int(batch), int(key_bits)
+    if batch < 0 or not 0.0 <= float(positive_fraction) <= 1.0:
+        raise ValueError(f"{who}: needs batch >= 0 and 0 <= positive_fraction <= 1, got {batch}, {positive_fraction}")
+    want_pos = int(batch * float(positive_fraction))
+    if mask is None:
+        mask = torch.empty(label.shape, dtype=torch.uint8, device=label.device)
+    else:
+        _dev(mask, f"{who}: mask", torch.uint8)
+        if mask.shape != label.shape:
+            raise ValueError(f"{who}: mask must have label's shape {tuple(label.shape)}, got {tuple(mask.shape)}")
+    n = label.numel()
+    lib = _abi.lib()
+    words = lib.tspn_span_anchor_sample_partials(n)
+    if words == 0:
+        raise ValueError(f"{who}: n = {n} anchors (needs < 2^31)")
+    partials = torch.empty((words,), dtype=torch.int32, device=label.device)     # uint32 words; torch only carries them
+    counts = torch.empty((4,), dtype=torch.int64, device=label.device)
+    _abi.check(lib.tspn_span_anchor_sample(_p(label), n, int(stream_key) & 0xFFFFFFFFFFFFFFFF, key_bits, batch, want_pos,
+                                           _p(partials), _p(counts), _p(mask), _stream()))
+    return mask, counts
 
 
 def _fused_desc(feats, pairs, B, N, conv_packed, conv_bias, head_w, head_b, cls_w, cls_b):
