@@ -130,6 +130,28 @@ int tspn::segment_span_topk(const unsigned* key, const float* sc, const int* ix,
   return tspn::check_launch(what);
 }
 
+int tspn::span_relation_sizes(const char* who, int64_t S, int64_t N, int64_t T, int64_t D, int64_t P, int64_t J, int64_t K,
+                              int64_t NO, int64_t topk_per_span, int64_t topk_per_seg) {
+  TSPN_REQUIRE(S >= 0 && N >= 0 && P >= 0 && T > 0 && D > 0 && J > 0 && K > 0 && NO > 0 && topk_per_span > 0 &&
+                   topk_per_seg > 0 && T < (1 << 30) && N < (1LL << 31) && P < (1LL << 31) && S < (1LL << 31),
+               TSPN_EINVAL, "%s: bad sizes S=%lld N=%lld T=%lld D=%lld P=%lld J=%lld K=%lld NO=%lld", who,
+               (long long)S, (long long)N, (long long)T, (long long)D, (long long)P, (long long)J, (long long)K,
+               (long long)NO);
+  return TSPN_OK;
+}
+
+int tspn::span_relation_limits(const char* who, int64_t P, int64_t J, int64_t K, int64_t topk_per_span,
+                               int64_t topk_per_seg, int64_t* R) {
+  TSPN_REQUIRE(K <= tspn::kRowTopkMaxK, TSPN_EUNSUPPORTED, "%s: K=%lld > %d", who, (long long)K, tspn::kRowTopkMaxK);
+  TSPN_REQUIRE(topk_per_seg <= tspn::kSelectMaxM, TSPN_EUNSUPPORTED, "%s: topk_per_seg=%lld > %d", who,
+               (long long)topk_per_seg, tspn::kSelectMaxM);
+  TSPN_REQUIRE(J <= MAX_J, TSPN_EUNSUPPORTED, "%s: spans_per_pair J=%lld > %d", who, (long long)J, MAX_J);
+  *R = std::min<int64_t>(topk_per_span, K);
+  TSPN_REQUIRE(P * J * *R < (1LL << 31), TSPN_EUNSUPPORTED, "%s: P*J*topk_per_span = %lld candidates per segment", who,
+               (long long)(P * J * *R));
+  return TSPN_OK;
+}
+
 extern "C" size_t tspn_decode_span_relations_workspace_bytes(int64_t S, int64_t N, int64_t T, int64_t D, int64_t P,
                                                              int64_t J, int64_t K, int64_t topk_per_span) {
   if (S <= 0 || N <= 0 || T <= 0 || D <= 0 || P <= 0 || J <= 0 || K <= 0 || topk_per_span <= 0) return 0;
@@ -149,18 +171,9 @@ extern "C" int tspn_decode_span_relations_f32(const float* feats, int64_t S, int
                                               int64_t* out_valid, void* workspace, size_t workspace_bytes,
                                               void* stream) {
   const char* who = "tspn_decode_span_relations_f32";
-  TSPN_REQUIRE(S >= 0 && N >= 0 && P >= 0 && T > 0 && D > 0 && J > 0 && K > 0 && NO > 0 && topk_per_span > 0 &&
-                   topk_per_seg > 0 && T < (1 << 30) && N < (1LL << 31) && P < (1LL << 31) && S < (1LL << 31),
-               TSPN_EINVAL, "%s: bad sizes S=%lld N=%lld T=%lld D=%lld P=%lld J=%lld K=%lld NO=%lld", who,
-               (long long)S, (long long)N, (long long)T, (long long)D, (long long)P, (long long)J, (long long)K,
-               (long long)NO);
-  TSPN_REQUIRE(K <= tspn::kRowTopkMaxK, TSPN_EUNSUPPORTED, "%s: K=%lld > %d", who, (long long)K, tspn::kRowTopkMaxK);
-  TSPN_REQUIRE(topk_per_seg <= tspn::kSelectMaxM, TSPN_EUNSUPPORTED, "%s: topk_per_seg=%lld > %d", who,
-               (long long)topk_per_seg, tspn::kSelectMaxM);
-  TSPN_REQUIRE(J <= MAX_J, TSPN_EUNSUPPORTED, "%s: spans_per_pair J=%lld > %d", who, (long long)J, MAX_J);
-  const int64_t R = std::min<int64_t>(topk_per_span, K);
-  TSPN_REQUIRE(P * J * R < (1LL << 31), TSPN_EUNSUPPORTED, "%s: P*J*topk_per_span = %lld candidates per segment", who,
-               (long long)(P * J * R));
+  int64_t R;
+  if (int rc = tspn::span_relation_sizes(who, S, N, T, D, P, J, K, NO, topk_per_span, topk_per_seg)) return rc;
+  if (int rc = tspn::span_relation_limits(who, P, J, K, topk_per_span, topk_per_seg, &R)) return rc;
   if (S == 0 || P == 0) return TSPN_OK;
   TSPN_REQUIRE(N > 0, TSPN_EINVAL, "%s: pairs without tracklets", who);
   TSPN_REQUIRE(feats && pairs && spans && span_scores && span_counts && cls_w && cls_logits && out_score &&

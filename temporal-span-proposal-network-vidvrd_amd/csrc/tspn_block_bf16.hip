@@ -510,6 +510,9 @@ int launch(const uint16_t* x, int64_t NB, int64_t Hin, int64_t Win, const uint16
            void* stream, const char* what) {
   constexpr int TR = tile_rows(CM);
   const int64_t H = (Hin - 1) / ST + 1, W = (Win - 1) / ST + 1;
+  // 32-bit byte offsets inside one image (the identity block, CIN = 4 CM and ST = 1, has one map: both terms are it)
+  TSPN_REQUIRE(H * W * 4 * CM * 2 < (1LL << 31) && Hin * Win * CIN * 2 < (1LL << 31), TSPN_EUNSUPPORTED,
+               "%s: one image's %s must stay below 2 GB", what, RES == 0 ? "map" : "maps");
   const int64_t tiles_x = tspn::ceil_div(W, TW), tiles_y = tspn::ceil_div(H, TR);
   const int64_t ntiles = NB * tiles_x * tiles_y;
   TSPN_REQUIRE(ntiles < (1LL << 30), TSPN_EUNSUPPORTED, "%s: grid too large", what);
@@ -536,12 +539,9 @@ extern "C" int tspn_bottleneck_block_bf16(const uint16_t* x, int64_t NB, int64_t
   TSPN_REQUIRE(CM == 64 || CM == 128, TSPN_EUNSUPPORTED, "%s: bottleneck channels must be 64 or 128 (got %lld)", what,
                (long long)CM);
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(x && frag1 && bias1 && frag2 && bias2 && frag3 && bias3 && out, TSPN_EINVAL, "%s: null pointer", what);
-  TSPN_REQUIRE(x != out, TSPN_EINVAL, "%s: the block cannot run in place (tiles read their neighbours' pixels)", what);
-  TSPN_REQUIRE(tspn::all_aligned16(x, frag1, bias1, frag2, bias2, frag3, bias3, out),
-               TSPN_EUNSUPPORTED, "%s: operands must be 16-byte aligned", what);
-  // 32-bit byte offsets inside one image
-  TSPN_REQUIRE(H * W * 4 * CM * 2 < (1LL << 31), TSPN_EUNSUPPORTED, "%s: one image's map must stay below 2 GB", what);
+  if (int rc = tspn::operand_checks(what, {x, frag1, bias1, frag2, bias2, frag3, bias3, out}, x != out,
+                                    "the block cannot run in place (tiles read their neighbours' pixels)"))
+    return rc;
   if (CM == 128)
     return launch<128, 512, 1, 0>(x, NB, H, W, frag1, bias1, frag2, bias2, frag3, bias3, nullptr, nullptr, out, stream, what);
   return launch<64, 256, 1, 0>(x, NB, H, W, frag1, bias1, frag2, bias2, frag3, bias3, nullptr, nullptr, out, stream, what);
@@ -560,13 +560,7 @@ extern "C" int tspn_bottleneck_block_proj_bf16(const uint16_t* x, int64_t NB, in
                "%s: built for the first block of res2 (64 -> 64 -> 256, stride 1); got CIN=%lld CM=%lld stride=%lld", what,
                (long long)CIN, (long long)CM, (long long)stride);
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(x && frag1 && bias1 && frag2 && bias2 && frag3 && bias3 && frags && biass && out, TSPN_EINVAL,
-               "%s: null pointer", what);
-  TSPN_REQUIRE(tspn::all_aligned16(x, frag1, bias1, frag2, bias2, frag3, bias3, frags, biass, out),
-               TSPN_EUNSUPPORTED, "%s: operands must be 16-byte aligned", what);
-  const int64_t H = (Hin - 1) / stride + 1, W = (Win - 1) / stride + 1;
-  TSPN_REQUIRE(H * W * 4 * CM * 2 < (1LL << 31) && Hin * Win * CIN * 2 < (1LL << 31), TSPN_EUNSUPPORTED,
-               "%s: one image's maps must stay below 2 GB", what);
+  if (int rc = tspn::operand_checks(what, {x, frag1, bias1, frag2, bias2, frag3, bias3, frags, biass, out})) return rc;
   return launch<64, 64, 1, 1>(x, NB, Hin, Win, frag1, bias1, frag2, bias2, frag3, bias3, frags, biass, out, stream, what);
 }
 
@@ -580,12 +574,7 @@ extern "C" int tspn_bottleneck_block_res_bf16(const uint16_t* x, int64_t NB, int
                "%s: built for the first block of res3 (256 -> 128 -> 512, stride 2); got CIN=%lld CM=%lld stride=%lld", what,
                (long long)CIN, (long long)CM, (long long)stride);
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(x && frag1 && bias1 && frag2 && bias2 && frag3 && bias3 && residual && out, TSPN_EINVAL, "%s: null pointer", what);
-  TSPN_REQUIRE(residual != out, TSPN_EINVAL, "%s: out must not alias the residual", what);
-  TSPN_REQUIRE(tspn::all_aligned16(x, frag1, bias1, frag2, bias2, frag3, bias3, residual, out),
-               TSPN_EUNSUPPORTED, "%s: operands must be 16-byte aligned", what);
-  const int64_t H = (Hin - 1) / stride + 1, W = (Win - 1) / stride + 1;
-  TSPN_REQUIRE(H * W * 4 * CM * 2 < (1LL << 31) && Hin * Win * CIN * 2 < (1LL << 31), TSPN_EUNSUPPORTED,
-               "%s: one image's maps must stay below 2 GB", what);
+  if (int rc = tspn::operand_checks(what, {x, frag1, bias1, frag2, bias2, frag3, bias3, residual, out}, residual != out,
+                                    "out must not alias the residual")) return rc;
   return launch<128, 256, 2, 2>(x, NB, Hin, Win, frag1, bias1, frag2, bias2, frag3, bias3, residual, nullptr, out, stream, what);
 }

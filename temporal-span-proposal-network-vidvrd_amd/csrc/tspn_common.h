@@ -158,6 +158,12 @@ int segment_span_topk(const unsigned* key, const float* sc, const int* ix, const
                       int64_t J, int64_t R, int64_t topk_per_seg, float* out_score, int64_t* out_triplet,
                       int64_t* out_pair_tid, int64_t* out_span, int64_t* out_span_rank, int64_t* out_valid, void* stream,
                       const char* what);
+// The size checks both entries open with (defined beside segment_span_topk), in two steps because the bf16 entry's D % 16
+// rule stands between them: the sizes, then the limits on K, topk_per_seg, J and the candidates; R = min(topk_per_span, K).
+int span_relation_sizes(const char* who, int64_t S, int64_t N, int64_t T, int64_t D, int64_t P, int64_t J, int64_t K,
+                        int64_t NO, int64_t topk_per_span, int64_t topk_per_seg);
+int span_relation_limits(const char* who, int64_t P, int64_t J, int64_t K, int64_t topk_per_span, int64_t topk_per_seg,
+                         int64_t* R);
 
 }  // namespace tspn
 
@@ -180,16 +186,48 @@ inline int tail_shape_checks(const char* what, int64_t NB, int64_t H, int64_t W,
   TSPN_REQUIRE(channels_ok, TSPN_EUNSUPPORTED, "%s: %s (got %lld)", what, channel_rule, (long long)CM);
   return TSPN_OK;
 }
-// ... then null operands, their alignment, and H, W below 2^20 (32-bit pixel arithmetic in the tap mask).
-inline int tail_operand_checks(const char* what, int64_t H, int64_t W, std::initializer_list<const void*> operands) {
+// ... then null operands, their alignment, and H, W below 2^20 (32-bit pixel arithmetic in the tap mask).  The fused
+// bottleneck block entries call operand_checks, with their aliasing rule (`alias_rule` words the refusal) between the two.
+inline int operand_checks(const char* what, std::initializer_list<const void*> operands, bool alias_free = true,
+                          const char* alias_rule = nullptr) {
   bool all = true, aligned = true;
   for (const void* p : operands) {
     all = all && p != nullptr;
     aligned = aligned && aligned16(p);
   }
   TSPN_REQUIRE(all, TSPN_EINVAL, "%s: null pointer", what);
+  TSPN_REQUIRE(alias_free, TSPN_EINVAL, "%s: %s", what, alias_rule);
   TSPN_REQUIRE(aligned, TSPN_EUNSUPPORTED, "%s: operands must be 16-byte aligned", what);
+  return TSPN_OK;
+}
+inline int tail_operand_checks(const char* what, int64_t H, int64_t W, std::initializer_list<const void*> operands) {
+  if (int rc = operand_checks(what, operands)) return rc;
   TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20), TSPN_EUNSUPPORTED, "%s: dimension too large", what);
+  return TSPN_OK;
+}
+
+// The opening checks of the conv2d and max-pool entries, again around the entry's own `if (NB == 0) return TSPN_OK;`.
+// First the sizes (`sizes_ok`: each entry has its list), the entry's rule on the window (`window_rule` words the refusal; the
+// pools have none) and a window larger than the padded map (the truncating division would still give one pixel) ...
+inline int window_shape_checks(const char* what, bool sizes_ok, bool window_ok, const char* window_rule, int64_t H,
+                               int64_t W, int64_t KH, int64_t KW, int64_t stride, int64_t pad, int64_t* OH, int64_t* OW) {
+  TSPN_REQUIRE(sizes_ok, TSPN_EINVAL, "%s: bad sizes", what);
+  TSPN_REQUIRE(window_ok, TSPN_EUNSUPPORTED, "%s: %s", what, window_rule);
+  TSPN_REQUIRE(H + 2 * pad >= KH && W + 2 * pad >= KW, TSPN_EINVAL, "%s: empty output", what);
+  *OH = (H + 2 * pad - KH) / stride + 1, *OW = (W + 2 * pad - KW) / stride + 1;
+  return TSPN_OK;
+}
+// ... then the operands of the f32, frag and bf16 conv entries: null, the entry's divisibility rule (`channel_rule` words
+// it), alignment (bias and residual may be null) and the sizes the kernels' 32-bit arithmetic holds.
+inline int conv_operand_checks(const char* what, const void* x, const void* w, const void* out, const void* bias,
+                               const void* residual, bool channels_ok, const char* channel_rule, int64_t H, int64_t W,
+                               int64_t Cin, int64_t Cout) {
+  TSPN_REQUIRE(x && w && out, TSPN_EINVAL, "%s: null pointer", what);
+  TSPN_REQUIRE(channels_ok, TSPN_EUNSUPPORTED, "%s: needs %s (Cin=%lld Cout=%lld)", what, channel_rule, (long long)Cin,
+               (long long)Cout);
+  TSPN_REQUIRE(all_aligned16(x, w, out, bias, residual), TSPN_EUNSUPPORTED, "%s: operands must be 16-byte aligned", what);
+  TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20) && Cin < (1 << 24) && Cout < (1 << 24), TSPN_EUNSUPPORTED,
+               "%s: dimension too large", what);
   return TSPN_OK;
 }
 

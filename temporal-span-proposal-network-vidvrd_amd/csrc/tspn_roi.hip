@@ -544,33 +544,25 @@ extern "C" int tspn_conv2d_nhwc_f32(const float* x, int64_t NB, int64_t H, int64
                                     const float* packed, int64_t Cout, int64_t KH, int64_t KW, int64_t stride,
                                     int64_t pad, const float* bias, const float* residual, int relu, float* out,
                                     void* stream) {
-  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0,
-               TSPN_EINVAL, "tspn_conv2d_nhwc_f32: bad sizes");
-  TSPN_REQUIRE(KH * KW <= 64, TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_f32: at most 64 taps");
-  // (a kernel larger than the padded map: the truncating division below would still give one output pixel)
-  TSPN_REQUIRE(H + 2 * pad >= KH && W + 2 * pad >= KW, TSPN_EINVAL, "tspn_conv2d_nhwc_f32: empty output");
-  const int64_t OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-  TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "tspn_conv2d_nhwc_f32: empty output (H=%lld W=%lld)", (long long)H,
-               (long long)W);
+  const char* what = "tspn_conv2d_nhwc_f32";
+  const bool sizes_ok = NB >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0;
+  int64_t OH, OW;
+  if (int rc = tspn::window_shape_checks(what, sizes_ok, KH * KW <= 64, "at most 64 taps", H, W, KH, KW, stride, pad, &OH, &OW))
+    return rc;
+  TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "%s: empty output (H=%lld W=%lld)", what, (long long)H, (long long)W);
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(x && packed && out, TSPN_EINVAL, "tspn_conv2d_nhwc_f32: null pointer");
-  TSPN_REQUIRE(Cin % 16 == 0 && Cout % 4 == 0, TSPN_EUNSUPPORTED,
-               "tspn_conv2d_nhwc_f32: needs Cin %% 16 == 0 and Cout %% 4 == 0 (Cin=%lld Cout=%lld)", (long long)Cin,
-               (long long)Cout);
-  TSPN_REQUIRE(tspn::all_aligned16(x, packed, out) && (!bias || tspn::aligned16(bias)) &&
-                   (!residual || tspn::aligned16(residual)),
-               TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_f32: operands must be 16-byte aligned");
-  TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20) && Cin < (1 << 24) && Cout < (1 << 24), TSPN_EUNSUPPORTED,
-               "tspn_conv2d_nhwc_f32: dimension too large");
+  if (int rc = tspn::conv_operand_checks(what, x, packed, out, bias, residual, Cin % 16 == 0 && Cout % 4 == 0,
+                                         "Cin % 16 == 0 and Cout % 4 == 0", H, W, Cin, Cout))
+    return rc;
   const int64_t npix = NB * OH * OW;
   const int64_t tiles_m = tspn::ceil_div(Cout, BM), tiles_n = tspn::ceil_div(npix, BN);
-  TSPN_REQUIRE(tiles_m * tiles_n < (1LL << 31), TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_f32: grid too large");
+  TSPN_REQUIRE(tiles_m * tiles_n < (1LL << 31), TSPN_EUNSUPPORTED, "%s: grid too large", what);
   // (32-channel chunks were measured slower: 92 vs 102 TFLOP/s on the res5 shapes; 16 ships)
   hipLaunchKernelGGL(conv2d_nhwc_kernel<16>, dim3((unsigned)(tiles_m * tiles_n)), dim3(THREADS),
                      smem_bytes<16>(), TSPN_STREAM(stream), x, packed, bias, residual, out, (int)H, (int)W,
                      (int)Cin, (int)Cout, (int)KH, (int)KW, (int)stride, (int)pad, (int)OH, (int)OW, npix,
                      (int)tiles_m, (int)tiles_n, relu);
-  return tspn::check_launch("tspn_conv2d_nhwc_f32");
+  return tspn::check_launch(what);
 }
 
 extern "C" int tspn_pack_conv2d_frag_f32(const float* w, int64_t Cout, int64_t Cin, int64_t KH, int64_t KW,
@@ -592,31 +584,24 @@ extern "C" int tspn_conv2d_nhwc_frag_f32(const float* x, int64_t NB, int64_t H, 
                                          const float* frag, int64_t Cout, int64_t KH, int64_t KW,
                                          int64_t stride, int64_t pad, const float* bias, const float* residual,
                                          int relu, float* out, void* stream) {
-  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0,
-               TSPN_EINVAL, "tspn_conv2d_nhwc_frag_f32: bad sizes");
-  TSPN_REQUIRE(KH * KW <= 64, TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_frag_f32: at most 64 taps");
-  // (a kernel larger than the padded map: the truncating division below would still give one output pixel)
-  TSPN_REQUIRE(H + 2 * pad >= KH && W + 2 * pad >= KW, TSPN_EINVAL, "tspn_conv2d_nhwc_frag_f32: empty output");
-  const int64_t OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-  TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "tspn_conv2d_nhwc_frag_f32: empty output");
+  const char* what = "tspn_conv2d_nhwc_frag_f32";
+  const bool sizes_ok = NB >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0;
+  int64_t OH, OW;
+  if (int rc = tspn::window_shape_checks(what, sizes_ok, KH * KW <= 64, "at most 64 taps", H, W, KH, KW, stride, pad, &OH, &OW))
+    return rc;
+  TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "%s: empty output", what);
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(x && frag && out, TSPN_EINVAL, "tspn_conv2d_nhwc_frag_f32: null pointer");
-  TSPN_REQUIRE(Cin % 16 == 0 && Cout % 32 == 0, TSPN_EUNSUPPORTED,
-               "tspn_conv2d_nhwc_frag_f32: needs Cin %% 16 == 0 and Cout %% 32 == 0 (Cin=%lld Cout=%lld)",
-               (long long)Cin, (long long)Cout);
-  TSPN_REQUIRE(tspn::all_aligned16(x, frag, out) && (!bias || tspn::aligned16(bias)) &&
-                   (!residual || tspn::aligned16(residual)),
-               TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_frag_f32: operands must be 16-byte aligned");
-  TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20) && Cin < (1 << 24) && Cout < (1 << 24), TSPN_EUNSUPPORTED,
-               "tspn_conv2d_nhwc_frag_f32: dimension too large");
+  if (int rc = tspn::conv_operand_checks(what, x, frag, out, bias, residual, Cin % 16 == 0 && Cout % 32 == 0,
+                                         "Cin % 16 == 0 and Cout % 32 == 0", H, W, Cin, Cout))
+    return rc;
   const int64_t npix = NB * OH * OW;
   const int64_t tiles_m = tspn::ceil_div(Cout, BM), tiles_n = tspn::ceil_div(npix, BN);
-  TSPN_REQUIRE(tiles_m * tiles_n < (1LL << 31), TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_frag_f32: grid too large");
+  TSPN_REQUIRE(tiles_m * tiles_n < (1LL << 31), TSPN_EUNSUPPORTED, "%s: grid too large", what);
   hipLaunchKernelGGL(conv2d_nhwc_frag_kernel<false>, dim3((unsigned)(tiles_m * tiles_n)), dim3(THREADS), 0,
                      TSPN_STREAM(stream), x, frag, bias, residual, out, (int)H, (int)W, (int)Cin, (int)Cout,
                      (int)KH, (int)KW, (int)stride, (int)pad, (int)OH, (int)OW, npix, (int)tiles_m, (int)tiles_n,
                      relu);
-  return tspn::check_launch("tspn_conv2d_nhwc_frag_f32");
+  return tspn::check_launch(what);
 }
 
 extern "C" int tspn_pack_conv2d_frag_cin4_f32(const float* w, int64_t Cout, int64_t Cin, int64_t KH, int64_t KW,
@@ -634,27 +619,26 @@ extern "C" int tspn_pack_conv2d_frag_cin4_f32(const float* w, int64_t Cout, int6
 extern "C" int tspn_conv2d_nhwc_cin4_f32(const float* x, int64_t NB, int64_t H, int64_t W, const float* frag,
                                          int64_t Cout, int64_t KH, int64_t KW, int64_t stride, int64_t pad,
                                          const float* bias, int relu, float* out, void* stream) {
-  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0, TSPN_EINVAL,
-               "tspn_conv2d_nhwc_cin4_f32: bad sizes");
-  TSPN_REQUIRE(KH * KW <= 64 && Cout % 32 == 0, TSPN_EUNSUPPORTED,
-               "tspn_conv2d_nhwc_cin4_f32: needs at most 64 taps and Cout %% 32 == 0");
-  // (a kernel larger than the padded map: the truncating division below would still give one output pixel)
-  TSPN_REQUIRE(H + 2 * pad >= KH && W + 2 * pad >= KW, TSPN_EINVAL, "tspn_conv2d_nhwc_cin4_f32: empty output");
-  const int64_t OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-  TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "tspn_conv2d_nhwc_cin4_f32: empty output");
+  const char* what = "tspn_conv2d_nhwc_cin4_f32";
+  const bool sizes_ok = NB >= 0 && H > 0 && W > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0;
+  int64_t OH, OW;
+  if (int rc = tspn::window_shape_checks(what, sizes_ok, KH * KW <= 64 && Cout % 32 == 0,
+                                         "needs at most 64 taps and Cout % 32 == 0", H, W, KH, KW, stride, pad, &OH, &OW))
+    return rc;
+  TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "%s: empty output", what);
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(x && frag && out, TSPN_EINVAL, "tspn_conv2d_nhwc_cin4_f32: null pointer");
-  TSPN_REQUIRE(tspn::all_aligned16(x, frag, out) && (!bias || tspn::aligned16(bias)), TSPN_EUNSUPPORTED,
-               "tspn_conv2d_nhwc_cin4_f32: operands must be 16-byte aligned");
+  // (its size limits are worded as one refusal, after the grid's: not conv_operand_checks)
+  TSPN_REQUIRE(x && frag && out, TSPN_EINVAL, "%s: null pointer", what);
+  TSPN_REQUIRE(tspn::all_aligned16(x, frag, out, bias), TSPN_EUNSUPPORTED, "%s: operands must be 16-byte aligned", what);
   const int64_t npix = NB * OH * OW;
   const int64_t tiles_m = tspn::ceil_div(Cout, BM), tiles_n = tspn::ceil_div(npix, BN);
   TSPN_REQUIRE(tiles_m * tiles_n < (1LL << 31) && H < (1 << 20) && W < (1 << 20), TSPN_EUNSUPPORTED,
-               "tspn_conv2d_nhwc_cin4_f32: problem too large");
+               "%s: problem too large", what);
   hipLaunchKernelGGL(conv2d_nhwc_frag_kernel<true>, dim3((unsigned)(tiles_m * tiles_n)), dim3(THREADS), 0,
                      TSPN_STREAM(stream), x, frag, bias, static_cast<const float*>(nullptr), out, (int)H, (int)W, 4,
                      (int)Cout, (int)KH, (int)KW, (int)stride, (int)pad, (int)OH, (int)OW, npix, (int)tiles_m,
                      (int)tiles_n, relu);
-  return tspn::check_launch("tspn_conv2d_nhwc_cin4_f32");
+  return tspn::check_launch(what);
 }
 
 static int roi_align_launch(const void* feat, bool bf16_in, int64_t NF, int64_t H, int64_t W, int64_t C,
@@ -703,11 +687,10 @@ extern "C" int tspn_roi_align_nhwc_bf16(const uint16_t* feat, int64_t NF, int64_
 
 extern "C" int tspn_max_pool_nhwc_f32(const float* x, int64_t NB, int64_t H, int64_t W, int64_t C, int64_t k,
                                       int64_t stride, int64_t pad, void* out, int out_bf16, void* stream) {
-  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0 && 2 * pad <= k, TSPN_EINVAL,
-               "tspn_max_pool_nhwc_f32: bad sizes");
-  // (a window larger than the padded map: the truncating division below would still give one output pixel)
-  TSPN_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k, TSPN_EINVAL, "tspn_max_pool_nhwc_f32: empty output");
-  const int64_t OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
+  const bool sizes_ok = NB >= 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0 && 2 * pad <= k;
+  int64_t OH, OW;
+  if (int rc = tspn::window_shape_checks("tspn_max_pool_nhwc_f32", sizes_ok, true, nullptr, H, W, k, k, stride, pad, &OH, &OW))
+    return rc;
   if (NB == 0) return TSPN_OK;
   TSPN_REQUIRE(x && out, TSPN_EINVAL, "tspn_max_pool_nhwc_f32: null pointer");
   TSPN_REQUIRE(C % 4 == 0 && tspn::all_aligned16(x, out),

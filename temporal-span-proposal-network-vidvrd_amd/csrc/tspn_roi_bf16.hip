@@ -449,30 +449,23 @@ extern "C" int tspn_conv2d_nhwc_bf16(const uint16_t* x, int64_t NB, int64_t H, i
                                      const uint16_t* frag, int64_t Cout, int64_t KH, int64_t KW, int64_t stride,
                                      int64_t pad, const float* bias, const uint16_t* residual, int relu,
                                      uint16_t* out, void* stream) {
-  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0,
-               TSPN_EINVAL, "tspn_conv2d_nhwc_bf16: bad sizes");
-  TSPN_REQUIRE(KH * KW <= 64, TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_bf16: at most 64 taps");
-  // (a kernel larger than the padded map: the truncating division below would still give one output pixel)
-  TSPN_REQUIRE(H + 2 * pad >= KH && W + 2 * pad >= KW, TSPN_EINVAL, "tspn_conv2d_nhwc_bf16: empty output");
-  const int64_t OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-  TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "tspn_conv2d_nhwc_bf16: empty output");
+  const char* what = "tspn_conv2d_nhwc_bf16";
+  const bool sizes_ok = NB >= 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && KH > 0 && KW > 0 && stride > 0 && pad >= 0;
+  int64_t OH, OW;
+  if (int rc = tspn::window_shape_checks(what, sizes_ok, KH * KW <= 64, "at most 64 taps", H, W, KH, KW, stride, pad, &OH, &OW))
+    return rc;
+  TSPN_REQUIRE(OH > 0 && OW > 0, TSPN_EINVAL, "%s: empty output", what);
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(x && frag && out, TSPN_EINVAL, "tspn_conv2d_nhwc_bf16: null pointer");
-  TSPN_REQUIRE(Cin % KC == 0 && Cout % 32 == 0, TSPN_EUNSUPPORTED,
-               "tspn_conv2d_nhwc_bf16: needs Cin %% 64 == 0 and Cout %% 32 == 0 (Cin=%lld Cout=%lld)", (long long)Cin,
-               (long long)Cout);
-  TSPN_REQUIRE(tspn::all_aligned16(x, frag, out) && (!bias || tspn::aligned16(bias)) &&
-                   (!residual || tspn::aligned16(residual)),
-               TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_bf16: operands must be 16-byte aligned");
-  TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20) && Cin < (1 << 24) && Cout < (1 << 24), TSPN_EUNSUPPORTED,
-               "tspn_conv2d_nhwc_bf16: dimension too large");
+  if (int rc = tspn::conv_operand_checks(what, x, frag, out, bias, residual, Cin % KC == 0 && Cout % 32 == 0,
+                                         "Cin % 64 == 0 and Cout % 32 == 0", H, W, Cin, Cout))
+    return rc;
   const int64_t npix = NB * OH * OW;
   // x goes out as buffer loads: 32-bit byte offsets from the first pixel of the image the tile starts in, num_records
   // 2^31 - 1 (an offset beyond it would read as padding zeros: silently wrong).  A 128-pixel tile spans at most
   // 127 / (OH OW) + 2 images, a tap reaches KH rows further.
   TSPN_REQUIRE(((int64_t)(BN - 1) / (OH * OW) + 2) * H * W * Cin * 2 + KH * W * Cin * 2 < (1LL << 31), TSPN_EUNSUPPORTED,
-               "tspn_conv2d_nhwc_bf16: the images one 128-pixel tile spans must stay below 2 GB (H=%lld W=%lld Cin=%lld)",
-               (long long)H, (long long)W, (long long)Cin);
+               "%s: the images one 128-pixel tile spans must stay below 2 GB (H=%lld W=%lld Cin=%lld)", what, (long long)H,
+               (long long)W, (long long)Cin);
   // 64 rows per wave where Cout allows — except the 1x1 layers with K <= 256 (res2 - res4 expand convs): four K
   // chunks of MFMAs between a 64 KB operand prologue and a residual + store epilogue are latency-bound, and
   // the 32-row form at three workgroups per CU hides more of it (backbone conv time 8.59 -> 8.12 ms per 16
@@ -482,7 +475,7 @@ extern "C" int tspn_conv2d_nhwc_bf16(const uint16_t* x, int64_t NB, int64_t H, i
 #endif
   const int mi = (Cout % 64 == 0 && !(KH * KW == 1 && Cin <= TSPN_ROI_BF16_SHORTK_MI1)) ? 2 : 1;
   const int64_t tiles_m = tspn::ceil_div(Cout, 128 * mi), tiles_n = tspn::ceil_div(npix, BN);
-  TSPN_REQUIRE(tiles_m * tiles_n < (1LL << 31), TSPN_EUNSUPPORTED, "tspn_conv2d_nhwc_bf16: grid too large");
+  TSPN_REQUIRE(tiles_m * tiles_n < (1LL << 31), TSPN_EUNSUPPORTED, "%s: grid too large", what);
   auto launch = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3((unsigned)(tiles_m * tiles_n)), dim3(THREADS), 0, TSPN_STREAM(stream),
                        reinterpret_cast<const __bf16*>(x), reinterpret_cast<const __bf16*>(frag), bias,
@@ -493,5 +486,5 @@ extern "C" int tspn_conv2d_nhwc_bf16(const uint16_t* x, int64_t NB, int64_t H, i
   const bool rng = KH == 3 && KW == 3 && stride == 1 && pad == 1;
   if (mi == 2) { if (rng) launch(conv2d_nhwc_bf16_kernel<2, true>); else launch(conv2d_nhwc_bf16_kernel<2, false>); }
   else { if (rng) launch(conv2d_nhwc_bf16_kernel<1, true>); else launch(conv2d_nhwc_bf16_kernel<1, false>); }
-  return tspn::check_launch("tspn_conv2d_nhwc_bf16");
+  return tspn::check_launch(what);
 }

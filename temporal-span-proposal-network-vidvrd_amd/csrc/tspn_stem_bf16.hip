@@ -384,6 +384,67 @@ __global__ __launch_bounds__(256) void max_pool_nhwc_bf16_kernel(const __bf16* _
 
 inline int64_t out_dim(int64_t n) { return (n + 2 * KPAD - KS) / 2 + 1; }
 
+// What tspn_stem_conv_bf16 and tspn_stem_pool_bf16 share: the checks, the space-to-depth pass into the workspace, the
+// geometry and the CU count.  An empty batch returns TSPN_OK before a look at the operands, `f` unfilled: the entry returns too.
+struct StemFront {
+  int64_t OH, OW, SH, SW, tiles_w;
+  int cus;
+};
+int stem_front(const char* what, const float* x, int64_t NB, int64_t H, int64_t W, const uint16_t* frag, int64_t Cout,
+               const float* bias, void* workspace, size_t workspace_bytes, uint16_t* out, void* stream, StemFront* f) {
+  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0, TSPN_EINVAL, "%s: bad sizes", what);
+  TSPN_REQUIRE(Cout == 32 || Cout == 64, TSPN_EUNSUPPORTED, "%s: Cout must be 32 or 64 (got %lld)", what, (long long)Cout);
+  if (NB == 0) return TSPN_OK;
+  TSPN_REQUIRE(x && frag && bias && workspace && out, TSPN_EINVAL, "%s: null pointer", what);
+  const int64_t OH = out_dim(H), OW = out_dim(W), SH = OH + 3, SW = OW + 3;
+  TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20) && NB * SH * SW < (1LL << 40), TSPN_EUNSUPPORTED, "%s: image too large", what);
+  const size_t need = tspn_stem_bf16_workspace_bytes(NB, H, W);
+  TSPN_REQUIRE(workspace_bytes >= need, TSPN_EWORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+  TSPN_REQUIRE(tspn::all_aligned16(frag, bias, workspace, out), TSPN_EUNSUPPORTED, "%s: operands must be 16-byte aligned", what);
+  const int64_t npx = NB * SH * SW;
+  hipLaunchKernelGGL(stem_s2d_bf16_kernel, dim3((unsigned)std::min<int64_t>(tspn::ceil_div(npx, 256), 1 << 20)), dim3(256),
+                     0, TSPN_STREAM(stream), x, NB, (int)H, (int)W, (int)SH, (int)SW, static_cast<__bf16*>(workspace));
+  char s2d[64];
+  snprintf(s2d, sizeof(s2d), "%s (space-to-depth)", what);
+  if (int rc = tspn::check_launch(s2d)) return rc;
+  int dev = 0, cus = 256;
+  (void)hipGetDevice(&dev);
+  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
+  *f = {OH, OW, SH, SW, tspn::ceil_div(OW, TPX), cus};
+  return TSPN_OK;
+}
+
+// One launch per kernel; MB = Cout / 32.  The static LdsLimit is one per instantiation, i.e. per kernel instance.
+template <int MB>
+int stem_conv_launch(const char* what, const StemFront& f, int64_t NB, const uint16_t* frag, const float* bias,
+                     const void* S, uint16_t* out, void* stream) {
+  const int64_t ntiles = NB * f.OH * f.tiles_w;
+  const unsigned grid = (unsigned)std::min<int64_t>(ntiles, 2LL * f.cus);
+  const size_t smem = 2 * STAGE_BYTES + 4 * 32 * ((size_t)(32 * MB) + 4) * sizeof(float);
+  static tspn::LdsLimit lds;
+  if (int rc = lds.ensure(reinterpret_cast<const void*>(stem_conv_bf16_kernel<MB>), smem, what)) return rc;
+  hipLaunchKernelGGL(stem_conv_bf16_kernel<MB>, dim3(grid), dim3(256), smem, TSPN_STREAM(stream),
+                     static_cast<const __bf16*>(S), reinterpret_cast<const __bf16*>(frag), bias,
+                     reinterpret_cast<__bf16*>(out), (int)f.SH, (int)f.SW, (int)f.OH, (int)f.OW, (int)f.tiles_w, ntiles);
+  return tspn::check_launch(what);
+}
+template <int MB>
+int stem_pool_launch(const char* what, const StemFront& f, int64_t NB, const uint16_t* frag, const float* bias,
+                     const void* S, uint16_t* out, void* stream) {
+  const int64_t PH = (f.OH - 1) / 2 + 1, PW = (f.OW - 1) / 2 + 1, nrows = NB * PH;     // max_pool2d(3, 2, 1)
+  // whole pooled rows per workgroup, as evenly as the row count allows (1440 rows of 8 frames of 720p: 480 x 3)
+  const int64_t slots = 2LL * f.cus, per = tspn::ceil_div(nrows, slots);
+  const unsigned grid = (unsigned)tspn::ceil_div(nrows, per);
+  const size_t smem = 2 * PSTAGE_BYTES + (size_t)(1 + TPX) * ((size_t)(32 * MB) * 2 + 16);
+  static tspn::LdsLimit lds;
+  if (int rc = lds.ensure(reinterpret_cast<const void*>(stem_pool_bf16_kernel<MB>), smem, what)) return rc;
+  hipLaunchKernelGGL(stem_pool_bf16_kernel<MB>, dim3(grid), dim3(256), smem, TSPN_STREAM(stream),
+                     static_cast<const __bf16*>(S), reinterpret_cast<const __bf16*>(frag), bias,
+                     reinterpret_cast<__bf16*>(out), (int)f.SH, (int)f.SW, (int)f.OH, (int)f.OW, (int)PH, (int)PW,
+                     (int)f.tiles_w, nrows);
+  return tspn::check_launch(what);
+}
+
 }  // namespace
 
 extern "C" size_t tspn_stem_bf16_workspace_bytes(int64_t NB, int64_t H, int64_t W) {
@@ -403,101 +464,31 @@ extern "C" int tspn_pack_stem_bf16(const float* w, int64_t Cout, uint16_t* frag,
 extern "C" int tspn_stem_conv_bf16(const float* x, int64_t NB, int64_t H, int64_t W, const uint16_t* frag, int64_t Cout,
                                    const float* bias, void* workspace, size_t workspace_bytes, uint16_t* out,
                                    void* stream) {
-  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0, TSPN_EINVAL, "tspn_stem_conv_bf16: bad sizes");
-  TSPN_REQUIRE(Cout == 32 || Cout == 64, TSPN_EUNSUPPORTED, "tspn_stem_conv_bf16: Cout must be 32 or 64 (got %lld)",
-               (long long)Cout);
+  const char* what = "tspn_stem_conv_bf16";
+  StemFront f;
+  if (int rc = stem_front(what, x, NB, H, W, frag, Cout, bias, workspace, workspace_bytes, out, stream, &f)) return rc;
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(x && frag && bias && workspace && out, TSPN_EINVAL, "tspn_stem_conv_bf16: null pointer");
-  const int64_t OH = out_dim(H), OW = out_dim(W), SH = OH + 3, SW = OW + 3;
-  TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20) && NB * SH * SW < (1LL << 40), TSPN_EUNSUPPORTED,
-               "tspn_stem_conv_bf16: image too large");
-  const size_t need = tspn_stem_bf16_workspace_bytes(NB, H, W);
-  TSPN_REQUIRE(workspace_bytes >= need, TSPN_EWORKSPACE, "tspn_stem_conv_bf16: workspace %zu < %zu bytes", workspace_bytes,
-               need);
-  TSPN_REQUIRE(tspn::all_aligned16(frag, bias, workspace, out), TSPN_EUNSUPPORTED,
-               "tspn_stem_conv_bf16: operands must be 16-byte aligned");
-  __bf16* S = static_cast<__bf16*>(workspace);
-  hipStream_t s = TSPN_STREAM(stream);
-  const int64_t npx = NB * SH * SW;
-  hipLaunchKernelGGL(stem_s2d_bf16_kernel, dim3((unsigned)std::min<int64_t>(tspn::ceil_div(npx, 256), 1 << 20)), dim3(256),
-                     0, s, x, NB, (int)H, (int)W, (int)SH, (int)SW, S);
-  if (int rc = tspn::check_launch("tspn_stem_conv_bf16 (space-to-depth)")) return rc;
-  const int64_t tiles_w = tspn::ceil_div(OW, TPX), ntiles = NB * OH * tiles_w;
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  const unsigned grid = (unsigned)std::min<int64_t>(ntiles, 2LL * cus);
-  const __bf16* Wf = reinterpret_cast<const __bf16*>(frag);
-  __bf16* o = reinterpret_cast<__bf16*>(out);
-  const size_t smem = 2 * STAGE_BYTES + 4 * 32 * ((size_t)Cout + 4) * sizeof(float);
-  if (Cout == 64) {
-    static tspn::LdsLimit lds;
-    if (int rc = lds.ensure(reinterpret_cast<const void*>(stem_conv_bf16_kernel<2>), smem, "tspn_stem_conv_bf16")) return rc;
-    hipLaunchKernelGGL(stem_conv_bf16_kernel<2>, dim3(grid), dim3(256), smem, s, S, Wf, bias, o, (int)SH, (int)SW, (int)OH,
-                       (int)OW, (int)tiles_w, ntiles);
-  } else {
-    static tspn::LdsLimit lds;
-    if (int rc = lds.ensure(reinterpret_cast<const void*>(stem_conv_bf16_kernel<1>), smem, "tspn_stem_conv_bf16")) return rc;
-    hipLaunchKernelGGL(stem_conv_bf16_kernel<1>, dim3(grid), dim3(256), smem, s, S, Wf, bias, o, (int)SH, (int)SW, (int)OH,
-                       (int)OW, (int)tiles_w, ntiles);
-  }
-  return tspn::check_launch("tspn_stem_conv_bf16");
+  return Cout == 64 ? stem_conv_launch<2>(what, f, NB, frag, bias, workspace, out, stream)
+                    : stem_conv_launch<1>(what, f, NB, frag, bias, workspace, out, stream);
 }
 
 extern "C" int tspn_stem_pool_bf16(const float* x, int64_t NB, int64_t H, int64_t W, const uint16_t* frag, int64_t Cout,
                                    const float* bias, void* workspace, size_t workspace_bytes, uint16_t* out,
                                    void* stream) {
-  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0, TSPN_EINVAL, "tspn_stem_pool_bf16: bad sizes");
-  TSPN_REQUIRE(Cout == 32 || Cout == 64, TSPN_EUNSUPPORTED, "tspn_stem_pool_bf16: Cout must be 32 or 64 (got %lld)",
-               (long long)Cout);
+  const char* what = "tspn_stem_pool_bf16";
+  StemFront f;
+  if (int rc = stem_front(what, x, NB, H, W, frag, Cout, bias, workspace, workspace_bytes, out, stream, &f)) return rc;
   if (NB == 0) return TSPN_OK;
-  TSPN_REQUIRE(x && frag && bias && workspace && out, TSPN_EINVAL, "tspn_stem_pool_bf16: null pointer");
-  const int64_t OH = out_dim(H), OW = out_dim(W), SH = OH + 3, SW = OW + 3;
-  const int64_t PH = (OH - 1) / 2 + 1, PW = (OW - 1) / 2 + 1;     // max_pool2d(3, 2, 1)
-  TSPN_REQUIRE(H < (1 << 20) && W < (1 << 20) && NB * SH * SW < (1LL << 40), TSPN_EUNSUPPORTED,
-               "tspn_stem_pool_bf16: image too large");
-  const size_t need = tspn_stem_bf16_workspace_bytes(NB, H, W);
-  TSPN_REQUIRE(workspace_bytes >= need, TSPN_EWORKSPACE, "tspn_stem_pool_bf16: workspace %zu < %zu bytes", workspace_bytes,
-               need);
-  TSPN_REQUIRE(tspn::all_aligned16(frag, bias, workspace, out), TSPN_EUNSUPPORTED,
-               "tspn_stem_pool_bf16: operands must be 16-byte aligned");
-  __bf16* S = static_cast<__bf16*>(workspace);
-  hipStream_t s = TSPN_STREAM(stream);
-  const int64_t npx = NB * SH * SW;
-  hipLaunchKernelGGL(stem_s2d_bf16_kernel, dim3((unsigned)std::min<int64_t>(tspn::ceil_div(npx, 256), 1 << 20)), dim3(256),
-                     0, s, x, NB, (int)H, (int)W, (int)SH, (int)SW, S);
-  if (int rc = tspn::check_launch("tspn_stem_pool_bf16 (space-to-depth)")) return rc;
-  const int64_t tiles_w = tspn::ceil_div(OW, TPX), nrows = NB * PH;
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  // whole pooled rows per workgroup, as evenly as the row count allows (1440 rows of 8 frames of 720p: 480 x 3)
-  const int64_t slots = 2LL * cus, per = tspn::ceil_div(nrows, slots);
-  const unsigned grid = (unsigned)tspn::ceil_div(nrows, per);
-  const __bf16* Wf = reinterpret_cast<const __bf16*>(frag);
-  __bf16* o = reinterpret_cast<__bf16*>(out);
-  const size_t smem = 2 * PSTAGE_BYTES + (size_t)(1 + TPX) * ((size_t)Cout * 2 + 16);
-  if (Cout == 64) {
-    static tspn::LdsLimit lds;
-    if (int rc = lds.ensure(reinterpret_cast<const void*>(stem_pool_bf16_kernel<2>), smem, "tspn_stem_pool_bf16")) return rc;
-    hipLaunchKernelGGL(stem_pool_bf16_kernel<2>, dim3(grid), dim3(256), smem, s, S, Wf, bias, o, (int)SH, (int)SW, (int)OH,
-                       (int)OW, (int)PH, (int)PW, (int)tiles_w, nrows);
-  } else {
-    static tspn::LdsLimit lds;
-    if (int rc = lds.ensure(reinterpret_cast<const void*>(stem_pool_bf16_kernel<1>), smem, "tspn_stem_pool_bf16")) return rc;
-    hipLaunchKernelGGL(stem_pool_bf16_kernel<1>, dim3(grid), dim3(256), smem, s, S, Wf, bias, o, (int)SH, (int)SW, (int)OH,
-                       (int)OW, (int)PH, (int)PW, (int)tiles_w, nrows);
-  }
-  return tspn::check_launch("tspn_stem_pool_bf16");
+  return Cout == 64 ? stem_pool_launch<2>(what, f, NB, frag, bias, workspace, out, stream)
+                    : stem_pool_launch<1>(what, f, NB, frag, bias, workspace, out, stream);
 }
 
 extern "C" int tspn_max_pool_nhwc_bf16(const uint16_t* x, int64_t NB, int64_t H, int64_t W, int64_t C, int64_t k,
                                        int64_t stride, int64_t pad, uint16_t* out, void* stream) {
-  TSPN_REQUIRE(NB >= 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0 && 2 * pad <= k, TSPN_EINVAL,
-               "tspn_max_pool_nhwc_bf16: bad sizes");
-  // (a window larger than the padded map: the truncating division below would still give one output pixel)
-  TSPN_REQUIRE(H + 2 * pad >= k && W + 2 * pad >= k, TSPN_EINVAL, "tspn_max_pool_nhwc_bf16: empty output");
-  const int64_t OH = (H + 2 * pad - k) / stride + 1, OW = (W + 2 * pad - k) / stride + 1;
+  const bool sizes_ok = NB >= 0 && H > 0 && W > 0 && C > 0 && k > 0 && stride > 0 && pad >= 0 && 2 * pad <= k;
+  int64_t OH, OW;
+  if (int rc = tspn::window_shape_checks("tspn_max_pool_nhwc_bf16", sizes_ok, true, nullptr, H, W, k, k, stride, pad, &OH, &OW))
+    return rc;
   if (NB == 0) return TSPN_OK;
   TSPN_REQUIRE(x && out, TSPN_EINVAL, "tspn_max_pool_nhwc_bf16: null pointer");
   TSPN_REQUIRE(C % 8 == 0 && tspn::aligned16(x) && tspn::aligned16(out),

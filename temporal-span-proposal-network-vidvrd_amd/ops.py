@@ -164,6 +164,33 @@ def _ws(nbytes, device):
     return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
 
 
+def _workspace(workspace, need, device, who, sizes=False):
+    """The caller's `workspace` if it holds `need` bytes (`sizes`: the refusal names both numbers), or a new one from the
+    module's `_ws`, looked up at call time.  A buffer allocated here is not measured: whether it is large enough is the C
+    entry's TSPN_EWORKSPACE to say."""
+    if workspace is None:
+        return _ws(need, device)
+    if workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f"{who}: workspace too small" + (f" ({workspace.numel()} < {need})" if sizes else ""))
+    return workspace
+
+
+def _toggle(setter, value):
+    """Set a process-wide switch of the library (a tspn_*_set_* entry); returns the previous setting."""
+    prev = getattr(_abi.lib(), setter)(int(value))
+    if prev < 0:
+        _abi.check(prev)
+    return prev
+
+
+def _out_hw(who, H, W, KH, KW, stride, padding):
+    """(OH, OW) of a KH x KW window over an H x W map; an empty output is refused."""
+    OH, OW = (H + 2 * padding - KH) // stride + 1, (W + 2 * padding - KW) // stride + 1
+    if OH <= 0 or OW <= 0:
+        raise ValueError(f"{who}: empty output")
+    return OH, OW
+
+
 def predicate_head(x, weight, bias, apply_sigmoid=True, norm=None):
     """sigmoid(x @ W.T + b) — RelationPredictor.forward (reference lib/modeling/model.py:85-88).
 
@@ -463,10 +490,7 @@ def conv3_tc_wino63(x, frag, bias=None, relu=False, workspace=None):
         raise ValueError(f"conv3_tc_wino63: weights are for Cin={cin_w}, x has Cin={Cin}")
     l = _abi.lib()
     need = l.tspn_conv3_tc_wino63_workspace_bytes(B, T, Cin)
-    if workspace is None:
-        workspace = _ws(need, x.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise ValueError(f"conv3_tc_wino63: workspace too small ({workspace.numel()} < {need})")
+    workspace = _workspace(workspace, need, x.device, "conv3_tc_wino63", sizes=True)
     y = torch.empty((B, M, T), dtype=torch.float32, device=x.device)
     _abi.check(l.tspn_conv3_tc_wino63_f32(_p(x), B, T, Cin, _p(frag), M, _p(bias), 1 if relu else 0, _p(y),
                                           _p(workspace), workspace.numel() * workspace.element_size(), _stream()))
@@ -510,10 +534,7 @@ def conv3_tc_wino63_f16x3(x, packed, bias=None, relu=False, workspace=None):
         raise ValueError(f"conv3_tc_wino63_f16x3: weights are for Cin={cin_w}, x has Cin={Cin}")
     l = _abi.lib()
     need = l.tspn_conv3_tc_wino63_f16x3_workspace_bytes(B, T, Cin, M)
-    if workspace is None:
-        workspace = _ws(need, x.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise ValueError(f"conv3_tc_wino63_f16x3: workspace too small ({workspace.numel()} < {need})")
+    workspace = _workspace(workspace, need, x.device, "conv3_tc_wino63_f16x3", sizes=True)
     y = torch.empty((B, M, T), dtype=torch.float32, device=x.device)
     _abi.check(l.tspn_conv3_tc_wino63_f16x3(_p(x), B, T, Cin, _p(packed), M, _p(bias), 1 if relu else 0, _p(y),
                                             _p(workspace), workspace.numel() * workspace.element_size(), _stream()))
@@ -523,19 +544,13 @@ def conv3_tc_wino63_f16x3(x, packed, bias=None, relu=False, workspace=None):
 def wino63_set_piece_form(form):
     """0 = buffer-load pieces where the operands allow (default), 1 = 64-bit pointer pieces everywhere, for the fp32
     and the split-fp16 F(6,3) contraction (tspn_conv3_tc_wino63_set_piece_form).  Returns the previous setting."""
-    prev = _abi.lib().tspn_conv3_tc_wino63_set_piece_form(int(form))
-    if prev < 0:
-        _abi.check(prev)
-    return prev
+    return _toggle("tspn_conv3_tc_wino63_set_piece_form", form)
 
 
 def wino63_f16x3_set_tail_split(on):
     """1 = the split-fp16 contraction cuts the tiles of its last, partly filled round into sub-tiles (default), 0 = whole
     tiles only (tspn_conv3_tc_wino63_f16x3_set_tail_split); same outputs bit for bit.  Returns the previous setting."""
-    prev = _abi.lib().tspn_conv3_tc_wino63_f16x3_set_tail_split(int(on))
-    if prev < 0:
-        _abi.check(prev)
-    return prev
+    return _toggle("tspn_conv3_tc_wino63_f16x3_set_tail_split", on)
 
 
 def heads(a, head_w, head_b, b=None, ia=None, ib=None, bias=None, channels=None, num_pairs=None):
@@ -583,10 +598,7 @@ def heads_pairgrid_f16x3_split_bytes(C, H):
 def heads_pairgrid_f16x3_set_force_exact(on):
     """1 = every tile of the split-fp16 pair stage takes its fp32 chain (tests), 0 = default.  Process-wide; returns the
     previous setting."""
-    prev = _abi.lib().tspn_heads_pairgrid_f16x3_set_force_exact(int(on))
-    if prev < 0:
-        _abi.check(prev)
-    return prev
+    return _toggle("tspn_heads_pairgrid_f16x3_set_force_exact", on)
 
 
 def heads_pairgrid_f16x3(y, B, N, head_w, head_b, T=None, split_buf=None, out=None):
@@ -883,10 +895,7 @@ def forward_fused(feats, pairs, B, N, conv_packed, conv_bias, head_w, head_b, cl
         raise IndexError("forward_fused: pair index out of range")
     l = _abi.lib()
     need = l.tspn_forward_fused_workspace_bytes(ctypes.byref(d))
-    if workspace is None:
-        workspace = _ws(need, feats.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise ValueError(f"forward_fused: workspace too small ({workspace.numel()} < {need})")
+    workspace = _workspace(workspace, need, feats.device, "forward_fused", sizes=True)
     if out_heads is None:
         out_heads = torch.empty((P, 3 * d.A, T), dtype=torch.float32, device=feats.device)
     if out_logits is None:
@@ -1176,10 +1185,7 @@ def forward_fused_bf16(feats, pairs, B, N, conv_packed, conv_bias, head_packed, 
     l = _abi.lib()
     need = (l.tspn_forward_fused_bf16_workspace_bytes if canonical_pairs
             else l.tspn_forward_fused_bf16_pairs_workspace_bytes)(ctypes.byref(d))
-    if workspace is None:
-        workspace = _ws(need, feats.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise ValueError("forward_fused_bf16: workspace too small")
+    workspace = _workspace(workspace, need, feats.device, "forward_fused_bf16")
     if out_heads is None:
         out_heads = torch.empty((P, 3 * A, T), dtype=torch.float32, device=feats.device)
     elif tuple(out_heads.shape) != (P, 3 * A, T):
@@ -1199,6 +1205,17 @@ def forward_fused_bf16(feats, pairs, B, N, conv_packed, conv_bias, head_packed, 
     return out_heads, out_logits
 
 
+def _span_rows(who, NT, pairs, spans, classifier_ok=True):
+    """P of span_predicate / span_predicate_bf16: pairs and spans are [P,2] (one refusal with the fp32 wrapper's
+    classifier shape), and the host-synchronising range test of the tracklet ids."""
+    P = pairs.shape[0]
+    if not classifier_ok or tuple(pairs.shape) != (P, 2) or tuple(spans.shape) != (P, 2):
+        raise ValueError(f"{who}: shape mismatch")
+    if P and (int(pairs.min()) < 0 or int(pairs.max()) >= NT):
+        raise IndexError(f"{who}: pair index out of range")
+    return P
+
+
 def span_predicate(feats, pairs, spans, cls_w, cls_b):
     """Span-restricted RelOIPool + predicate head (tspn_span_predicate_f32): feats [NT,T,D], pairs [P,2]
     global tracklet ids, spans int64 [P,2] frames [start,end) -> sigmoid logits [P,K]."""
@@ -1208,17 +1225,63 @@ def span_predicate(feats, pairs, spans, cls_w, cls_b):
         _dev(cls_b, "cls_b")
     NT, T, D = feats.shape
     K = cls_w.shape[0]
-    P = pairs.shape[0]
-    if tuple(cls_w.shape) != (K, 2 * D) or tuple(pairs.shape) != (P, 2) or tuple(spans.shape) != (P, 2):
-        raise ValueError("span_predicate: shape mismatch")
-    if P and (int(pairs.min()) < 0 or int(pairs.max()) >= NT):
-        raise IndexError("span_predicate: pair index out of range")
+    P = _span_rows("span_predicate", NT, pairs, spans, tuple(cls_w.shape) == (K, 2 * D))
     l = _abi.lib()
     ws = _ws(l.tspn_span_predicate_workspace_bytes(NT, T, D, K), feats.device)
     out = torch.empty((P, K), dtype=torch.float32, device=feats.device)
     _abi.check(l.tspn_span_predicate_f32(_p(feats), NT, T, D, _p(pairs), _p(spans), P, _p(cls_w), _p(cls_b), K,
                                          _p(out), _p(ws), ws.numel(), _stream()))
     return out
+
+
+def _decode_span_relations(who, entry, ws_query, classifier, classifier_last, feats, pairs, spans, span_scores,
+                           span_counts, cls, cls_b, cls_logits, topk_per_span, topk_per_seg, check_pairs, out):
+    """decode_span_relations and decode_span_relations_bf16 behind their `_dev` lines: one body.  `entry`, `ws_query`: the
+    names of the C entry and of its workspace query; `classifier(D)` checks `cls` / `cls_b` and returns K, after the spans'
+    checks where `classifier_last` (the fp32 wrapper), before them otherwise."""
+    if pairs.dim() != 3 or pairs.shape[2] != 2 or cls_logits.dim() != 3 or cls_logits.shape[0] != pairs.shape[0]:
+        raise ValueError(f"{who}: pairs must be [S,P,2] and cls_logits [S,N,num_obj]")
+    S, P, _ = pairs.shape
+    N, NO = cls_logits.shape[1], cls_logits.shape[2]
+    if feats.dim() == 4:
+        feats = feats.view(-1, feats.shape[2], feats.shape[3])
+    if feats.dim() != 3 or feats.shape[0] != S * N:
+        raise ValueError(f"{who}: feats must hold S*N = {S * N} tracklets [S*N,T,D], got {tuple(feats.shape)}")
+    T, D = feats.shape[1], feats.shape[2]
+    if not classifier_last:
+        K = classifier(D)
+    if spans.dim() < 3 or spans.shape[-1] != 2:
+        raise ValueError(f"{who}: spans must be [S*P,J,2]")
+    J = spans.shape[-2]
+    if spans.numel() != S * P * J * 2 or span_scores.numel() != S * P * J or span_counts.numel() != S * P \
+            or (span_scores.numel() and span_scores.shape[-1] != J):
+        raise ValueError(f"{who}: spans [S*P,J,2], span_scores [S*P,J] and span_counts [S*P] expected for "
+                         f"S*P = {S * P}, J = {J}")
+    if classifier_last:
+        K = classifier(D)
+    if check_pairs and S * P and (int(pairs.min()) < 0 or int(pairs.max()) >= N):
+        raise IndexError(f"{who}: tracklet id outside the segment")
+    R = min(int(topk_per_span), K)
+    Mc = min(int(topk_per_seg), P * J * R)
+    dev = feats.device
+    shapes = (((S, Mc), torch.float32), ((S, Mc, 3), torch.int64), ((S, Mc, 2), torch.int64), ((S, Mc, 2), torch.int64),
+              ((S, Mc), torch.int64), ((S,), torch.int64))
+    if out is None:
+        out = tuple(torch.empty(sh, dtype=dt, device=dev) for sh, dt in shapes)
+        if S * P == 0:
+            out[5].zero_()                       # nothing is launched
+    else:
+        if len(out) != 6:
+            raise ValueError(f"{who}: out must be the six result tensors")
+        for t, (sh, dt), name in zip(out, shapes, ("scores", "triplets", "pair_tids", "spans", "span_rank", "valid")):
+            if tuple(_dev(t, "out." + name, dt).shape) != sh:
+                raise ValueError(f"{who}: out.{name} must be {sh}")
+    l = _abi.lib()
+    ws = _ws(getattr(l, ws_query)(S, N, T, D, P, J, K, int(topk_per_span)), dev)
+    _abi.check(getattr(l, entry)(_p(feats), S, N, T, D, _p(pairs), P, _p(spans), _p(span_scores), _p(span_counts), J,
+                                 _p(cls), _p(cls_b), K, _p(cls_logits), NO, int(topk_per_span), int(topk_per_seg),
+                                 *[_p(t) for t in out], _p(ws), ws.numel(), _stream()))
+    return tuple(out)
 
 
 def decode_span_relations(feats, pairs, spans, span_scores, span_counts, cls_w, cls_b, cls_logits, topk_per_span=20,
@@ -1238,49 +1301,16 @@ def decode_span_relations(feats, pairs, spans, span_scores, span_counts, cls_w, 
     _dev(cls_w, "cls_w"); _dev(cls_logits, "cls_logits")
     if cls_b is not None:
         _dev(cls_b, "cls_b")
-    if pairs.dim() != 3 or pairs.shape[2] != 2 or cls_logits.dim() != 3 or cls_logits.shape[0] != pairs.shape[0]:
-        raise ValueError("decode_span_relations: pairs must be [S,P,2] and cls_logits [S,N,num_obj]")
-    S, P, _ = pairs.shape
-    N, NO = cls_logits.shape[1], cls_logits.shape[2]
-    if feats.dim() == 4:
-        feats = feats.view(-1, feats.shape[2], feats.shape[3])
-    if feats.dim() != 3 or feats.shape[0] != S * N:
-        raise ValueError(f"decode_span_relations: feats must hold S*N = {S * N} tracklets [S*N,T,D], got {tuple(feats.shape)}")
-    T, D = feats.shape[1], feats.shape[2]
-    K = cls_w.shape[0]
-    if spans.dim() < 3 or spans.shape[-1] != 2:
-        raise ValueError("decode_span_relations: spans must be [S*P,J,2]")
-    J = spans.shape[-2]
-    if spans.numel() != S * P * J * 2 or span_scores.numel() != S * P * J or span_counts.numel() != S * P \
-            or (span_scores.numel() and span_scores.shape[-1] != J):
-        raise ValueError(f"decode_span_relations: spans [S*P,J,2], span_scores [S*P,J] and span_counts [S*P] expected for "
-                         f"S*P = {S * P}, J = {J}")
-    if tuple(cls_w.shape) != (K, 2 * D) or (cls_b is not None and tuple(cls_b.shape) != (K,)):
-        raise ValueError("decode_span_relations: cls_w must be [K,2D] and cls_b [K]")
-    if check_pairs and S * P and (int(pairs.min()) < 0 or int(pairs.max()) >= N):
-        raise IndexError("decode_span_relations: tracklet id outside the segment")
-    R = min(int(topk_per_span), K)
-    Mc = min(int(topk_per_seg), P * J * R)
-    dev = feats.device
-    shapes = (((S, Mc), torch.float32), ((S, Mc, 3), torch.int64), ((S, Mc, 2), torch.int64), ((S, Mc, 2), torch.int64),
-              ((S, Mc), torch.int64), ((S,), torch.int64))
-    if out is None:
-        out = tuple(torch.empty(sh, dtype=dt, device=dev) for sh, dt in shapes)
-        if S * P == 0:
-            out[5].zero_()                       # nothing is launched
-    else:
-        if len(out) != 6:
-            raise ValueError("decode_span_relations: out must be the six result tensors")
-        for t, (sh, dt), name in zip(out, shapes, ("scores", "triplets", "pair_tids", "spans", "span_rank", "valid")):
-            if tuple(_dev(t, "out." + name, dt).shape) != sh:
-                raise ValueError(f"decode_span_relations: out.{name} must be {sh}")
-    l = _abi.lib()
-    ws = _ws(l.tspn_decode_span_relations_workspace_bytes(S, N, T, D, P, J, K, int(topk_per_span)), dev)
-    _abi.check(l.tspn_decode_span_relations_f32(_p(feats), S, N, T, D, _p(pairs), P, _p(spans), _p(span_scores),
-                                                _p(span_counts), J, _p(cls_w), _p(cls_b), K, _p(cls_logits), NO,
-                                                int(topk_per_span), int(topk_per_seg), *[_p(t) for t in out],
-                                                _p(ws), ws.numel(), _stream()))
-    return tuple(out)
+
+    def classifier(D):
+        K = cls_w.shape[0]
+        if tuple(cls_w.shape) != (K, 2 * D) or (cls_b is not None and tuple(cls_b.shape) != (K,)):
+            raise ValueError("decode_span_relations: cls_w must be [K,2D] and cls_b [K]")
+        return K
+    return _decode_span_relations("decode_span_relations", "tspn_decode_span_relations_f32",
+                                  "tspn_decode_span_relations_workspace_bytes", classifier, True, feats, pairs, spans,
+                                  span_scores, span_counts, cls_w, cls_b, cls_logits, topk_per_span, topk_per_seg,
+                                  check_pairs, out)
 
 
 def pack_span_cls_bf16(cls_w):
@@ -1320,21 +1350,14 @@ def span_predicate_bf16(feats, pairs, spans, cls_packed, cls_b, K, out=None, wor
         raise ValueError("span_predicate_bf16: feats must be [NT,T,D]")
     NT, T, D = feats.shape
     K = _span_cls_packed(cls_packed, cls_b, K, D, "span_predicate_bf16")
-    P = pairs.shape[0]
-    if tuple(pairs.shape) != (P, 2) or tuple(spans.shape) != (P, 2):
-        raise ValueError("span_predicate_bf16: shape mismatch")
-    if P and (int(pairs.min()) < 0 or int(pairs.max()) >= NT):
-        raise IndexError("span_predicate_bf16: pair index out of range")
+    P = _span_rows("span_predicate_bf16", NT, pairs, spans)
     if out is None:
         out = torch.empty((P, K), dtype=torch.float32, device=feats.device)
     elif tuple(_dev(out, "out").shape) != (P, K):
         raise ValueError("span_predicate_bf16: out shape mismatch")
     l = _abi.lib()
     need = l.tspn_span_predicate_bf16_workspace_bytes(NT, T, D, K, P)
-    if workspace is None:
-        workspace = _ws(need, feats.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise ValueError("span_predicate_bf16: workspace too small")
+    workspace = _workspace(workspace, need, feats.device, "span_predicate_bf16")
     _abi.check(l.tspn_span_predicate_bf16(_p(feats), NT, T, D, _p(pairs), _p(spans), P, _p(cls_packed), _p(cls_b), K,
                                           _p(out), _p(workspace), workspace.numel() * workspace.element_size(), _stream()))
     return out
@@ -1346,49 +1369,14 @@ def decode_span_relations_bf16(feats, pairs, spans, span_scores, span_counts, cl
     [S*N,T,D]), cls_packed = pack_span_cls_bf16(cls_w [K,2D]), cls_b fp32 [K] or None; every other argument and the six
     results as decode_span_relations.  A candidate's predicate value is span_predicate_bf16's for that (pair, span) row,
     bit for bit."""
+    who = "decode_span_relations_bf16"
     _dev(feats, "feats", torch.bfloat16); _dev(pairs, "pairs", torch.int64); _dev(spans, "spans", torch.int64)
     _dev(span_scores, "span_scores"); _dev(span_counts, "span_counts", torch.int64); _dev(cls_logits, "cls_logits")
-    if pairs.dim() != 3 or pairs.shape[2] != 2 or cls_logits.dim() != 3 or cls_logits.shape[0] != pairs.shape[0]:
-        raise ValueError("decode_span_relations_bf16: pairs must be [S,P,2] and cls_logits [S,N,num_obj]")
-    S, P, _ = pairs.shape
-    N, NO = cls_logits.shape[1], cls_logits.shape[2]
-    if feats.dim() == 4:
-        feats = feats.view(-1, feats.shape[2], feats.shape[3])
-    if feats.dim() != 3 or feats.shape[0] != S * N:
-        raise ValueError(f"decode_span_relations_bf16: feats must hold S*N = {S * N} tracklets [S*N,T,D], got {tuple(feats.shape)}")
-    T, D = feats.shape[1], feats.shape[2]
-    K = _span_cls_packed(cls_packed, cls_b, K, D, "decode_span_relations_bf16")
-    if spans.dim() < 3 or spans.shape[-1] != 2:
-        raise ValueError("decode_span_relations_bf16: spans must be [S*P,J,2]")
-    J = spans.shape[-2]
-    if spans.numel() != S * P * J * 2 or span_scores.numel() != S * P * J or span_counts.numel() != S * P \
-            or (span_scores.numel() and span_scores.shape[-1] != J):
-        raise ValueError(f"decode_span_relations_bf16: spans [S*P,J,2], span_scores [S*P,J] and span_counts [S*P] expected "
-                         f"for S*P = {S * P}, J = {J}")
-    if check_pairs and S * P and (int(pairs.min()) < 0 or int(pairs.max()) >= N):
-        raise IndexError("decode_span_relations_bf16: tracklet id outside the segment")
-    R = min(int(topk_per_span), K)
-    Mc = min(int(topk_per_seg), P * J * R)
-    dev = feats.device
-    shapes = (((S, Mc), torch.float32), ((S, Mc, 3), torch.int64), ((S, Mc, 2), torch.int64), ((S, Mc, 2), torch.int64),
-              ((S, Mc), torch.int64), ((S,), torch.int64))
-    if out is None:
-        out = tuple(torch.empty(sh, dtype=dt, device=dev) for sh, dt in shapes)
-        if S * P == 0:
-            out[5].zero_()                       # nothing is launched
-    else:
-        if len(out) != 6:
-            raise ValueError("decode_span_relations_bf16: out must be the six result tensors")
-        for t, (sh, dt), name in zip(out, shapes, ("scores", "triplets", "pair_tids", "spans", "span_rank", "valid")):
-            if tuple(_dev(t, "out." + name, dt).shape) != sh:
-                raise ValueError(f"decode_span_relations_bf16: out.{name} must be {sh}")
-    l = _abi.lib()
-    ws = _ws(l.tspn_decode_span_relations_bf16_workspace_bytes(S, N, T, D, P, J, K, int(topk_per_span)), dev)
-    _abi.check(l.tspn_decode_span_relations_bf16(_p(feats), S, N, T, D, _p(pairs), P, _p(spans), _p(span_scores),
-                                                 _p(span_counts), J, _p(cls_packed), _p(cls_b), K, _p(cls_logits), NO,
-                                                 int(topk_per_span), int(topk_per_seg), *[_p(t) for t in out],
-                                                 _p(ws), ws.numel(), _stream()))
-    return tuple(out)
+    return _decode_span_relations(who, "tspn_decode_span_relations_bf16",
+                                  "tspn_decode_span_relations_bf16_workspace_bytes",
+                                  lambda D: _span_cls_packed(cls_packed, cls_b, K, D, who), False, feats, pairs, spans,
+                                  span_scores, span_counts, cls_packed, cls_b, cls_logits, topk_per_span, topk_per_seg,
+                                  check_pairs, out)
 
 
 # --------------------------------------------------------------------------- #
@@ -1419,6 +1407,19 @@ def pack_conv2d_frag(weight):
     return frag
 
 
+def _bias_residual(who, bias, residual, out_shape, dtype):
+    """The optional epilogue operands of conv2d_nhwc / conv2d_nhwc_bf16: bias fp32 [Cout], residual `dtype` of the output's
+    shape."""
+    if bias is not None:
+        _dev(bias, "bias")
+        if bias.shape != (out_shape[3],):
+            raise ValueError(f"{who}: bias shape mismatch")
+    if residual is not None:
+        _dev(residual, "residual", dtype)
+        if tuple(residual.shape) != tuple(out_shape):
+            raise ValueError(f"{who}: residual shape mismatch")
+
+
 def conv2d_nhwc(x, packed, kernel_size, stride=1, padding=0, bias=None, residual=None, relu=False):
     """act(conv2d(x) + bias + residual) on channels-last tensors: x [NB,H,W,Cin] -> [NB,OH,OW,Cout];
     `packed` = pack_conv2d(weight) or pack_conv2d_frag(weight) (5-D: fast kernel), kernel_size = (KH, KW)."""
@@ -1435,17 +1436,8 @@ def conv2d_nhwc(x, packed, kernel_size, stride=1, padding=0, bias=None, residual
         if packed.dim() != 3 or packed.shape[0] != KH * KW or packed.shape[1] != Cin:
             raise ValueError(f"conv2d_nhwc: packed weights {tuple(packed.shape)} do not match taps={KH * KW}, Cin={Cin}")
         Cout = packed.shape[2]
-    OH, OW = (H + 2 * padding - KH) // stride + 1, (W + 2 * padding - KW) // stride + 1
-    if OH <= 0 or OW <= 0:
-        raise ValueError("conv2d_nhwc: empty output")
-    if bias is not None:
-        _dev(bias, "bias")
-        if bias.shape != (Cout,):
-            raise ValueError("conv2d_nhwc: bias shape mismatch")
-    if residual is not None:
-        _dev(residual, "residual")
-        if tuple(residual.shape) != (NB, OH, OW, Cout):
-            raise ValueError("conv2d_nhwc: residual shape mismatch")
+    OH, OW = _out_hw("conv2d_nhwc", H, W, KH, KW, stride, padding)
+    _bias_residual("conv2d_nhwc", bias, residual, (NB, OH, OW, Cout), torch.float32)
     out = torch.empty((NB, OH, OW, Cout), dtype=torch.float32, device=x.device)
     fn = _abi.lib().tspn_conv2d_nhwc_frag_f32 if frag else _abi.lib().tspn_conv2d_nhwc_f32
     _abi.check(fn(_p(x), NB, H, W, Cin, _p(packed), Cout, KH, KW, stride, padding,
@@ -1516,17 +1508,8 @@ def conv2d_nhwc_bf16(x, frag, kernel_size, stride=1, padding=0, bias=None, resid
     if frag.dim() != 6 or tuple(frag.shape[1:]) != _frag_shape_bf16(32, Cin, KH * KW)[1:] or Cin % 64:
         raise ValueError(f"conv2d_nhwc_bf16: weights {tuple(frag.shape)} do not match taps={KH * KW}, Cin={Cin}")
     Cout = frag.shape[0] * 32
-    OH, OW = (H + 2 * padding - KH) // stride + 1, (W + 2 * padding - KW) // stride + 1
-    if OH <= 0 or OW <= 0:
-        raise ValueError("conv2d_nhwc_bf16: empty output")
-    if bias is not None:
-        _dev(bias, "bias")
-        if bias.shape != (Cout,):
-            raise ValueError("conv2d_nhwc_bf16: bias shape mismatch")
-    if residual is not None:
-        _dev(residual, "residual", torch.bfloat16)
-        if tuple(residual.shape) != (NB, OH, OW, Cout):
-            raise ValueError("conv2d_nhwc_bf16: residual shape mismatch")
+    OH, OW = _out_hw("conv2d_nhwc_bf16", H, W, KH, KW, stride, padding)
+    _bias_residual("conv2d_nhwc_bf16", bias, residual, (NB, OH, OW, Cout), torch.bfloat16)
     out = torch.empty((NB, OH, OW, Cout), dtype=torch.bfloat16, device=x.device)
     _abi.check(_abi.lib().tspn_conv2d_nhwc_bf16(_p(x), NB, H, W, Cin, _p(frag), Cout, KH, KW, stride, padding,
                                                 _p(bias), _p(residual), 1 if relu else 0, _p(out), _stream()))
@@ -1537,13 +1520,30 @@ def max_pool_nhwc(x, kernel_size=3, stride=2, padding=1, out_bf16=False):
     """max_pool2d on a channels-last fp32 map [NB,H,W,C] -> [NB,OH,OW,C] (fp32, or bf16 rounded once)."""
     _dev(x, "x")
     NB, H, W, C = x.shape
-    OH, OW = (H + 2 * padding - kernel_size) // stride + 1, (W + 2 * padding - kernel_size) // stride + 1
-    if OH <= 0 or OW <= 0:
-        raise ValueError("max_pool_nhwc: empty output")
+    OH, OW = _out_hw("max_pool_nhwc", H, W, kernel_size, kernel_size, stride, padding)
     out = torch.empty((NB, OH, OW, C), dtype=torch.bfloat16 if out_bf16 else torch.float32, device=x.device)
     _abi.check(_abi.lib().tspn_max_pool_nhwc_f32(_p(x), NB, H, W, C, kernel_size, stride, padding, _p(out),
                                                  1 if out_bf16 else 0, _stream()))
     return out
+
+
+def _block_operands(x, frags, biases, residual=None):
+    """The operand check of the three bottleneck_block*_bf16 wrappers: x (and a residual) bf16, frag1 .. frag3 (and frags)
+    bf16, their biases fp32, all contiguous device tensors."""
+    _dev(x, "x", torch.bfloat16)
+    if residual is not None:
+        _dev(residual, "residual", torch.bfloat16)
+    for nm, t in zip(("frag1", "frag2", "frag3", "frags"), frags):
+        _dev(t, nm, torch.bfloat16)
+    for nm, t in zip(("bias1", "bias2", "bias3", "biass"), biases):
+        _dev(t, nm)
+
+
+def _block_frags_match(frags, CIN, CM):
+    """frag1 .. frag3 (and frags) are pack_conv2d_frag_bf16 of [CM,CIN,1,1] / [CM,CM,3,3] / [4CM,CM,1,1] (/ [4CM,CIN,1,1])."""
+    want = (_frag_shape_bf16(CM, CIN, 1), _frag_shape_bf16(CM, CM, 9), _frag_shape_bf16(4 * CM, CM, 1),
+            _frag_shape_bf16(4 * CM, CIN, 1))
+    return all(tuple(f.shape) == w for f, w in zip(frags, want))
 
 
 def bottleneck_block_bf16(x, frag1, bias1, frag2, bias2, frag3, bias3, out=None):
@@ -1551,16 +1551,12 @@ def bottleneck_block_bf16(x, frag1, bias1, frag2, bias2, frag3, bias3, out=None)
     relu(conv1x1(relu(conv3x3(relu(conv1x1(x) + b1)) + b2)) + b3 + x) for x bf16 [NB,H,W,4 CM], CM in (64, 128);
     frag1 / frag2 / frag3 = pack_conv2d_frag_bf16 of the folded conv1 [CM,4CM,1,1], conv2 [CM,CM,3,3], conv3 [4CM,CM,1,1].
     Bit-identical to conv2d_nhwc_bf16 (conv1) + bottleneck_tail_bf16; the 4 CM-channel map is read once."""
-    _dev(x, "x", torch.bfloat16)
-    for nm, t in (("frag1", frag1), ("frag2", frag2), ("frag3", frag3)):
-        _dev(t, nm, torch.bfloat16)
-    _dev(bias1, "bias1"); _dev(bias2, "bias2"); _dev(bias3, "bias3")
+    _block_operands(x, (frag1, frag2, frag3), (bias1, bias2, bias3))
     NB, H, W, C4 = x.shape
     CM = C4 // 4
     if CM not in (64, 128) or C4 != 4 * CM:
         raise ValueError(f"bottleneck_block_bf16: needs 4 x 64 or 4 x 128 channels (got {C4})")
-    if (tuple(frag1.shape) != _frag_shape_bf16(CM, C4, 1) or tuple(frag2.shape) != _frag_shape_bf16(CM, CM, 9)
-            or tuple(frag3.shape) != _frag_shape_bf16(C4, CM, 1)):
+    if not _block_frags_match((frag1, frag2, frag3), C4, CM):
         raise ValueError("bottleneck_block_bf16: frag1 / frag2 / frag3 must be pack_conv2d_frag_bf16 of [CM,4CM,1,1] / "
                          "[CM,CM,3,3] / [4CM,CM,1,1]")
     if bias1.shape != (CM,) or bias2.shape != (CM,) or bias3.shape != (C4,):
@@ -1576,17 +1572,12 @@ def bottleneck_block_proj_bf16(x, stride, frag1, bias1, frag2, bias2, frag3, bia
     1x1 convs of stride `stride` on x bf16 [NB,Hin,Win,CIN]; frags / biass = the folded shortcut [4CM,CIN,1,1].  Built for
     (CIN, CM, stride) = (64, 64, 1), detectron2's res2.0.  Bit-identical to conv1 + shortcut + fused tail; the shortcut map
     never goes to memory."""
-    _dev(x, "x", torch.bfloat16)
-    for nm, t in (("frag1", frag1), ("frag2", frag2), ("frag3", frag3), ("frags", frags)):
-        _dev(t, nm, torch.bfloat16)
-    for nm, t in (("bias1", bias1), ("bias2", bias2), ("bias3", bias3), ("biass", biass)):
-        _dev(t, nm)
+    _block_operands(x, (frag1, frag2, frag3, frags), (bias1, bias2, bias3, biass))
     NB, Hin, Win, CIN = x.shape
     CM = frag2.shape[0] * 32
     if (CIN, CM, int(stride)) != (64, 64, 1):
         raise ValueError(f"bottleneck_block_proj_bf16: built for (CIN, CM, stride) = (64, 64, 1), got {(CIN, CM, stride)}")
-    if (tuple(frag1.shape) != _frag_shape_bf16(CM, CIN, 1) or tuple(frag2.shape) != _frag_shape_bf16(CM, CM, 9)
-            or tuple(frag3.shape) != _frag_shape_bf16(4 * CM, CM, 1) or tuple(frags.shape) != _frag_shape_bf16(4 * CM, CIN, 1)):
+    if not _block_frags_match((frag1, frag2, frag3, frags), CIN, CM):
         raise ValueError("bottleneck_block_proj_bf16: fragment shapes do not match [CM,CIN,1,1] / [CM,CM,3,3] / [4CM,CM,1,1] / [4CM,CIN,1,1]")
     if bias1.shape != (CM,) or bias2.shape != (CM,) or bias3.shape != (4 * CM,) or biass.shape != (4 * CM,):
         raise ValueError("bottleneck_block_proj_bf16: bias shape mismatch")
@@ -1602,17 +1593,12 @@ def bottleneck_block_res_bf16(x, stride, frag1, bias1, frag2, bias2, frag3, bias
     """conv1 (1x1, stride `stride`) + 3x3 + expand + `residual` + ReLU in one launch (tspn_bottleneck_block_res_bf16): x bf16
     [NB,Hin,Win,CIN], residual bf16 [NB,H,W,4CM] (e.g. the separately launched projection shortcut).  Built for res3.0:
     (CIN, CM, stride) = (256, 128, 2).  Bit-identical to conv1 + bottleneck_tail_bf16."""
-    _dev(x, "x", torch.bfloat16); _dev(residual, "residual", torch.bfloat16)
-    for nm, t in (("frag1", frag1), ("frag2", frag2), ("frag3", frag3)):
-        _dev(t, nm, torch.bfloat16)
-    for nm, t in (("bias1", bias1), ("bias2", bias2), ("bias3", bias3)):
-        _dev(t, nm)
+    _block_operands(x, (frag1, frag2, frag3), (bias1, bias2, bias3), residual)
     NB, Hin, Win, CIN = x.shape
     CM = frag2.shape[0] * 32
     if (CIN, CM, int(stride)) != (256, 128, 2):
         raise ValueError(f"bottleneck_block_res_bf16: built for (CIN, CM, stride) = (256, 128, 2), got {(CIN, CM, stride)}")
-    if (tuple(frag1.shape) != _frag_shape_bf16(CM, CIN, 1) or tuple(frag2.shape) != _frag_shape_bf16(CM, CM, 9)
-            or tuple(frag3.shape) != _frag_shape_bf16(4 * CM, CM, 1)):
+    if not _block_frags_match((frag1, frag2, frag3), CIN, CM):
         raise ValueError("bottleneck_block_res_bf16: fragment shapes do not match [CM,CIN,1,1] / [CM,CM,3,3] / [4CM,CM,1,1]")
     H, W = (Hin - 1) // stride + 1, (Win - 1) // stride + 1
     if bias1.shape != (CM,) or bias2.shape != (CM,) or bias3.shape != (4 * CM,) or tuple(residual.shape) != (NB, H, W, 4 * CM):
@@ -1680,9 +1666,7 @@ def max_pool_nhwc_bf16(x, kernel_size=3, stride=2, padding=1):
     """max_pool2d on a channels-last bf16 map [NB,H,W,C] -> bf16 [NB,OH,OW,C] (tspn_max_pool_nhwc_bf16; C % 8 == 0)."""
     _dev(x, "x", torch.bfloat16)
     NB, H, W, C = x.shape
-    OH, OW = (H + 2 * padding - kernel_size) // stride + 1, (W + 2 * padding - kernel_size) // stride + 1
-    if OH <= 0 or OW <= 0:
-        raise ValueError("max_pool_nhwc_bf16: empty output")
+    OH, OW = _out_hw("max_pool_nhwc_bf16", H, W, kernel_size, kernel_size, stride, padding)
     out = torch.empty((NB, OH, OW, C), dtype=torch.bfloat16, device=x.device)
     _abi.check(_abi.lib().tspn_max_pool_nhwc_bf16(_p(x), NB, H, W, C, kernel_size, stride, padding, _p(out), _stream()))
     return out
@@ -1699,51 +1683,37 @@ def pack_stem_bf16(weight):
     return frag
 
 
-def stem_conv_bf16(x, frag, bias, workspace=None):
-    """relu(conv7x7/2/pad3(x) + bias) with bf16 operands: x fp32 [NB,H,W,3] -> bf16 [NB,OH,OW,Cout]
-    (tspn_stem_conv_bf16; `workspace` >= tspn_stem_bf16_workspace_bytes holds the space-to-depth image)."""
+def _stem_bf16(who, pooled, x, frag, bias, workspace):
+    """stem_conv_bf16 and, `pooled`, stem_pool_bf16: one body, the entry tspn_<who> and the output's size apart."""
     _dev(x, "x"); _dev(frag, "frag", torch.bfloat16); _dev(bias, "bias")
     if x.dim() != 4 or x.shape[3] != 3 or frag.dim() != 4 or tuple(frag.shape[1:]) != (16, 64, 8):
-        raise ValueError("stem_conv_bf16: x must be [NB,H,W,3] and frag = pack_stem_bf16(weight)")
+        raise ValueError(f"{who}: x must be [NB,H,W,3] and frag = pack_stem_bf16(weight)")
     NB, H, W, _ = x.shape
     Cout = frag.shape[0] * 32
     if bias.shape != (Cout,):
-        raise ValueError("stem_conv_bf16: bias shape mismatch")
+        raise ValueError(f"{who}: bias shape mismatch")
     OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+    if pooled:
+        OH, OW = (OH - 1) // 2 + 1, (OW - 1) // 2 + 1
     l = _abi.lib()
-    need = l.tspn_stem_bf16_workspace_bytes(NB, H, W)
-    if workspace is None:
-        workspace = _ws(need, x.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise ValueError("stem_conv_bf16: workspace too small")
+    workspace = _workspace(workspace, l.tspn_stem_bf16_workspace_bytes(NB, H, W), x.device, who)
     out = torch.empty((NB, OH, OW, Cout), dtype=torch.bfloat16, device=x.device)
-    _abi.check(l.tspn_stem_conv_bf16(_p(x), NB, H, W, _p(frag), Cout, _p(bias), _p(workspace),
-                                     workspace.numel() * workspace.element_size(), _p(out), _stream()))
+    _abi.check(getattr(l, "tspn_" + who)(_p(x), NB, H, W, _p(frag), Cout, _p(bias), _p(workspace),
+                                         workspace.numel() * workspace.element_size(), _p(out), _stream()))
     return out
+
+
+def stem_conv_bf16(x, frag, bias, workspace=None):
+    """relu(conv7x7/2/pad3(x) + bias) with bf16 operands: x fp32 [NB,H,W,3] -> bf16 [NB,OH,OW,Cout]
+    (tspn_stem_conv_bf16; `workspace` >= tspn_stem_bf16_workspace_bytes holds the space-to-depth image)."""
+    return _stem_bf16("stem_conv_bf16", False, x, frag, bias, workspace)
 
 
 def stem_pool_bf16(x, frag, bias, workspace=None):
     """BasicStem.forward on bf16 operands in one conv launch: max_pool2d(relu(conv7x7/2/pad3(x) + bias), 3, 2, 1),
     x fp32 [NB,H,W,3] -> bf16 [NB,PH,PW,Cout] (tspn_stem_pool_bf16); bit-identical to
     max_pool_nhwc_bf16(stem_conv_bf16(x, frag, bias), 3, 2, 1) without writing the conv map."""
-    _dev(x, "x"); _dev(frag, "frag", torch.bfloat16); _dev(bias, "bias")
-    if x.dim() != 4 or x.shape[3] != 3 or frag.dim() != 4 or tuple(frag.shape[1:]) != (16, 64, 8):
-        raise ValueError("stem_pool_bf16: x must be [NB,H,W,3] and frag = pack_stem_bf16(weight)")
-    NB, H, W, _ = x.shape
-    Cout = frag.shape[0] * 32
-    if bias.shape != (Cout,):
-        raise ValueError("stem_pool_bf16: bias shape mismatch")
-    OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
-    l = _abi.lib()
-    need = l.tspn_stem_bf16_workspace_bytes(NB, H, W)
-    if workspace is None:
-        workspace = _ws(need, x.device)
-    elif workspace.numel() * workspace.element_size() < need:
-        raise ValueError("stem_pool_bf16: workspace too small")
-    out = torch.empty((NB, (OH - 1) // 2 + 1, (OW - 1) // 2 + 1, Cout), dtype=torch.bfloat16, device=x.device)
-    _abi.check(l.tspn_stem_pool_bf16(_p(x), NB, H, W, _p(frag), Cout, _p(bias), _p(workspace),
-                                     workspace.numel() * workspace.element_size(), _p(out), _stream()))
-    return out
+    return _stem_bf16("stem_pool_bf16", True, x, frag, bias, workspace)
 
 
 def pack_conv2d_frag_cin4(weight):
@@ -1765,9 +1735,7 @@ def conv2d_nhwc_cin4(x, frag, kernel_size, stride=1, padding=0, bias=None, relu=
     if C4 != 4 or frag.dim() != 4 or tuple(frag.shape[1:]) != ((KH * KW + 3) // 4, 64, 8):
         raise ValueError("conv2d_nhwc_cin4: x must be [NB,H,W,4] and frag = pack_conv2d_frag_cin4(weight)")
     Cout = frag.shape[0] * 32
-    OH, OW = (H + 2 * padding - KH) // stride + 1, (W + 2 * padding - KW) // stride + 1
-    if OH <= 0 or OW <= 0:
-        raise ValueError("conv2d_nhwc_cin4: empty output")
+    OH, OW = _out_hw("conv2d_nhwc_cin4", H, W, KH, KW, stride, padding)
     if bias is not None:
         _dev(bias, "bias")
     out = torch.empty((NB, OH, OW, Cout), dtype=torch.float32, device=x.device)
