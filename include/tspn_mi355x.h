@@ -949,6 +949,35 @@ int64_t tspn_span_anchor_sample_partials(int64_t n);
 int tspn_span_anchor_sample(const int8_t* label, int64_t n, uint64_t stream_key, int key_bits, int64_t batch,
                             int64_t want_pos, uint32_t* partials, int64_t* counts, uint8_t* mask, void* stream);
 
+/* ---- training targets from ground-truth relation instances (csrc/pairlabels/tspn_pair_labels.hip) -----------------
+ * Build-defined (DESIGN.md 2 "pair labels"): the intent of VRDataset._get_proposals_rel_feature (lib/dataset/
+ * vrdataset.py:85-138, whose statements cannot run once a pair is positive), for a batch of S segments stored back to
+ * back as tspn_proposal_pair_filter_i64 takes them, plus the ground-truth spans of every pair.
+ *   pairs int64 [P, 2] (any pair table: track indices local to the segment), trackid int64 [M] (< 0 proposal, >= 0 the
+ *   ground-truth track id), iou fp32 (segment s: [M_s, M_s] row-major from element iou_off[s] on), insts int64 [R, 5] =
+ *   (sub_tid, obj_tid, pred, begin, end) with [begin, end) in video frames (read only when G > 0), seg_frames int64
+ *   [S, 2] = (fstart, fend) per segment (read only when G > 0).  pair_off / track_off / iou_off / inst_off int64 [S + 1]
+ *   on the device; all four NULL with S == 1 is the single-segment form (P, M, R its sizes; otherwise the totals).
+ *   col(tid) = the largest j with trackid[j] == tid >= 0; an instance is live when both columns exist and
+ *   0 <= pred < K.  A live instance covers pair (s, o) iff s != o, both in [0, M), trackid[s] < 0, trackid[o] < 0,
+ *   iou[s, col(sub_tid)] >= thr and iou[o, col(obj_tid)] >= thr with thr = (float)iou_thres, compared in fp32.
+ *   labels fp32 [P, K]: merge 0 ("last") the one-hot of pred of the covering instance of the largest r; merge 1 ("or")
+ *   the pred of every covering instance; zero where nothing covers.
+ *   spans int64 [P, G, 2], span_count int32 [P]: for the covering instances in ascending r the span
+ *   [max(begin, fstart) - fstart, min(end, fend) - fstart), skipped when empty or already stored for the pair; unused
+ *   rows (0, 0); span_count = the distinct spans, G + 1 when more than G were found (the excess is dropped), -1 for a
+ *   pair naming a track outside [0, M) (labels zero, rows padding).  G == 0 with NULL spans / span_count: labels only.
+ *   inst_cols int32 [R, 2], an output: the resolved columns, -1 for a missing one, (-2, -2) for pred outside [0, K).
+ * Two launches (resolve, label), no host synchronisation, atomic, memset or scratch; every output element is written
+ * exactly once.  Limits: 1 <= K <= 512, 0 <= G <= 16, S, P, M, R < 2^31, iou_thres finite.  P == 0 and R == 0 (and
+ * S == 0) launch nothing; an operand without elements may be NULL.  The offsets are trusted; pair indices, instance
+ * ids and predicates are checked on the device. */
+int tspn_pair_labels_f32(const int64_t* pairs, const int64_t* pair_off, const int64_t* trackid,
+                         const int64_t* track_off, const float* iou, const int64_t* iou_off, const int64_t* insts,
+                         const int64_t* inst_off, const int64_t* seg_frames, int64_t S, int64_t P, int64_t M, int64_t R,
+                         int64_t K, int64_t G, double iou_thres, int merge, float* labels, int64_t* spans,
+                         int32_t* span_count, int32_t* inst_cols, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,7 +13,14 @@ What the reference does on the host per segment, and where it runs here:
     num_tracks = sum(trackid < 0)                           -> same kernel
     feats = _feature_preprocess(feats)                      -> tspn_feature_preprocess_f32 (in place), or
                                                                left RAW for PREDICT.FUSE_PREPROCESS
-The label construction (vrdataset.py:85-138) stays outside this build (dataset I/O is out of scope).
+    pred_labels = _get_proposals_rel_feature(...)           -> tspn_pair_labels_f32 on the kept pair table
+                                                               (`gt_rel_insts=`; DESIGN.md §2 "pair labels": the
+                                                               reference's statements, vrdataset.py:85-138, cannot run
+                                                               once a pair is positive, so their intent is frozen there),
+                                                               with the ground-truth spans of every pair as the
+                                                               'spans' target of the span heads
+The per-segment instance lists of `VRDataset.__init__` (vrdataset.py:26-55) come from `segment_relation_instances`
+(host, numpy); annotation and file parsing stay outside this build (dataset I/O is out of scope).
 
 On-disk side (the formats a feature-extraction front end has to honour): the small helpers
 at the end of this file read and write the two per-segment files the reference's dataset opens —
@@ -32,7 +39,8 @@ import torch
 from . import ops
 from .pair_list import PairList, TargetList
 
-__all__ = ["DevicePrefetcher", "proposal_pair_list", "proposal_pair_lists", "select_proposal_pairs", "segment_signature", "feature_path",
+__all__ = ["DevicePrefetcher", "proposal_pair_list", "proposal_pair_lists", "select_proposal_pairs", "segment_video",
+           "segment_relation_instances", "segment_signature", "feature_path",
            "write_traj_cls_json", "read_traj_cls_json", "tracklets_to_traj_cls", "write_relation_h5",
            "read_relation_h5"]
 
@@ -52,12 +60,19 @@ def select_proposal_pairs(pairs, trackid, device=None):
 
 
 def proposal_pair_list(pairs, feats, iou, trackid, cls_logits, pred_labels=None, preprocess=True,
-                       device=None):
+                       device=None, gt_rel_insts=None, segment=None, max_spans=0, iou_thres=0.5, merge="last",
+                       num_predicates=132):
     """One segment's (PairList, TargetList | None) as `VRDataset.__getitem__` builds them
     (vrdataset.py:64-83), resident on the HIP device.
 
     `preprocess=False` leaves the kept feature rows RAW for a model built with
-    PREDICT.FUSE_PREPROCESS (the block-L1 normalisation then runs inside the predicate GEMM)."""
+    PREDICT.FUSE_PREPROCESS (the block-L1 normalisation then runs inside the predicate GEMM).
+
+    Labels: `pred_labels` [P,K] computed by the caller, or `gt_rel_insts`, the segment's ground-truth relation instances
+    int64 [R,3] = (sub_tid, obj_tid, pred), labelled on the device (`ops.pair_labels` on the kept pair table, `iou_thres`,
+    `merge`, K = `num_predicates`; DESIGN.md §2 "pair labels").  [R,5] = (.., begin, end) with `segment=(fstart, fend)` and
+    `max_spans=G` also gives the TargetList the fields 'spans' int64 [P',G,2] (the target of the span heads) and
+    'span_count' int32 [P']."""
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     p_all = _to_dev(pairs, device, torch.int64).reshape(-1, 2)
     f_all = _to_dev(feats, device, torch.float32)
@@ -65,8 +80,44 @@ def proposal_pair_list(pairs, feats, iou, trackid, cls_logits, pred_labels=None,
         raise ValueError(f"feats must be [P,F] with one row per pair (pairs {tuple(p_all.shape)}, "
                          f"feats {tuple(f_all.shape)})")
     tid = _to_dev(trackid, device, torch.int64).reshape(-1)
+    insts, frames = _relation_instances(gt_rel_insts, segment, max_spans, pred_labels)
     idx, num_tracks = ops.proposal_pair_filter(p_all, tid)
-    return _assemble(p_all, f_all, idx, num_tracks, iou, trackid, cls_logits, pred_labels, preprocess, device)
+    plist, tlist = _assemble(p_all, f_all, idx, num_tracks, iou, trackid, cls_logits, pred_labels, preprocess, device)
+    if insts is not None:
+        iou_dev = _to_dev(iou, device, torch.float32)
+        out = ops.pair_labels(plist.get_field("tracklet_pairs"), tid, iou_dev, torch.from_numpy(insts).to(device),
+                              num_predicates, iou_thres, merge, max_spans,
+                              torch.from_numpy(frames).to(device) if max_spans else None)
+        tlist = _label_targets(out[0], out[1], out[2])
+    return plist, tlist
+
+
+def _relation_instances(gt_rel_insts, segment, max_spans, pred_labels):
+    """(int64 [R,5] host array, int64 [1,2] (fstart, fend)) of a `gt_rel_insts` argument, or (None, None) without one.
+    [R,3] rows get an empty duration; spans (`max_spans` > 0) need [R,5] rows and the segment's frames."""
+    if gt_rel_insts is None:
+        return None, None
+    if pred_labels is not None:
+        raise ValueError("give either pred_labels or gt_rel_insts, not both")
+    a = np.asarray(gt_rel_insts.cpu() if isinstance(gt_rel_insts, torch.Tensor) else gt_rel_insts, dtype=np.int64)
+    a = a.reshape(-1, a.shape[-1] if a.ndim == 2 else (5 if max_spans else 3))
+    if a.shape[1] not in (3, 5):
+        raise ValueError(f"gt_rel_insts must be [R,3] or [R,5], got {a.shape}")
+    if max_spans and (a.shape[1] != 5 or segment is None):
+        raise ValueError("max_spans > 0 needs gt_rel_insts [R,5] = (sub_tid, obj_tid, pred, begin, end) and "
+                         "segment=(fstart, fend)")
+    if a.shape[1] == 3:
+        a = np.concatenate([a, np.zeros((a.shape[0], 2), np.int64)], axis=1)
+    frames = np.asarray(segment if segment is not None else (0, 0), dtype=np.int64).reshape(1, 2)
+    return np.ascontiguousarray(a), frames
+
+
+def _label_targets(labels, spans, span_count):
+    tlist = TargetList(labels)
+    if spans is not None:
+        tlist.add_field("spans", spans)
+        tlist.add_field("span_count", span_count)
+    return tlist
 
 
 def _assemble(p_all, f_all, idx, num_tracks, iou, trackid, cls_logits, pred_labels, preprocess, device):
@@ -95,11 +146,14 @@ def _assemble(p_all, f_all, idx, num_tracks, iou, trackid, cls_logits, pred_labe
     return plist, tlist
 
 
-def proposal_pair_lists(segments, preprocess=True, device=None):
+def proposal_pair_lists(segments, preprocess=True, device=None, max_spans=0, iou_thres=0.5, merge="last",
+                        num_predicates=132):
     """A batch of segments at once: `segments` = sequence of dicts with the keys of `proposal_pair_list`
-    (pairs, feats, iou, trackid, cls_logits[, pred_labels]).  The pair filter of ALL segments is ONE launch
-    (`pair_off` / `track_off` form of tspn_proposal_pair_filter_i64) and the loader pays ONE host sync per
-    batch (the kept-row counts) instead of several per segment.  Returns [(PairList, TargetList | None)]."""
+    (pairs, feats, iou, trackid, cls_logits[, pred_labels | gt_rel_insts[, segment]]).  The pair filter of ALL segments is
+    ONE launch (`pair_off` / `track_off` form of tspn_proposal_pair_filter_i64) and the loader pays ONE host sync per
+    batch (the kept-row counts) instead of several per segment.  The segments with a "gt_rel_insts" key are labelled by
+    ONE `ops.pair_labels` call over their kept pair tables, after that sync (`max_spans`, `iou_thres`, `merge`,
+    `num_predicates` as in `proposal_pair_list`).  Returns [(PairList, TargetList | None)]."""
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     if not len(segments):
         return []
@@ -109,6 +163,7 @@ def proposal_pair_lists(segments, preprocess=True, device=None):
     for p, f in zip(p_all, f_all):
         if f.dim() != 2 or f.shape[0] != p.shape[0]:
             raise ValueError(f"feats must be [P,F] with one row per pair (pairs {tuple(p.shape)}, feats {tuple(f.shape)})")
+    insts = [_relation_instances(s.get("gt_rel_insts"), s.get("segment"), max_spans, s.get("pred_labels")) for s in segments]
     pair_off = np.concatenate([[0], np.cumsum([p.shape[0] for p in p_all])]).astype(np.int64)
     track_off = np.concatenate([[0], np.cumsum([t.shape[0] for t in tids])]).astype(np.int64)
     idx, count, ntr = ops.proposal_pair_filter(torch.cat(p_all), torch.cat(tids),
@@ -122,7 +177,63 @@ def proposal_pair_lists(segments, preprocess=True, device=None):
         lo = int(pair_off[k])
         out.append(_assemble(p_all[k], f_all[k], idx[lo:lo + int(counts[0, k])], int(counts[1, k]), s["iou"], s["trackid"],
                              s["cls_logits"], s.get("pred_labels"), preprocess, device))
+    ks = [k for k, (a, _) in enumerate(insts) if a is not None]
+    if ks:
+        # the offsets of the labelled segments' kept pair tables, tracks, iou tables and instances: host arithmetic on
+        # the counts the one sync brought, one upload
+        sizes = np.array([[int(counts[0, k]), tids[k].shape[0], tids[k].shape[0] ** 2, insts[k][0].shape[0]] for k in ks],
+                         dtype=np.int64)
+        offs = torch.from_numpy(np.concatenate([np.zeros((1, 4), np.int64), np.cumsum(sizes, axis=0)]).T.copy()).to(device)
+        ious = [_to_dev(segments[k]["iou"], device, torch.float32).reshape(-1) for k in ks]
+        for k, v in zip(ks, ious):
+            if v.numel() != tids[k].shape[0] ** 2:
+                raise ValueError(f"proposal_pair_lists: segment {k}: iou must be [M,M] with M = {tids[k].shape[0]}")
+        labels, spans, span_count, _ = ops.pair_labels(
+            torch.cat([out[k][0].get_field("tracklet_pairs") for k in ks]), torch.cat([tids[k] for k in ks]), torch.cat(ious),
+            torch.from_numpy(np.concatenate([insts[k][0] for k in ks])).to(device), num_predicates, iou_thres, merge,
+            max_spans, torch.from_numpy(np.concatenate([insts[k][1] for k in ks])).to(device) if max_spans else None,
+            offs[0], offs[1], offs[2], offs[3])
+        for j, k in enumerate(ks):
+            lo, hi = int(sizes[:j, 0].sum()), int(sizes[:j + 1, 0].sum())
+            out[k] = (out[k][0], _label_targets(labels[lo:hi], spans[lo:hi] if max_spans else None,
+                                                span_count[lo:hi] if max_spans else None))
     return out
+
+
+def segment_video(fstart, fend):
+    """The 30-frame segments, 15 frames apart, that lie inside [fstart, fend) (lib/modeling/__init__.py:35-41)."""
+    return [(f, f + 30) for f in range(int(fstart), int(fend) - 30 + 1, 15)]
+
+
+def segment_relation_instances(rel_insts, mode, frame_count=None, has_segment=None):
+    """The per-segment ground-truth instance lists of one video, as `VRDataset.__init__` collects them
+    (vrdataset.py:26-55): {(fstart, fend): int64 [R,5] = (sub_tid, obj_tid, pred, begin, end)}, the `gt_rel_insts` /
+    `segment` arguments of `proposal_pair_list`.  Host only, numpy only; nothing is parsed here.
+
+    `rel_insts`: the video's instances in annotation order, rows (sub_tid, obj_tid, pred, begin, end) with the track ids
+    and the predicate index as plain ints (the 1-tuples of vrdataset.py:40-42 are a defect and are not reproduced) and
+    [begin, end) the instance's duration in video frames.  `has_segment(fstart, fend)` stands for the reference's check
+    that the segment's feature file exists (vrdataset.py:52); default: every segment.
+      mode "train": an instance goes to every segment of segment_video(begin, end)            (vrdataset.py:46-47)
+      mode "test" : every segment of segment_video(0, frame_count) gets every instance        (vrdataset.py:48-49)
+      mode "clip" : every segment of segment_video(0, frame_count) gets the instances whose duration intersects it
+                    (build-defined: the mode whose spans are not the whole segment)"""
+    a = np.asarray(rel_insts, dtype=np.int64).reshape(-1, 5)
+    if mode not in ("train", "test", "clip"):
+        raise ValueError(f"segment_relation_instances: mode must be 'train', 'test' or 'clip', got {mode!r}")
+    if mode != "train" and frame_count is None:
+        raise ValueError(f"segment_relation_instances: mode {mode!r} needs frame_count")
+    keep = has_segment if has_segment is not None else (lambda fstart, fend: True)
+    video = None if mode == "train" else segment_video(0, frame_count)
+    rows = {}
+    for row in a:
+        begin, end = int(row[3]), int(row[4])
+        for fstart, fend in (segment_video(begin, end) if mode == "train" else video):
+            if mode == "clip" and not (begin < fend and end > fstart):
+                continue
+            if keep(fstart, fend):
+                rows.setdefault((fstart, fend), []).append(row)
+    return {seg: np.stack(r).astype(np.int64) for seg, r in rows.items()}
 
 
 # ---------------------------------------------------------------------------------------------------------

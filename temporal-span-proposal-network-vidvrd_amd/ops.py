@@ -17,7 +17,7 @@ __all__ = [
     "pair_gather", "pack_conv3", "conv3", "conv3_tc", "pack_conv3_wino63", "conv3_tc_wino63", "pack_conv3_wino63_f16x3", "conv3_tc_wino63_f16x3", "heads", "heads_pairgrid", "heads_pairgrid_f16x3", "heads_pairgrid_f16x3_split_bytes",
     "heads_pairgrid_f16x3_set_force_exact", "temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
     "forward_fused", "temporal_encoder_heads", "fused_workspace_bytes", "fused_bf16_workspace_bytes", "decode_topk", "decode_spans", "decode_span_relations",
-    "span_anchor_labels", "span_loss", "span_anchor_sample",
+    "span_anchor_labels", "span_loss", "span_anchor_sample", "pair_labels",
     "cast_bf16", "pack_conv3_bf16", "pack_heads_bf16", "conv3_tc_bf16", "heads_pairgrid_bf16",
     "pair_plan", "heads_pairlist_bf16",
     "transpose_cast_bf16", "temporal_encoder_heads_bf16",
@@ -822,6 +822,66 @@ def span_anchor_sample(label, batch, positive_fraction, stream_key, key_bits=32,
     _abi.check(lib.tspn_span_anchor_sample(_p(label), n, int(stream_key) & 0xFFFFFFFFFFFFFFFF, key_bits, batch, want_pos,
                                            _p(partials), _p(counts), _p(mask), _stream()))
     return mask, counts
+
+
+PAIR_LABEL_MERGES = {"last": 0, "or": 1}
+
+
+def pair_labels(pairs, trackid, iou, insts, num_predicates, iou_thres=0.5, merge="last", max_spans=0, seg_frames=None,
+                pair_off=None, track_off=None, iou_off=None, inst_off=None):
+    """Training targets from ground-truth relation instances (tspn_pair_labels_f32, DESIGN.md §2 "pair labels").
+
+    One segment: pairs int64 [P,2] (any pair table), trackid int64 [M] (< 0 proposal, >= 0 ground-truth track id), iou fp32
+    [M,M], insts int64 [R,5] = (sub_tid, obj_tid, pred, begin, end).  Several segments stored back to back: iou flat, and
+    int64 device offsets pair_off / track_off / iou_off / inst_off [S+1] (all four or none).  `max_spans` = G > 0 also
+    wants seg_frames int64 [S,2] = (fstart, fend) on the device.  merge "last": the one-hot of the last covering instance's
+    predicate (the reference's statement order); "or": every covering instance's predicate.
+    Returns (labels fp32 [P,K], spans int64 [P,G,2] | None, span_count int32 [P] | None, inst_cols int32 [R,2]); a pair
+    naming a track outside its segment gets span_count -1 and zero labels.  Nothing is synchronised."""
+    who = "pair_labels"
+    _dev(pairs, f"{who}: pairs", torch.int64); _dev(trackid, f"{who}: trackid", torch.int64)
+    _dev(iou, f"{who}: iou"); _dev(insts, f"{who}: insts", torch.int64)
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or trackid.dim() != 1 or insts.dim() != 2 or insts.shape[1] != 5:
+        raise ValueError(f"{who}: pairs must be [P,2], trackid [M] and insts [R,5], got {tuple(pairs.shape)}, "
+                         f"{tuple(trackid.shape)}, {tuple(insts.shape)}")
+    if merge not in PAIR_LABEL_MERGES:
+        raise ValueError(f"{who}: merge must be 'last' or 'or', got {merge!r}")
+    K, G, thr = int(num_predicates), int(max_spans), float(iou_thres)
+    if not 1 <= K <= 512 or not 0 <= G <= 16:
+        raise ValueError(f"{who}: needs 1 <= num_predicates <= 512 and 0 <= max_spans <= 16, got {K}, {G}")
+    if thr != thr or thr in (float("inf"), float("-inf")):
+        raise ValueError(f"{who}: iou_thres must be finite, got {iou_thres}")
+    offs = (pair_off, track_off, iou_off, inst_off)
+    dev, P, M, R = pairs.device, pairs.shape[0], trackid.shape[0], insts.shape[0]
+    if all(o is None for o in offs):
+        S = 1
+        if iou.shape != (M, M):
+            raise ValueError(f"{who}: iou must be [M,M] with M = {M}, got {tuple(iou.shape)}")
+    elif any(o is None for o in offs):
+        raise ValueError(f"{who}: pair_off, track_off, iou_off and inst_off go together")
+    else:
+        for name, o in zip(("pair_off", "track_off", "iou_off", "inst_off"), offs):
+            _dev(o, f"{who}: {name}", torch.int64)
+        if any(o.dim() != 1 or o.shape != pair_off.shape for o in offs) or pair_off.numel() < 1:
+            raise ValueError(f"{who}: the offsets must be int64 [S+1]")
+        S = pair_off.numel() - 1
+        if iou.dim() != 1:
+            raise ValueError(f"{who}: iou of several segments must be flat, got {tuple(iou.shape)}")
+    if G > 0:
+        if seg_frames is None:
+            raise ValueError(f"{who}: max_spans = {G} needs seg_frames [S,2]")
+        _dev(seg_frames, f"{who}: seg_frames", torch.int64)
+        if tuple(seg_frames.shape) != (S, 2):
+            raise ValueError(f"{who}: seg_frames must be [S,2] with S = {S}, got {tuple(seg_frames.shape)}")
+    labels = torch.empty((P, K), dtype=torch.float32, device=dev)
+    inst_cols = torch.empty((R, 2), dtype=torch.int32, device=dev)
+    spans = torch.empty((P, G, 2), dtype=torch.int64, device=dev) if G else None
+    span_count = torch.empty((P,), dtype=torch.int32, device=dev) if G else None
+    _abi.check(_abi.lib().tspn_pair_labels_f32(_p(pairs), _p(pair_off), _p(trackid), _p(track_off), _p(iou), _p(iou_off),
+                                               _p(insts), _p(inst_off), _p(seg_frames if G else None), S, P, M, R, K, G, thr,
+                                               PAIR_LABEL_MERGES[merge], _p(labels), _p(spans), _p(span_count),
+                                               _p(inst_cols), _stream()))
+    return labels, spans, span_count, inst_cols
 
 
 def _fused_desc(feats, pairs, B, N, conv_packed, conv_bias, head_w, head_b, cls_w, cls_b):

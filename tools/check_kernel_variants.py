@@ -2,7 +2,8 @@
 """Check a profiled test run against the kernel variant tables (tests/kernel_variants.py for csrc/*.hip,
 tests/eval_kernel_variants.py for csrc/eval/*.hip, tests/relations_kernel_variants.py for csrc/relations/*.hip,
 tests/pairlist_kernel_variants.py for csrc/pairlist/*.hip, tests/spanbf16_kernel_variants.py for csrc/spanbf16/*.hip,
-tests/spanloss_kernel_variants.py for csrc/spanloss/*.hip, tests/spansample_kernel_variants.py for csrc/spansample/*.hip).
+tests/spanloss_kernel_variants.py for csrc/spanloss/*.hip, tests/spansample_kernel_variants.py for csrc/spansample/*.hip,
+tests/pairlabels_kernel_variants.py for csrc/pairlabels/*.hip).
 
     rocprofv3 --kernel-trace --stats -d OUT -o run -- python -m pytest FILE... -q -m gpu
     python tools/check_kernel_variants.py OUT/.../run_kernel_stats.csv FILE...   (or OUT/.../run_results.db)
@@ -22,6 +23,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import eval_kernel_variants  # noqa: E402
 import kernel_variants  # noqa: E402
+import pairlabels_kernel_variants  # noqa: E402
 import pairlist_kernel_variants  # noqa: E402
 import relations_kernel_variants  # noqa: E402
 import spanbf16_kernel_variants  # noqa: E402
@@ -136,7 +138,8 @@ def main(argv):
     checked, missing = 0, []
     for r in (kernel_variants.VARIANTS + eval_kernel_variants.VARIANTS + relations_kernel_variants.VARIANTS
               + pairlist_kernel_variants.VARIANTS + spanbf16_kernel_variants.VARIANTS
-              + spanloss_kernel_variants.VARIANTS + spansample_kernel_variants.VARIANTS):
+              + spanloss_kernel_variants.VARIANTS + spansample_kernel_variants.VARIANTS
+              + pairlabels_kernel_variants.VARIANTS):
         if not any(node.partition("::")[0] in files for node in r["tests"]):
             continue
         checked += 1
