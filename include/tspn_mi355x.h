@@ -307,6 +307,25 @@ int tspn_conv3_tc_wino63_f16x3(const float* x, int64_t B, int64_t T, int64_t Cin
  * tiles only.  The outputs are the same bit for bit (tests/test_gpu_wino63_f16x3_tail.py).  Process-wide (additive, no
  * version bump); returns the previous value, TSPN_EINVAL for any other `on`. */
 int tspn_conv3_tc_wino63_f16x3_set_tail_split(int on);
+/* The input side of the split form (additive, no version bump).  Two forms produce the same bytes
+ * (tests/test_gpu_input_f16x3.py): the two-pass transform (a workgroup per 8 sextets, x read twice; in
+ * tspn_forward_fused_f32 the temporal mean is a third read by its own kernel) and the fused kernels of
+ * csrc/inputf16/ (a scan with a workgroup per tracklet takes the column maxima AND the mean in one read, a second
+ * kernel splits: x read twice in all; Cin <= 2048).
+ *   tspn_conv3_tc_wino63_f16x3_input_form(NT, T, Cin, cus): 1 where the fused kernels are taken for NT tracklets on a
+ *     device of `cus` compute units, 0 for the two-pass form -- a pure function, what the entries ask by default
+ *   tspn_conv3_tc_wino63_f16x3_set_input_form(form): 0 (default) = by that function, 1 = two-pass everywhere,
+ *     2 = fused wherever the kernels support the shape.  Process-wide; returns the previous value, TSPN_EINVAL for any
+ *     other `form`.
+ *   tspn_conv3_tc_wino63_f16x3_input: the input side alone -- split input and column exponents, its outputs, into the head of
+ *     `split_input` (sized and aligned as the conv's buffer, tspn_conv3_tc_wino63_f16x3_workspace_bytes(B, T, Cin, M): fp16 [8][2][Cin/8][nsp2][8], 256-byte aligned
+ *     int32 [8][nsp2] behind it, nsp2 = B ceil(T/6) rounded up to 256), the temporal mean into fbar [B, Cin] (may be
+ *     null), the hot-sextet keys ((float bits of the largest |x| << 32) | sextet) into hot_slots (64 slots 256 bytes
+ *     apart, zeroed by the caller, the reader takes their maximum; may be null). */
+int tspn_conv3_tc_wino63_f16x3_input_form(int64_t NT, int64_t T, int64_t Cin, int cus);
+int tspn_conv3_tc_wino63_f16x3_set_input_form(int form);
+int tspn_conv3_tc_wino63_f16x3_input(const float* x, int64_t B, int64_t T, int64_t Cin, int64_t M, void* split_input,
+                                     size_t split_input_bytes, float* fbar, uint64_t* hot_slots, void* stream);
 
 
 /* ---- a8/a10: relationness + span-regression heads -----------------------

@@ -157,6 +157,9 @@ PROTOTYPES = {
     "tspn_conv3_tc_wino63_f16x3_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "tspn_conv3_tc_wino63_f16x3": (_int, [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _int, _vp, _vp, _sz, _vp]),
     "tspn_conv3_tc_wino63_f16x3_set_tail_split": (_int, [_int]),
+    "tspn_conv3_tc_wino63_f16x3_input_form": (_int, [_i64, _i64, _i64, _int]),
+    "tspn_conv3_tc_wino63_f16x3_set_input_form": (_int, [_int]),
+    "tspn_conv3_tc_wino63_f16x3_input": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _sz, _vp, _vp, _vp]),
     "tspn_span_predicate_workspace_bytes": (_sz, [_i64, _i64, _i64, _i64]),
     "tspn_span_predicate_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
     "tspn_decode_span_relations_workspace_bytes": (_sz, [_i64] * 8),

@@ -67,12 +67,32 @@ __global__ __launch_bounds__(1024) void pairf16_scale_kernel(const float* __rest
   const int lane = threadIdx.x & 63, h = threadIdx.x >> 6;
   float mx = 0.f;
   bool finite = true;
-  if (h < H) {
-    for (int c = lane; c < C; c += 64) {
-      const float a = fabsf(Wh[(int64_t)h * C + c]);
-      finite = finite && (a < __builtin_inff());       // false for NaN and Inf
-      mx = fmaxf(mx, a);
+  // The maximum (fmaxf: of the values that are not NaN) and the finite test do not depend on the order, so a lane takes
+  // 16-byte loads, four of them in flight into four partial maxima: a row of 4096 weights is 4 round trips, not 64.
+  auto take = [&](float w, float& m) {
+    const float a = fabsf(w);
+    finite = finite && (a < __builtin_inff());         // false for NaN and Inf
+    m = fmaxf(m, a);
+  };
+  if (h < H && (reinterpret_cast<uintptr_t>(Wh) & 15) == 0) {     // (C % 32 == 0 keeps every row aligned as Wh is)
+    const float4* row = reinterpret_cast<const float4*>(Wh + (int64_t)h * C);
+    const int n4 = C >> 2;
+    float m[4] = {0.f, 0.f, 0.f, 0.f};
+    int c = lane;
+    for (; c + 192 < n4; c += 256) {
+      float4 v[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) v[u] = row[c + 64 * u];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { take(v[u].x, m[u]); take(v[u].y, m[u]); take(v[u].z, m[u]); take(v[u].w, m[u]); }
     }
+    for (; c < n4; c += 64) {
+      const float4 v = row[c];
+      take(v.x, m[0]); take(v.y, m[0]); take(v.z, m[0]); take(v.w, m[0]);
+    }
+    mx = fmaxf(fmaxf(m[0], m[1]), fmaxf(m[2], m[3]));
+  } else if (h < H) {
+    for (int c = lane; c < C; c += 64) take(Wh[(int64_t)h * C + c], mx);
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));

@@ -119,8 +119,22 @@ int conv3_tc_wino63(const float* x, int64_t B, int64_t T, int64_t Cin, const flo
 // split transformed input and the contraction's parking area
 bool wino63_f16x3_supported(int64_t Cin, int64_t M);
 size_t wino63_f16x3_workspace_bytes(int64_t B, int64_t T, int64_t Cin, int64_t M);
+// `fused_in`: which input kernels run -- wino63_f16x3_fused_input()'s answer, asked once per pass.  The fused form (scan +
+// split kernels) also writes the temporal mean `fbar` [B, Cin] where that is not null (the two-pass transform ignores it).
 int wino63_f16x3_input_transform(const float* x, int64_t B, int64_t T, int64_t Cin, int64_t M, void* workspace,
-                                 size_t workspace_bytes, void* stream, uint64_t* hot = nullptr);
+                                 size_t workspace_bytes, void* stream, uint64_t* hot = nullptr, bool fused_in = false,
+                                 float* fbar = nullptr, int stages = 3);
+// whether a launch of B tracklets takes the fused input kernels: tspn_conv3_tc_wino63_f16x3_set_input_form()'s switch,
+// else wino63_f16x3_input_form() on the current device's CUs
+bool wino63_f16x3_fused_input(int64_t B, int64_t T, int64_t Cin);
+// The fused input kernels (inputf16/tspn_input_f16x3.hip): split input, column exponents, hot-sextet report and
+// (fbar != nullptr) the temporal mean from two reads of x.  nsp2: the padded sextet count of the workspace layout.
+// `stages`: TSPN_INPUT_SCAN (column exponents, hot sextet, mean) | TSPN_INPUT_SPLIT (the halves, behind a scan on the same
+// stream) -- the fused pass puts the predicate head and its event between the two.
+constexpr int TSPN_INPUT_SCAN = 1, TSPN_INPUT_SPLIT = 2;
+bool input_f16x3_supported(int64_t T, int64_t Cin);
+int input_f16x3(const float* x, int64_t NT, int64_t T, int64_t Cin, int64_t nsp2, _Float16* Vh, int* Ve, float* fbar,
+                uint64_t* hot, void* stream, int stages = TSPN_INPUT_SCAN | TSPN_INPUT_SPLIT);
 int wino63_f16x3_contract(void* workspace, size_t workspace_bytes, int64_t B, int64_t T, int64_t Cin,
                           const int16_t* packed, int64_t M, const float* bias, int relu, float* y, int64_t ldy,
                           void* stream);

@@ -125,10 +125,29 @@ extern "C" int tspn_forward_fused_f32(const tspn_fused_desc* d, void* stream) {
   if (e != hipSuccess)
     return tspn::fail(TSPN_ELAUNCH, "tspn_forward_fused: bias staging: %s", hipGetErrorString(e));
 
+  // Accuracy guard of F(6,3) (d->conv_check rows, needs the raw weights and an attached status block): the transform
+  // reports the sextet with the largest |x|; behind the conv a few outputs are recomputed in float64 (tspn_conv_guard.hip)
+  const bool guard = w63 && d->conv_check > 0 && d->conv_weight != nullptr;
+  uint64_t* hot = guard ? reinterpret_cast<uint64_t*>(ws + L.hot) : nullptr;
+  // (scratch of the spot check: the workgroups' meeting point + the slots the transform reports the hot sextet into)
+  if (guard && hipMemsetAsync(hot, 0, TSPN_CONV_CHECK_SCRATCH_BYTES, s) != hipSuccess)
+    return tspn::fail(TSPN_ELAUNCH, "tspn_forward_fused: guard staging: %s", hipGetErrorString(hipGetLastError()));
+  uint64_t* hot_slots = hot ? hot + TSPN_CONV_CHECK_HOT_OFFSET / 8 : nullptr;
+
   // 0. RelOIPool over the segment on the pair feats (= cat of the two tracklet means) + predicate head;
   // linear in the two halves, so evaluated per tracklet and combined per pair.  Done FIRST: the logits do not
   // depend on the encoder, and a caller may decode / gather them on another stream behind ev_logits_ready.
-  if ((rc = tspn_temporal_mean_f32(d->feats, NT, T, D, 1, fbar, stream))) return rc;
+  // Split-fp16 F(6,3), where the shape fills the chip: the mean comes out of the transform's pass for the column maxima
+  // (inputf16/tspn_input_f16x3.hip: two reads of the features instead of three).  That scan takes the mean kernel's place
+  // here and the split stays where the transform was, behind ev_logits_ready: what a caller runs on another stream behind
+  // the event then overlaps the HBM-bound split as it did the transform, not the contraction.
+  const bool fused_in = f16x3 && tspn::wino63_f16x3_fused_input(NT, T, D);
+  if (fused_in)
+    rc = tspn::wino63_f16x3_input_transform(d->feats, NT, T, D, 2 * C, ws + L.vt, L.vt_bytes, stream, hot_slots, true, fbar,
+                                            tspn::TSPN_INPUT_SCAN);
+  else
+    rc = tspn_temporal_mean_f32(d->feats, NT, T, D, 1, fbar, stream);
+  if (rc) return rc;
   (void)pooled;
   if ((rc = tspn::pair_predicate(fbar, NT, D, d->pairs, d->P, d->cls_w, d->cls_b, d->K, d->out_logits, lin,
                                  L.lin_bytes, stream)))
@@ -144,18 +163,12 @@ extern "C" int tspn_forward_fused_f32(const tspn_fused_desc* d, void* stream) {
   if (!tc && (rc = tspn_transpose_td_f32(d->feats, NT, T, D, xt, stream))) return rc;
   // F(6,3): the Winograd input transform runs as its own HBM-bound pass; the profiling events bracket the
   // MFMA kernel only
-  // Accuracy guard of F(6,3) (d->conv_check rows, needs the raw weights and an attached status block): the transform
-  // reports the sextet with the largest |x|; behind the conv a few outputs are recomputed in float64 (tspn_conv_guard.hip)
-  const bool guard = w63 && d->conv_check > 0 && d->conv_weight != nullptr;
-  uint64_t* hot = guard ? reinterpret_cast<uint64_t*>(ws + L.hot) : nullptr;
-  // (scratch of the spot check: the workgroups' meeting point + the slots the transform reports the hot sextet into)
-  if (guard && hipMemsetAsync(hot, 0, TSPN_CONV_CHECK_SCRATCH_BYTES, s) != hipSuccess)
-    return tspn::fail(TSPN_ELAUNCH, "tspn_forward_fused: guard staging: %s", hipGetErrorString(hipGetLastError()));
-  uint64_t* hot_slots = hot ? hot + TSPN_CONV_CHECK_HOT_OFFSET / 8 : nullptr;
   if (f16x3) {
-    if ((rc = tspn::wino63_f16x3_input_transform(d->feats, NT, T, D, 2 * C, ws + L.vt, L.vt_bytes, stream, hot_slots)))
+    if ((rc = tspn::wino63_f16x3_input_transform(d->feats, NT, T, D, 2 * C, ws + L.vt, L.vt_bytes, stream, hot_slots, fused_in,
+                                                 nullptr, tspn::TSPN_INPUT_SPLIT)))
       return rc;
-  } else if (w63 && (rc = tspn::wino63_input_transform(d->feats, NT, T, D, ws + L.vt, L.vt_bytes, stream, hot_slots))) {
+  } else if (w63 && !f16x3 &&
+             (rc = tspn::wino63_input_transform(d->feats, NT, T, D, ws + L.vt, L.vt_bytes, stream, hot_slots))) {
     return rc;
   }
   if (d->ev_conv_begin) (void)hipEventRecord(static_cast<hipEvent_t>(d->ev_conv_begin), s);

@@ -38,6 +38,7 @@
 
 #include "tspn_common.h"
 #include "tspn_device.h"
+#include "tspn_wino63_input.h"
 
 namespace {
 
@@ -104,60 +105,7 @@ __global__ void pack_wino63_frag_kernel(const float* __restrict__ W, int64_t M, 
   }
 }
 
-// ---- pieces of the F(6,3) input transform, shared by the fp32 form and the split-fp16 form below: the two must agree bit
-// for bit (the accuracy guard treats them as one algorithm).
-// The eight frames 6 q - 1 .. 6 q + 6 of sextet q of tracklet b, four channels from `channel_offset`.  Frames outside the
-// tracklet are zero (the conv's padding) and so is a sextet past the end of the launch (!ok); their addresses are clamped.
-__device__ __forceinline__ void wino63_load_sextet(const float* __restrict__ x, int64_t b, int q, int T, int Cin,
-                                                   int64_t ncols, bool ok, int channel_offset, f32x4 (&d)[8]) {
-#pragma unroll
-  for (int i = 0; i < 8; ++i) {
-    const int t = 6 * q + i - 1;
-    int64_t n = b * T + t;
-    n = n < 0 ? 0 : (n < ncols ? n : ncols - 1);
-    const f32x4 v = *reinterpret_cast<const f32x4*>(x + n * Cin + channel_offset);
-    d[i] = (ok && t >= 0 && t < T) ? v : f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-}
-// V = B^T d
-__device__ __forceinline__ void wino63_bt(const f32x4 (&d)[8], f32x4 (&V)[8]) {
-  V[0] = d[0] - d[6] + 5.25f * (d[4] - d[2]);
-  V[7] = d[7] - d[1] + 5.25f * (d[3] - d[5]);
-  {
-    const f32x4 t1 = d[2] + d[6] - 4.25f * d[4], t2 = d[1] + d[5] - 4.25f * d[3];
-    V[1] = t1 + t2;
-    V[2] = t1 - t2;
-  }
-  {
-    const f32x4 t1 = d[6] + 0.25f * d[2] - 1.25f * d[4], t2 = 0.5f * d[1] - 2.5f * d[3] + 2.f * d[5];
-    V[3] = t1 + t2;
-    V[4] = t1 - t2;
-  }
-  {
-    const f32x4 t1 = d[6] + 4.f * (d[2] - 1.25f * d[4]), t2 = 2.f * d[1] - 2.5f * d[3] + 0.5f * d[5];
-    V[5] = t1 + t2;
-    V[6] = t1 - t2;
-  }
-}
-// m = max(m, |d[1..6]|) for the hot-sextet key.  NaN-propagating maxima (fmaxf drops NaN): a NaN input makes its sextet
-// hot, and |NaN| (sign cleared by fabsf) has larger bits than +Inf, so NaN ranks above Inf in the key.  Only the sextet's
-// OWN frames d[1..6] count: a value in the halo d[0] / d[7] enters one transformed column of the neighbour (one of its
-// outputs), while the sextet that holds it carries it into all six -- with the window counted, the equal keys of both went
-// to the later sextet.
-__device__ __forceinline__ void wino63_absmax_own_frames(const f32x4 (&d)[8], float& m) {
-#pragma unroll
-  for (int i = 1; i < 7; ++i)
-    m = __builtin_elementwise_maximum(
-        __builtin_elementwise_maximum(m, __builtin_elementwise_maximum(fabsf(d[i][0]), fabsf(d[i][1]))),
-        __builtin_elementwise_maximum(fabsf(d[i][2]), fabsf(d[i][3])));
-}
-// the wave's largest key into slot `slot` of `hot`: one 64-bit atomic max per wave, no return value
-__device__ __forceinline__ void wino63_hot_publish(unsigned long long* __restrict__ hot, unsigned long long key, unsigned slot) {
-  key = tspn::wave_max_u64(key);
-  if ((threadIdx.x & 63) == 0)
-    __hip_atomic_fetch_max(hot + 32 * (slot & (TSPN_CONV_CHECK_HOT_SLOTS - 1)), key, __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-}
+// (the pieces of the input transform that the fp32 form and the split-fp16 forms share: tspn_wino63_input.h)
 
 // Input transform V = B^T d.  A wave = 8 sextets x 8 channel groups (loads: whole 128-byte lines of x; stores:
 // 128-byte runs of Vg).  Frames outside the tracklet are zero (the conv's padding); sextets past the end of the
@@ -180,7 +128,7 @@ __global__ __launch_bounds__(256) void wino63_input_transform_kernel(
   const int64_t b = ok ? S / nq : 0;
   const int q = ok ? (int)(S - b * nq) : 0;
   f32x4 d[8], V[8];
-  wino63_load_sextet(x, b, q, T, Cin, ncols, ok, 4 * cg, d);
+  wino63_load_sextet(x, b, q, T, Cin, ok, 4 * cg, d);
   if (hot) {                                                         // uniform
     float m = 0.f;
     wino63_absmax_own_frames(d, m);
@@ -451,15 +399,6 @@ constexpr size_t F_SMEM_ALL = F_SMEM + 2 * 256 * sizeof(int);   // + the exponen
 static_assert(TSPN_WINO63_GM > 0 && TSPN_WINO63_GM < 256, "the contraction's GM argument carries the tail split and the piece form above bit 7");
 constexpr size_t F_PARK_PER_TILE = (size_t)7 * F_THREADS * 128 * sizeof(float);   // points 0..6 of a tile, fp32
 
-// power-of-two exponent e with max * 2^e in [2^14, 2^15); 0 for a zero or non-finite maximum (a non-finite value then
-// stays non-finite through the split, and so does every output it reaches)
-__device__ __forceinline__ int split_exponent(double mx) {
-  if (!(mx > 0.0) || !(mx <= 1.7976931348623157e308)) return 0;
-  int k;
-  (void)frexp(mx, &k);           // mx = f 2^k, f in [0.5, 1)
-  return 15 - k;
-}
-
 __device__ __forceinline__ double wino63_u(int j, double g0, double g1, double g2) {
   switch (j) {
     case 0: return g0;
@@ -528,7 +467,7 @@ __global__ __launch_bounds__(256) void wino63_input_transform_kernel(
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       f32x4 d[8];
-      wino63_load_sextet(x, b, q, T, Cin, ncols, ok, 8 * cg + 4 * h, d);
+      wino63_load_sextet(x, b, q, T, Cin, ok, 8 * cg + 4 * h, d);
       if (want_max) wino63_absmax_own_frames(d, xmax);
       wino63_bt(d, V[h]);
     }
@@ -545,9 +484,7 @@ __global__ __launch_bounds__(256) void wino63_input_transform_kernel(
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
       for (int h = 0; h < 2; ++h)
-        cmax[j] = __builtin_elementwise_maximum(
-            __builtin_elementwise_maximum(cmax[j], __builtin_elementwise_maximum(fabsf(V[h][j][0]), fabsf(V[h][j][1]))),
-            __builtin_elementwise_maximum(fabsf(V[h][j][2]), fabsf(V[h][j][3])));
+        cmax[j] = wino63_absmax4(cmax[j], V[h][j]);
   }
   if (hot)                                                         // uniform
     wino63_hot_publish(hot, ((unsigned long long)__float_as_uint(xm) << 32) | (unsigned)(ok ? S : 0),
@@ -580,10 +517,10 @@ __global__ __launch_bounds__(256) void wino63_input_transform_kernel(
       f16x8 hi, lo;
 #pragma unroll
       for (int i = 0; i < 8; ++i) {
-        const float u = ldexpf(V[i >> 2][j][i & 3], ecol[j]);
-        const _Float16 h = (_Float16)u;
+        _Float16 h, l;
+        wino63_split_f16(V[i >> 2][j][i & 3], ecol[j], h, l);
         hi[i] = h;
-        lo[i] = (_Float16)(u - (float)h);     // exact in fp32
+        lo[i] = l;
       }
       _Float16* dst = Vh + (((int64_t)j * 2 * ncg + cg) * nsp2 + S) * 8;
       *reinterpret_cast<f16x8*>(dst) = hi;
@@ -1133,7 +1070,8 @@ extern "C" int tspn_pack_conv3_wino63_f16x3(const float* W, int64_t M, int64_t C
 
 // step 1 of the split form: V = B^T d, split and scaled, into the workspace (+ the guard's hot-sextet report)
 int tspn::wino63_f16x3_input_transform(const float* x, int64_t B, int64_t T, int64_t Cin, int64_t M, void* workspace,
-                                       size_t workspace_bytes, void* stream, uint64_t* hot) {
+                                       size_t workspace_bytes, void* stream, uint64_t* hot, bool fused_in, float* fbar,
+                                       int stages) {
   const char* what = "tspn_conv3_tc_wino63_f16x3(input transform)";
   if (int rc = check_common(what, B, T, Cin, 32, T)) return rc;
   TSPN_REQUIRE(tspn::wino63_f16x3_supported(Cin, M), TSPN_EUNSUPPORTED,
@@ -1149,6 +1087,9 @@ int tspn::wino63_f16x3_input_transform(const float* x, int64_t B, int64_t T, int
   const int64_t nsext = B * nq, nsp2 = padded_sextets_f16x3(B, T);
   TSPN_REQUIRE(nsp2 / 8 < (1LL << 31), TSPN_EUNSUPPORTED, "%s: grid too large", what);
   char* ws = static_cast<char*>(workspace);
+  if (fused_in)
+    return tspn::input_f16x3(x, B, T, Cin, nsp2, reinterpret_cast<_Float16*>(ws + L.v), reinterpret_cast<int*>(ws + L.e), fbar,
+                             hot, stream, stages);
   void (*kern)(const float*, _Float16*, int*, int, int, int, int64_t, int64_t, int64_t, unsigned long long*) =
       wino63_input_transform_kernel;
   hipLaunchKernelGGL(kern, dim3((unsigned)(nsp2 / 8)), dim3(256), 0, TSPN_STREAM(stream), x,
@@ -1176,6 +1117,34 @@ static int device_cus() {
   if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 0;
   if (tracked) cached[dev].store(cus, std::memory_order_relaxed);
   return cus;
+}
+
+// ---- which input kernels run ahead of the split contraction
+// The fused form (inputf16/tspn_input_f16x3.hip) takes the column maxima and the temporal mean in ONE pass over x, one
+// workgroup of Cin / 4 threads per tracklet, and splits in a second; the two-pass kernel above is one workgroup per 8
+// sextets, whatever Cin, and leaves the mean to a third pass (tspn_temporal_mean_f32).  The fused form is taken where its
+// scan workgroups are large enough to keep a CU's loads in flight (Cin >= 1024: four waves) and numerous enough to fill the
+// chip: at least one tracklet per TWO CUs (profiles/r31/README.md has the measured crossover).  A pure function of
+// (NT, T, Cin, CUs); 1 = fused.
+extern "C" int tspn_conv3_tc_wino63_f16x3_input_form(int64_t NT, int64_t T, int64_t Cin, int cus) {
+  if (NT <= 0 || cus <= 0 || !tspn::input_f16x3_supported(T, Cin)) return 0;
+  return Cin >= 1024 && 2 * NT >= cus;
+}
+
+// 0 = by tspn_conv3_tc_wino63_f16x3_input_form (default), 1 = the two-pass transform (and the mean kernel) everywhere,
+// 2 = the fused kernels wherever they support the shape
+static std::atomic<int> g_input_form{0};
+
+extern "C" int tspn_conv3_tc_wino63_f16x3_set_input_form(int form) {
+  TSPN_REQUIRE(form >= 0 && form <= 2, TSPN_EINVAL, "tspn_conv3_tc_wino63_f16x3_set_input_form: form must be 0, 1 or 2");
+  return g_input_form.exchange(form, std::memory_order_relaxed);
+}
+
+bool tspn::wino63_f16x3_fused_input(int64_t B, int64_t T, int64_t Cin) {
+  const int form = g_input_form.load(std::memory_order_relaxed);
+  if (form == 1 || B <= 0) return false;
+  if (form == 2) return tspn::input_f16x3_supported(T, Cin);
+  return tspn_conv3_tc_wino63_f16x3_input_form(B, T, Cin, device_cus()) != 0;
 }
 
 // The tail split of a launch of `tiles` workgroups (one per CU at a time): R = tiles % CUs tiles are left for the last
@@ -1245,6 +1214,23 @@ extern "C" int tspn_conv3_tc_wino63_f16x3(const float* x, int64_t B, int64_t T, 
     TSPN_REQUIRE(tspn::aligned16(packed) && (reinterpret_cast<uintptr_t>(y) & 3) == 0,
                  TSPN_EUNSUPPORTED, "%s: packed weights must be 16-byte aligned", what);
   }
-  if (int rc = tspn::wino63_f16x3_input_transform(x, B, T, Cin, M, workspace, workspace_bytes, stream)) return rc;
+  if (int rc = tspn::wino63_f16x3_input_transform(x, B, T, Cin, M, workspace, workspace_bytes, stream, nullptr,
+                                                  tspn::wino63_f16x3_fused_input(B, T, Cin)))
+    return rc;
   return tspn::wino63_f16x3_contract(workspace, workspace_bytes, B, T, Cin, packed, M, bias, relu, y, T, stream);
+}
+
+// The input side alone (tests, A/B timing): split input + column exponents into the head of `split_input`, a buffer of the
+// conv entry's size and layout, the temporal mean into `fbar` [B, Cin] (may be null), the hot-sextet keys into `hot_slots`
+// (TSPN_CONV_CHECK_HOT_SLOTS slots 256 bytes apart, zeroed by the caller; may be null).  Runs the kernels the conv entry and
+// the fused pass would run for the shape (tspn_conv3_tc_wino63_f16x3_set_input_form).
+extern "C" int tspn_conv3_tc_wino63_f16x3_input(const float* x, int64_t B, int64_t T, int64_t Cin, int64_t M, void* split_input,
+                                                size_t split_input_bytes, float* fbar, uint64_t* hot_slots, void* stream) {
+  const char* what = "tspn_conv3_tc_wino63_f16x3_input";
+  if (int rc = check_common(what, B, T, Cin, 32, T)) return rc;
+  const bool fused_in = tspn::wino63_f16x3_fused_input(B, T, Cin);
+  if (int rc = tspn::wino63_f16x3_input_transform(x, B, T, Cin, M, split_input, split_input_bytes, stream, hot_slots, fused_in, fbar))
+    return rc;
+  if (fbar != nullptr && !fused_in) return tspn_temporal_mean_f32(x, B, T, Cin, 1, fbar, stream);
+  return TSPN_OK;
 }

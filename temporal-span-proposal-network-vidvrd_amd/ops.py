@@ -24,6 +24,7 @@ __all__ = [
     "temporal_mean_bf16", "forward_fused_bf16", "span_predicate",
     "pack_span_cls_bf16", "span_predicate_bf16", "decode_span_relations_bf16", "bottleneck_block_bf16", "bottleneck_block_proj_bf16", "bottleneck_block_res_bf16",
     "proposal_pair_filter", "gather_rows", "wino63_set_piece_form", "wino63_f16x3_set_tail_split", "conv3_spot_check",
+    "wino63_f16x3_set_input_form", "wino63_f16x3_input_form", "wino63_f16x3_input",
     "pack_conv2d", "pack_conv2d_frag", "conv2d_nhwc", "roi_align_nhwc", "pack_conv2d_frag_bf16", "conv2d_nhwc_bf16", "max_pool_nhwc", "pack_conv2d_frag_cin4", "conv2d_nhwc_cin4", "max_pool_nhwc_bf16", "pack_stem_bf16", "stem_conv_bf16", "stem_pool_bf16", "bottleneck_tail_bf16",
     "eval_traj_volume", "eval_viou", "eval_greedy_match",
     "status_words", "status_fault", "status_clear", "status_selftest",
@@ -551,6 +552,41 @@ def wino63_f16x3_set_tail_split(on):
     """1 = the split-fp16 contraction cuts the tiles of its last, partly filled round into sub-tiles (default), 0 = whole
     tiles only (tspn_conv3_tc_wino63_f16x3_set_tail_split); same outputs bit for bit.  Returns the previous setting."""
     return _toggle("tspn_conv3_tc_wino63_f16x3_set_tail_split", on)
+
+
+def wino63_f16x3_set_input_form(form):
+    """Which kernels run ahead of the split-fp16 F(6,3) contraction (tspn_conv3_tc_wino63_f16x3_set_input_form): 0 = chosen
+    by shape (default, `wino63_f16x3_input_form`), 1 = the two-pass transform (and the mean kernel) everywhere, 2 = the
+    fused kernels (column maxima and mean in one read) wherever they support the shape; same outputs bit for bit.  Returns the previous setting."""
+    return _toggle("tspn_conv3_tc_wino63_f16x3_set_input_form", form)
+
+
+def wino63_f16x3_input_form(NT, T, Cin, cus):
+    """1 where the default takes the fused input kernels for NT tracklets [T, Cin] on a device of `cus` compute units,
+    else 0 (tspn_conv3_tc_wino63_f16x3_input_form: a pure host function, no device needed)."""
+    return int(_abi.lib().tspn_conv3_tc_wino63_f16x3_input_form(int(NT), int(T), int(Cin), int(cus)))
+
+
+def wino63_f16x3_input(x, M, workspace=None, mean=True, hot=True):
+    """The input side of the split-fp16 F(6,3) conv alone (tspn_conv3_tc_wino63_f16x3_input) on channels-last x[B,T,Cin]
+    for M output rows.  Returns (v, e, fbar, key): the split input as int16 [8, 2, Cin/8, nsp2, 8], the column exponents
+    int32 [8, nsp2] (both views of the workspace), the temporal mean [B, Cin] or None, and the hot-sextet key
+    ((float bits of the largest |x| << 32) | sextet) as a 0-d int64 tensor or None."""
+    _dev(x, "x")
+    B, T, Cin = x.shape
+    l = _abi.lib()
+    need = l.tspn_conv3_tc_wino63_f16x3_workspace_bytes(B, T, Cin, M)
+    workspace = _workspace(workspace, need, x.device, "wino63_f16x3_input", sizes=True)
+    fbar = torch.empty((B, Cin), dtype=torch.float32, device=x.device) if mean else None
+    slots = torch.zeros((64, 32), dtype=torch.int64, device=x.device) if hot else None
+    _abi.check(l.tspn_conv3_tc_wino63_f16x3_input(_p(x), B, T, Cin, M, _p(workspace),
+                                                  workspace.numel() * workspace.element_size(), _p(fbar), _p(slots), _stream()))
+    nsp2 = -(-(B * (-(-T // 6))) // 256) * 256
+    vbytes = 8 * 2 * Cin * nsp2 * 2
+    v = workspace[:vbytes].view(torch.int16).view(8, 2, Cin // 8, nsp2, 8)
+    eoff = -(-vbytes // 256) * 256
+    e = workspace[eoff:eoff + 8 * nsp2 * 4].view(torch.int32).view(8, nsp2)
+    return v, e, fbar, (slots[:, 0].max() if hot else None)
 
 
 def heads(a, head_w, head_b, b=None, ia=None, ib=None, bias=None, channels=None, num_pairs=None):
