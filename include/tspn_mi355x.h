@@ -249,7 +249,19 @@ int tspn_pack_conv3_f32(const float* W, int64_t M, int64_t Cin, int64_t split,
 /* ---- a8: temporal context encoder (k=3 conv as implicit GEMM on MFMA) ----
  * Replaces self.conv + F.relu of DPNHead.forward (lib/modeling/relpn/dpn.py:70):
  *   y[B, M, T] = act(bias[M] + sum_{tap,ci} packed[tap][ci][m] * x[B, ci, t+tap-1])
- * zero padding outside [0,T).  bias may be NULL; relu != 0 applies ReLU.    */
+ * zero padding outside [0,T).  bias may be NULL; relu != 0 applies ReLU.
+ *
+ * Numerical contract of the fp32 scorer entries (this one, tspn_conv3_tc_f32, tspn_heads_f32, tspn_heads_pairgrid_f32,
+ * tspn_predicate_head_f32, tspn_predicate_head_norm_f32, tspn_temporal_mean_f32, tspn_temporal_sum_f32 and the passes built
+ * from them), tests/fp32_reference.py, DESIGN.md §3: with u = 2^-24 and S = |bias| + sum |w| |x|,
+ *   |out - exact| <= (2 (k + Kd / k + extra) + 1) u S
+ * for a contraction of depth Kd on an MFMA of k products per step (conv: k = 2, Kd = 3 Cin, extra = 2; heads and pair grid:
+ * k = 4, Kd = C, extra = 2; split-K GEMM: k = 4, Kd = the slice length, extra = splits + 2), and where every product and every
+ * partial sum is exactly representable the output is the exact sum, bit for bit, whatever the summation order.
+ * fp32 SUBNORMAL operands are KEPT: v_mfma_f32_32x32x2_f32, v_mfma_f32_16x16x4_f32 and the fp32 adds in front of them read
+ * and produce subnormals (measured on gfx950: subnormal activations against weights near 2^100 stay within 0.14 of that
+ * budget, where reading them as zero would miss it by a factor of 10^3 to 10^5), so the contract has no absolute floor.
+ * The sign of a zero output is not part of the contract.                   */
 int tspn_conv3_f32(const float* x, int64_t B, int64_t Cin, int64_t T,
                    const float* packed, int64_t M, const float* bias, int relu,
                    float* y, void* stream);

@@ -335,3 +335,56 @@ VARIANTS = [
          "CM == 128 && CIN == 256 && stride == 2 (else TSPN_EUNSUPPORTED)",
          [ROI + "test_res3_first_block_conv1_3x3_expand_one_launch_bit_identical"], "as above"),
 ]
+
+# tests/test_gpu_fp32_bound.py: the fp32 scorer rows its exact cases, derived budgets and held outputs reach, added to the rows
+# above ((kernel, inst) -> tests; the file asserts the conv and pair-grid variant with conv3_variant / pairgrid_variant)
+F32 = "tests/test_gpu_fp32_bound.py::"
+_CONV_F32 = [F32 + "test_conv3_every_variant_is_exact_at_tile_edges", F32 + "test_conv3_every_variant_meets_the_budget_on_every_kind",
+             F32 + "test_conv3_is_exact_on_the_tile_map_with_a_short_last_group"]
+_HEADS_F32 = [F32 + "test_heads_kernel_is_exact_in_both_modes_vec2_and_scalar", F32 + "test_heads_kernel_meets_the_budget_on_every_kind"]
+_GRID_F32 = [F32 + "test_heads_pairgrid_is_exact_in_every_variant_and_has_the_bits_of_heads_mode_1",
+             F32 + "test_heads_pairgrid_meets_the_budget_on_every_kind"]
+_MEAN_F32 = [F32 + "test_temporal_mean_and_sum_are_exact_for_every_t", F32 + "test_temporal_mean_and_sum_lie_in_their_intervals"]
+_LIN_F32 = [F32 + "test_predicate_head_raw_is_exact_on_every_split_k_row", F32 + "test_predicate_head_raw_meets_the_budget_on_every_kind",
+            F32 + "test_training_backward_products_are_exact_on_the_split_k_gemm",
+            F32 + "test_sigmoid_epilogue_against_the_float64_sigmoid_of_the_kernels_own_logits"]
+_NORM_F32 = [F32 + "test_predicate_head_norm_is_exact_and_meets_the_budget",
+             F32 + "test_sigmoid_epilogue_against_the_float64_sigmoid_of_the_kernels_own_logits"]
+_FUSED_F32 = [F32 + "test_fused_pass_is_exact_and_equals_its_stages"]
+_MOVERS_F32 = [F32 + "test_data_movers_into_held_outputs"]
+FP32_BOUND_TESTS = {
+    ("pack_conv3_kernel", None): _CONV_F32,
+    ("conv3_mfma_kernel", "false"): _CONV_F32,
+    ("conv3_mfma_kernel", "true"): _CONV_F32,
+    ("conv3_mfma_dma_kernel", "16"): _CONV_F32 + [F32 + "test_conv3_at_full_depth", F32 + "test_temporal_encoder_heads_is_exact_and_equals_its_stages"],
+    ("conv3_mfma_dma_kernel", "8"): _CONV_F32,
+    ("conv3_mfma_cl_kernel", None): [F32 + "test_conv3_channels_last_is_exact_and_has_the_bits_of_the_channels_first_kernel",
+                                     F32 + "test_conv3_channels_last_meets_the_budget_on_every_kind", F32 + "test_conv3_at_full_depth"]
+    + _FUSED_F32,
+    ("heads_kernel", "0, true"): _HEADS_F32 + [F32 + "test_temporal_encoder_heads_is_exact_and_equals_its_stages"],
+    ("heads_kernel", "0, false"): _HEADS_F32 + [F32 + "test_heads_kernel_is_exact_at_full_depth",
+                                                F32 + "test_temporal_encoder_heads_is_exact_and_equals_its_stages"],
+    ("heads_kernel", "1, true"): _HEADS_F32 + _GRID_F32[:1],
+    ("heads_kernel", "1, false"): _HEADS_F32 + [F32 + "test_heads_kernel_is_exact_at_full_depth"] + _GRID_F32[:1] + _FUSED_F32,
+    ("heads_pairgrid_kernel", "true"): _GRID_F32,
+    ("heads_pairgrid_kernel", "false"): _GRID_F32 + _FUSED_F32,
+    ("heads_pairgrid3_kernel", None): _GRID_F32,
+    ("pack_heads12_kernel", None): _FUSED_F32,
+    ("heads_pairgrid4_kernel", "8"): _FUSED_F32,
+    ("transpose_gather_kernel", None): _MOVERS_F32,
+    ("transpose_gather_rows_kernel", None): _MOVERS_F32,
+    ("pair_rows_kernel", None): _MOVERS_F32,
+    ("temporal_mean_td_kernel", None): _MEAN_F32,
+    ("temporal_mean_td4_kernel", None): _MEAN_F32 + _FUSED_F32,
+    ("temporal_mean_ct_kernel", None): _MEAN_F32,
+    ("gather_rows_kernel", "HIP_vector_type<float, 2u>"): [F32 + "test_gather_rows_past_one_slab"],
+    ("gather_rows_kernel", "float"): [F32 + "test_gather_rows_past_one_slab"],
+    ("linear_splitk_kernel", "false"): _LIN_F32 + _FUSED_F32,
+    ("linear_reduce_kernel", None): _LIN_F32,
+    ("linear_splitk_kernel", "true"): _NORM_F32,
+    ("linear_reduce_norm_kernel", None): _NORM_F32,
+    ("pair_combine_kernel", None): _FUSED_F32,
+}
+_rows = {(r["kernel"], r["inst"]): r for r in VARIANTS}
+for _key, _tests in FP32_BOUND_TESTS.items():
+    _rows[_key]["tests"] += _tests
