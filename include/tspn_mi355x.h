@@ -379,9 +379,14 @@ int tspn_heads_pairgrid_f32(const float* y, int64_t B, int64_t N, int64_t C, int
  * split_buf: split_bytes >= tspn_heads_pairgrid_f16x3_split_bytes(C, H) bytes of 16-byte aligned scratch, every byte of
  * which the call writes before it reads it (0 bytes for a C or H the entry refuses).
  * tspn_heads_pairgrid_f16x3_set_force_exact(1) sends every tile of later calls (this entry and the fused pass) through
- * the fp32 chain, process-wide, for tests; returns the previous setting.                                           */
+ * the fp32 chain, process-wide, for tests; returns the previous setting.
+ * tspn_heads_pair_f16x3_set_diag_skip(on): 1 (default) = in a tile whose subject and object block are the same, which
+ * holds no pair (s, s), a wave forms and multiplies only the seven objects it stores; 0 = all eight, as in every other
+ * tile.  Same outputs bit for bit (an output's products and their order do not depend on the walk); process-wide, for
+ * A/B timing; returns the previous setting.                                                                        */
 size_t tspn_heads_pairgrid_f16x3_split_bytes(int64_t C, int64_t H);
 int tspn_heads_pairgrid_f16x3_set_force_exact(int on);
+int tspn_heads_pair_f16x3_set_diag_skip(int on);
 int tspn_heads_pairgrid_f16x3(const float* y, int64_t ldt, int64_t B, int64_t N, int64_t C, int64_t T,
                               const float* Wh, const float* bh, int64_t H, void* split_buf, size_t split_bytes,
                               float* out, void* stream);

@@ -103,6 +103,7 @@ PROTOTYPES = {
     "tspn_heads_pairgrid_f32": (_int, [_vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp]),
     "tspn_heads_pairgrid_f16x3_split_bytes": (_sz, [_i64, _i64]),
     "tspn_heads_pairgrid_f16x3_set_force_exact": (_int, [_int]),
+    "tspn_heads_pair_f16x3_set_diag_skip": (_int, [_int]),
     "tspn_heads_pairgrid_f16x3": (_int, [_vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _sz, _vp, _vp]),
     "tspn_temporal_mean_f32": (_int, [_vp, _i64, _i64, _i64, _int, _vp, _vp]),
     "tspn_temporal_sum_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp]),

@@ -31,6 +31,8 @@
 #include "tspn_common.h"
 #include "tspn_device.h"
 
+#include <type_traits>
+
 namespace {
 using namespace tspn_dev;
 
@@ -47,6 +49,7 @@ constexpr float PF_RANGE = 16384.f;   // |u|, |v| <= 2^14: relu(u + v) <= 2^15, 
 typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 std::atomic<int> g_force_exact{0};
+std::atomic<int> g_diag_skip{1};   // tspn_heads_pair_f16x3_set_diag_skip
 
 // The lo pieces of two activations whose hi pieces are the fp16 pair `h2`:  f16(as - 2^11 f32(h)) per half, `as` = 2^11 a.
 // v_fma_mixlo_f16 / v_fma_mixhi_f16 read the fp16 half as an fma operand and round the fp32 result once into the low /
@@ -161,7 +164,7 @@ __device__ __noinline__ void exact_tile(const float* __restrict__ y, int64_t ldt
 __global__ __launch_bounds__(PF_THREADS, 1) void heads_pair_f16x3_kernel(
     const float* __restrict__ y, int64_t ldt, int C, int T, int N, int H, const float* __restrict__ Wh,
     const float* __restrict__ bh, const unsigned* __restrict__ hdr, const u32x4* __restrict__ frag,
-    float* __restrict__ out, int ntb, int nob, int nsb, int64_t ngroups, int force_exact) {
+    float* __restrict__ out, int ntb, int nob, int nsb, int64_t ngroups, int force_exact, int diag_skip) {
   extern __shared__ __attribute__((aligned(16))) char smem_raw[];
   float* S = reinterpret_cast<float*>(smem_raw);   // [2][16 rows][32 ch][32 t]
 
@@ -220,93 +223,109 @@ __global__ __launch_bounds__(PF_THREADS, 1) void heads_pair_f16x3_kernel(
   const float* vrow = S + (PF_S * PF_CK + kg) * PF_T + 2 * j;        // + buffer + object * 32 channels + 4 i channels
   const float* trow = vrow + wave * PF_CK * PF_T;                    // the object row whose range this wave tracks
   float mu = 0.f, mv = 0.f;
-  for (int k = 0; k < nk; ++k) {
-    const int buf = k & 1;
-    u32x4 whn = wh, wln = wl;
-    if (k + 1 < nk) {
-      stage(buf ^ 1);
-      whn = frag[(int64_t)(k + 1) * 128 + lane];
-      wln = frag[(int64_t)(k + 1) * 128 + 64 + lane];
-    }
-    const float* ub = urow + buf * PF_STAGE;
-    const float* vb = vrow + buf * PF_STAGE;
-    const float* tb = trow + buf * PF_STAGE;
-    f32x2 u[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      u[i] = *reinterpret_cast<const f32x2*>(ub + 4 * i * PF_T);
-      const f32x2 vt = *reinterpret_cast<const f32x2*>(tb + 4 * i * PF_T);
-      mu = __builtin_elementwise_maximum(__builtin_elementwise_maximum(mu, __builtin_fabsf(u[i][0])), __builtin_fabsf(u[i][1]));
-      mv = __builtin_elementwise_maximum(__builtin_elementwise_maximum(mv, __builtin_fabsf(vt[0])), __builtin_fabsf(vt[1]));
-    }
-    const f16x8 a_hi = __builtin_bit_cast(f16x8, wh), a_lo = __builtin_bit_cast(f16x8, wl);
-    // Software pipeline over the objects: slot o forms the fragments of object o on the vector pipe while the six MFMAs
-    // of object o - 1 run, and reads the V values of object o + 1 from LDS; the two MFMAs into one acc_lo are issued
-    // two MFMAs apart.
-    f32x2 v[8], vn[8];
-    u32x4 fh[2], fl[2], gh[2], gl[2];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const f32x2*>(vb + 4 * i * PF_T);
-#pragma unroll
-    for (int o = 0; o <= PF_O; ++o) {
-      if (o + 1 < PF_O) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) vn[i] = *reinterpret_cast<const f32x2*>(vb + ((o + 1) * PF_CK + 4 * i) * PF_T);
+  // A diagonal tile (sb == ob) has no pair (s, s): wave w walks the seven objects (w + 1 + i) & 7, i = 0 .. 6, slot i
+  // into accumulator i, and forms nothing for object w.  Every other tile walks object i in slot i.  Two instances of
+  // the loop: the identity walk keeps its objects as immediate offsets of the LDS reads.
+  const bool diag = diag_skip && sb == ob;
+  auto kloop = [&](auto diag_c) {
+    constexpr bool DIAG = decltype(diag_c)::value;
+    constexpr int NS = DIAG ? PF_O - 1 : PF_O;
+    for (int k = 0; k < nk; ++k) {
+      const int buf = k & 1;
+      u32x4 whn = wh, wln = wl;
+      if (k + 1 < nk) {
+        stage(buf ^ 1);
+        whn = frag[(int64_t)(k + 1) * 128 + lane];
+        wln = frag[(int64_t)(k + 1) * 128 + 64 + lane];
       }
-      if (o < PF_O) {
-        f32x2 a[8], as[8];
+      const float* ub = urow + buf * PF_STAGE;
+      const float* vb = vrow + buf * PF_STAGE;
+      const float* tb = trow + buf * PF_STAGE;
+      auto vobj = [&](int i) { return vb + (DIAG ? ((wave + 1 + i) & 7) : i) * (PF_CK * PF_T); };
+      f32x2 u[8];
 #pragma unroll
-        for (int i = 0; i < 8; ++i) {
-          const f32x2 x = u[i] + v[i];
-          a[i] = f32x2{tspn::relu_f32(x[0]), tspn::relu_f32(x[1])};
-          as[i] = a[i] * PF_LO;
+      for (int i = 0; i < 8; ++i) {
+        u[i] = *reinterpret_cast<const f32x2*>(ub + 4 * i * PF_T);
+        const f32x2 vt = *reinterpret_cast<const f32x2*>(tb + 4 * i * PF_T);
+        mu = __builtin_elementwise_maximum(__builtin_elementwise_maximum(mu, __builtin_fabsf(u[i][0])), __builtin_fabsf(u[i][1]));
+        mv = __builtin_elementwise_maximum(__builtin_elementwise_maximum(mv, __builtin_fabsf(vt[0])), __builtin_fabsf(vt[1]));
+      }
+      const f16x8 a_hi = __builtin_bit_cast(f16x8, wh), a_lo = __builtin_bit_cast(f16x8, wl);
+      // Software pipeline over the slots: slot o forms the fragments of its object on the vector pipe while the six
+      // MFMAs of slot o - 1 run, and reads the V values of slot o + 1 from LDS; the two MFMAs into one acc_lo are
+      // issued two MFMAs apart.  The add and the 2^11 stay packed fp32 (v_pk_add_f32, v_pk_mul_f32): the same chain in
+      // single fp32 instructions, and with the 2^11 carried through an fma, timed slower here (profiles/r33/README.md).
+      f32x2 v[8], vn[8];
+      u32x4 fh[2], fl[2], gh[2], gl[2];
+      {
+        const float* vp = vobj(0);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) v[i] = *reinterpret_cast<const f32x2*>(vp + 4 * i * PF_T);
+      }
+#pragma unroll
+      for (int o = 0; o <= NS; ++o) {
+        if (o + 1 < NS) {
+          const float* vp = vobj(o + 1);
+#pragma unroll
+          for (int i = 0; i < 8; ++i) vn[i] = *reinterpret_cast<const f32x2*>(vp + 4 * i * PF_T);
         }
+        if (o < NS) {
+          f32x2 a[8], as[8];
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) {
-          unsigned ph[4], pl[4];
-#pragma unroll
-          for (int ip = 0; ip < 4; ++ip) {
-            // ah = f16(a) (round to nearest), al = f16(2^11 a - 2^11 ah): the fma is exact before its one rounding to fp16
-            const f16x2 h = __builtin_convertvector(f32x2{a[2 * ip][cb], a[2 * ip + 1][cb]}, f16x2);
-            ph[ip] = __builtin_bit_cast(unsigned, h);
-            pl[ip] = split_lo(ph[ip], as[2 * ip][cb], as[2 * ip + 1][cb]);
+          for (int i = 0; i < 8; ++i) {
+            const f32x2 x = u[i] + v[i];
+            a[i] = f32x2{tspn::relu_f32(x[0]), tspn::relu_f32(x[1])};
+            as[i] = a[i] * PF_LO;
           }
-          gh[cb] = u32x4{ph[0], ph[1], ph[2], ph[3]};
-          gl[cb] = u32x4{pl[0], pl[1], pl[2], pl[3]};
+#pragma unroll
+          for (int cb = 0; cb < 2; ++cb) {
+            unsigned ph[4], pl[4];
+#pragma unroll
+            for (int ip = 0; ip < 4; ++ip) {
+              // ah = f16(a) (round to nearest), al = f16(2^11 a - 2^11 ah): the fma is exact before its one rounding to fp16
+              const f16x2 h = __builtin_convertvector(f32x2{a[2 * ip][cb], a[2 * ip + 1][cb]}, f16x2);
+              ph[ip] = __builtin_bit_cast(unsigned, h);
+              pl[ip] = split_lo(ph[ip], as[2 * ip][cb], as[2 * ip + 1][cb]);
+            }
+            gh[cb] = u32x4{ph[0], ph[1], ph[2], ph[3]};
+            gl[cb] = u32x4{pl[0], pl[1], pl[2], pl[3]};
+          }
         }
-      }
-      if (o > 0) {
-        const f16x8 h0 = __builtin_bit_cast(f16x8, fh[0]), h1 = __builtin_bit_cast(f16x8, fh[1]);
-        const f16x8 l0 = __builtin_bit_cast(f16x8, fl[0]), l1 = __builtin_bit_cast(f16x8, fl[1]);
-        acc_hi[o - 1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, h0, acc_hi[o - 1][0], 0, 0, 0);
-        acc_lo[o - 1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, l0, acc_lo[o - 1][0], 0, 0, 0);
-        acc_hi[o - 1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, h1, acc_hi[o - 1][1], 0, 0, 0);
-        acc_lo[o - 1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, l1, acc_lo[o - 1][1], 0, 0, 0);
-        acc_lo[o - 1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo, h0, acc_lo[o - 1][0], 0, 0, 0);
-        acc_lo[o - 1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo, h1, acc_lo[o - 1][1], 0, 0, 0);
-      }
-      if (o > 0 && o < PF_O) {
+        if (o > 0) {
+          const f16x8 h0 = __builtin_bit_cast(f16x8, fh[0]), h1 = __builtin_bit_cast(f16x8, fh[1]);
+          const f16x8 l0 = __builtin_bit_cast(f16x8, fl[0]), l1 = __builtin_bit_cast(f16x8, fl[1]);
+          acc_hi[o - 1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, h0, acc_hi[o - 1][0], 0, 0, 0);
+          acc_lo[o - 1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, l0, acc_lo[o - 1][0], 0, 0, 0);
+          acc_hi[o - 1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, h1, acc_hi[o - 1][1], 0, 0, 0);
+          acc_lo[o - 1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_hi, l1, acc_lo[o - 1][1], 0, 0, 0);
+          acc_lo[o - 1][0] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo, h0, acc_lo[o - 1][0], 0, 0, 0);
+          acc_lo[o - 1][1] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a_lo, h1, acc_lo[o - 1][1], 0, 0, 0);
+        }
+        if (o > 0 && o < NS) {
 #define TSPN_G                                         \
   __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   \
   __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);   \
   __builtin_amdgcn_sched_group_barrier(0x002, 10, 0);
-        TSPN_G TSPN_G TSPN_G TSPN_G TSPN_G TSPN_G
+          TSPN_G TSPN_G TSPN_G TSPN_G TSPN_G TSPN_G
 #undef TSPN_G
-      }
-      __builtin_amdgcn_sched_barrier(0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int cb = 0; cb < 2; ++cb) {
-        fh[cb] = gh[cb];
-        fl[cb] = gl[cb];
-      }
+        for (int cb = 0; cb < 2; ++cb) {
+          fh[cb] = gh[cb];
+          fl[cb] = gl[cb];
+        }
 #pragma unroll
-      for (int i = 0; i < 8; ++i) v[i] = vn[i];
+        for (int i = 0; i < 8; ++i) v[i] = vn[i];
+      }
+      wh = whn;
+      wl = wln;
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's LDS-DMA pieces have landed before the barrier publishes them
+      __syncthreads();
     }
-    wh = whn;
-    wl = wln;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's LDS-DMA pieces have landed before the barrier publishes them
-    __syncthreads();
-  }
+  };
+  if (diag) kloop(std::true_type{});
+  else kloop(std::false_type{});
 
   // ---- range vote over the staged values that a written output reads: frame pair in range, row a real tracklet
   const int tA = t0 + 2 * j;
@@ -326,8 +345,9 @@ __global__ __launch_bounds__(PF_THREADS, 1) void heads_pair_f16x3_kernel(
     bias[r] = (h < H && bh) ? bh[h] : 0.f;
   }
 #pragma unroll
-  for (int o = 0; o < PF_O; ++o) {
-    const int ot = ob * PF_O + o;
+  for (int o = 0; o < PF_O; ++o) {             // slot o holds object (w + 1 + o) & 7 of a diagonal tile, object o elsewhere
+    if (diag && o == PF_O - 1) continue;
+    const int ot = ob * PF_O + (diag ? (wave + 1 + o) & 7 : o);
     if (ot >= N || ot == s) continue;
     const int64_t p = b * N * (int64_t)(N - 1) + (int64_t)s * (N - 1) + ot - (ot > s ? 1 : 0);
 #pragma unroll
@@ -384,7 +404,7 @@ int tspn::heads_pair_f16x3(const float* y, int64_t ldt, int64_t B, int64_t N, in
   if (int rc = lds.ensure(reinterpret_cast<const void*>(heads_pair_f16x3_kernel), PF_SMEM, what)) return rc;
   hipLaunchKernelGGL(heads_pair_f16x3_kernel, dim3((unsigned)nwg), dim3(PF_THREADS), PF_SMEM, s, y, ldt, (int)C, (int)T,
                      (int)N, (int)H, Wh, bh, hdr, frag, out, ntb, nob, nsb, ngroups,
-                     g_force_exact.load(std::memory_order_relaxed));
+                     g_force_exact.load(std::memory_order_relaxed), g_diag_skip.load(std::memory_order_relaxed));
   return tspn::check_launch(what);
 }
 
@@ -395,6 +415,11 @@ extern "C" size_t tspn_heads_pairgrid_f16x3_split_bytes(int64_t C, int64_t H) {
 extern "C" int tspn_heads_pairgrid_f16x3_set_force_exact(int on) {
   TSPN_REQUIRE(on == 0 || on == 1, TSPN_EINVAL, "tspn_heads_pairgrid_f16x3_set_force_exact: on must be 0 or 1");
   return g_force_exact.exchange(on, std::memory_order_relaxed);
+}
+
+extern "C" int tspn_heads_pair_f16x3_set_diag_skip(int on) {
+  TSPN_REQUIRE(on == 0 || on == 1, TSPN_EINVAL, "tspn_heads_pair_f16x3_set_diag_skip: on must be 0 or 1");
+  return g_diag_skip.exchange(on, std::memory_order_relaxed);
 }
 
 extern "C" int tspn_heads_pairgrid_f16x3(const float* y, int64_t ldt, int64_t B, int64_t N, int64_t C, int64_t T,

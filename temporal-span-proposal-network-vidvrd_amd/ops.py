@@ -15,7 +15,7 @@ from . import _abi
 __all__ = [
     "predicate_head", "feature_preprocess_", "ppn_pair_matrix_topk", "traj_iou", "traj_iou_tail", "pair_index",
     "pair_gather", "pack_conv3", "conv3", "conv3_tc", "pack_conv3_wino63", "conv3_tc_wino63", "pack_conv3_wino63_f16x3", "conv3_tc_wino63_f16x3", "heads", "heads_pairgrid", "heads_pairgrid_f16x3", "heads_pairgrid_f16x3_split_bytes",
-    "heads_pairgrid_f16x3_set_force_exact", "temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
+    "heads_pairgrid_f16x3_set_force_exact", "heads_pair_f16x3_set_diag_skip","temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
     "forward_fused", "temporal_encoder_heads", "fused_workspace_bytes", "fused_bf16_workspace_bytes", "decode_topk", "decode_spans", "decode_span_relations",
     "span_anchor_labels", "span_loss", "span_anchor_sample", "pair_labels",
     "cast_bf16", "pack_conv3_bf16", "pack_heads_bf16", "conv3_tc_bf16", "heads_pairgrid_bf16",
@@ -635,6 +635,13 @@ def heads_pairgrid_f16x3_set_force_exact(on):
     """1 = every tile of the split-fp16 pair stage takes its fp32 chain (tests), 0 = default.  Process-wide; returns the
     previous setting."""
     return _toggle("tspn_heads_pairgrid_f16x3_set_force_exact", on)
+
+
+def heads_pair_f16x3_set_diag_skip(on):
+    """1 = in a diagonal tile of the split-fp16 pair stage a wave walks only the seven objects it stores (default), 0 =
+    all eight as in every other tile (tspn_heads_pair_f16x3_set_diag_skip); same outputs bit for bit.  Process-wide;
+    returns the previous setting."""
+    return _toggle("tspn_heads_pair_f16x3_set_diag_skip", on)
 
 
 def heads_pairgrid_f16x3(y, B, N, head_w, head_b, T=None, split_buf=None, out=None):

@@ -1,13 +1,14 @@
 #!/usr/bin/env python
 """Isolated timing of the canonical pair stage at one shape (default: config 2, 16 videos): the split-fp16 MFMA form
 (tspn_heads_pairgrid_f16x3, with its two pack kernels) against heads_pairgrid4_kernel (with its pack kernel), both in one
-process, taking turns, HIP events around each launch.
+process, taking turns, HIP events around each launch.  The split-fp16 form is timed with its diagonal-tile skip
+(ops.heads_pair_f16x3_set_diag_skip) on, the default, and off, the walk of all eight objects in every tile.
 
 heads_pairgrid4_kernel has no entry of its own: it is reached through the fused pass with direct-tap conv weights, and
 timed from the pass's `conv end` event to an event recorded behind the pass, so the interval holds the pair stage and
 nothing else.  Prints one JSON line.
 
-    python tools/bench_pair_stage_f16x3.py [--B 16 --N 32 --T 150 --D 2048 --iters 10 --rounds 3]
+    python tools/bench_pair_stage_f16x3.py [--B 16 --N 32 --T 150 --D 2048 --iters 10 --rounds 3 --no-fp32]
 """
 import argparse
 import json
@@ -31,6 +32,7 @@ def main():
     ap.add_argument("--K", type=int, default=132)
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--no-fp32", action="store_true", help="time the split-fp16 form only (a counter pass over it alone)")
     a = ap.parse_args()
     import tspn_mi355x as tspn
     ops = tspn.ops
@@ -62,21 +64,31 @@ def main():
         torch.cuda.synchronize()
         return ev[1].elapsed_time(ev[2])
 
-    def f16_once():
+    def f16_once(skip=1):
+        prev = ops.heads_pair_f16x3_set_diag_skip(skip)
         ev[2].record()
         ops.heads_pairgrid_f16x3(y, B, N, head_w, head_b, T=T, split_buf=split, out=out)
         ev[3].record()
         torch.cuda.synchronize()
+        ops.heads_pair_f16x3_set_diag_skip(prev)
         return ev[2].elapsed_time(ev[3])
 
-    fp32_once(), f16_once()           # warm-up (module load, LDS limits)
-    t32, t16 = [], []
+    if not a.no_fp32:
+        fp32_once()                   # warm-up (module load, LDS limits)
+    f16_once(1), f16_once(0)
+    t32, t16, t16_off = [], [], []
     for _ in range(a.rounds):
-        t32 += [fp32_once() for _ in range(a.iters)]
-        t16 += [f16_once() for _ in range(a.iters)]
-    summ = lambda v: {"mean_ms": statistics.mean(v), "sigma_ms": statistics.pstdev(v), "min_ms": min(v), "max_ms": max(v)}
-    print(json.dumps({"shape": {"B": B, "N": N, "T": T, "D": D, "C": C, "H": H}, "launches_each": len(t32),
-                      "heads_pairgrid4": summ(t32), "heads_pair_f16x3": summ(t16)}))
+        if not a.no_fp32:
+            t32 += [fp32_once() for _ in range(a.iters)]
+        t16 += [f16_once(1) for _ in range(a.iters)]
+        t16_off += [f16_once(0) for _ in range(a.iters)]
+    summ = lambda v: {"mean_ms": statistics.mean(v), "median_ms": statistics.median(v), "sigma_ms": statistics.pstdev(v),
+                      "min_ms": min(v), "max_ms": max(v)}
+    res = {"shape": {"B": B, "N": N, "T": T, "D": D, "C": C, "H": H}, "launches_each": len(t16),
+           "heads_pair_f16x3": summ(t16), "heads_pair_f16x3_diag_skip_off": summ(t16_off)}
+    if t32:
+        res["heads_pairgrid4"] = summ(t32)
+    print(json.dumps(res))
 
 
 if __name__ == "__main__":
