@@ -218,7 +218,7 @@ int tspn_traj_iou_f32(const float* boxes1, int64_t N1, const float* boxes2, int6
  * guarantees len_a[u] <= L); b [N,L,4] = the current segment's tracklets; out [U,N] float32.  Rounding
  * recipe of the reference chain kept to the bit: coordinates max/min stored as float32, intersection in
  * float32 in frame order, areas float64 in numpy's pairwise summation order, quotient in float64 stored as
- * float32.  The length check is the caller's: this function reads len_a[u] frames of both rows.           */
+ * float32.  The length check is the caller's: this function reads len_a[u] frames of both rows.  L < 2^31.  */
 int tspn_traj_iou_tail_f64(const double* a, const int32_t* len_a, const double* b, int64_t U, int64_t N,
                            int64_t L, float* out, void* stream);
 
@@ -1013,6 +1013,31 @@ int tspn_pair_labels_f32(const int64_t* pairs, const int64_t* pair_off, const in
                          const int64_t* inst_off, const int64_t* seg_frames, int64_t S, int64_t P, int64_t M, int64_t R,
                          int64_t K, int64_t G, double iou_thres, int merge, float* labels, int64_t* spans,
                          int32_t* span_count, int32_t* inst_cols, void* stream);
+
+/* ---- span-bounded association of one segment (csrc/spanmatch/tspn_span_match.hip) --------------------------------
+ * Build-defined (DESIGN.md 2 "span match"): which relation of the previous segment every span-bounded prediction of a
+ * segment extends, decided before the host's loop.  A span-bounded prediction owns its two trajectories, so the
+ * decision depends only on state fixed when the segment starts.  Frames are local to the segment (L frames, N tracklets).
+ *   rel_boxes float64 [U, 2, L, 4]: role 0 = subject, 1 = object; index f = the relation's box at frame f of THIS segment
+ *   (only the frames of a candidate's window are read); rel_range int32 [U, 2, 2]: per role [start, end) =
+ *   max(pstart - fstart, 0), max(pend - fstart, 0), end may exceed L; rel_fend int32 [U] = r.fend - fstart; rel_triplet
+ *   int64 [U, 3]; trk_boxes float64 [N, L, 4]; pred_triplet int64 [P, 3]; pred_pair int32 [P, 2]; pred_span int32 [P, 2]
+ *   = [a, e).  Rows u are in candidate order (mean confidence, descending and stable), predictions in score order.
+ *   (u, p) is a candidate pair iff the triplets are equal, a < rel_fend[u], for both roles start <= a < end <= e,
+ *   0 <= a < e <= L and both pair indices lie in [0, N); nothing else reads a box.
+ *   iou float32 [U, P, 2]: for a candidate pair and role c the IoU of rel_boxes[u, c, a:end] against
+ *   trk_boxes[pred_pair[p, c], a:end] with the rounding recipe of tspn_traj_iou_tail_f64, the float64 areas summed in
+ *   numpy's pairwise order over the window that starts at a; -1 for both roles of any other pair.
+ *   match int32 [P]: in order of p, the smallest u not yet taken with iou[u, p, 0] >= iou_thr and iou[u, p, 1] >= iou_thr
+ *   (compared in float64: NaN fails, -1 fails for iou_thr > -1), which is then taken; -1 for none.
+ * Two launches (the pairs; one workgroup for the greedy pass), no allocation, synchronisation, memset or scratch buffer;
+ * every element of iou and match is written.  P == 0 launches nothing; U == 0 with P > 0 writes match = -1.  Limits:
+ * sizes >= 0, iou_thr finite, U <= 65536 (the taken flags live in 8 KB of LDS), U * P < 2^31, N and L < 2^31.  An
+ * operand without elements may be NULL. */
+int tspn_span_match_f64(const double* rel_boxes, const int32_t* rel_range, const int32_t* rel_fend,
+                        const int64_t* rel_triplet, const double* trk_boxes, const int64_t* pred_triplet,
+                        const int32_t* pred_pair, const int32_t* pred_span, int64_t U, int64_t P, int64_t N, int64_t L,
+                        double iou_thr, float* iou, int32_t* match, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,6 +13,9 @@ reference does per prediction are done once per segment because they cannot chan
 stable sort of the previous segment's relations by mean confidence (a relation's confidences change only
 when it is extended, and then it leaves that list), and the scan for relations with the same triplet
 (grouped once, order kept).  Without `device` the same loop calls the host IoU per candidate.
+Span-bounded predictions own their trajectories, so for them even the loop's decisions are fixed when a segment starts:
+with `device_spans=True` one `ops.span_match` call per segment (csrc/spanmatch/) returns which relation every prediction
+extends, and the loop only cuts and merges (`_span_match_segment`).
 
 Behaviour reproduced as is (each checked against the reference's own code by tests/golden/g9):
   * segments are visited in order of `int(fstart)`; per segment the predictions are sorted by score,
@@ -300,8 +303,48 @@ class _SegmentIoUTable:
         return ent[1][int(j)]
 
 
+def _span_match_segment(device, rows, preds, trajs, fstart, fend):
+    """The decisions of one segment's loop for span-bounded predictions, in one `ops.span_match` call: int32 [P], the
+    index into `rows` of the relation prediction p extends, -1 where it opens a relation.
+
+    `rows`: the previous segment's relations a prediction can meet, in candidate order (mean confidence, descending and
+    stable); `preds`: the segment's predictions in score order, spans and pair indices already checked against `trajs`.
+    A span-bounded prediction owns its trajectories, so none of what `both_overlap` reads changes inside the segment
+    except that an extended relation leaves the list - which the device's greedy pass does too."""
+    import torch
+
+    from . import ops
+    U, P, N, L = len(rows), len(preds), len(trajs), int(fend) - int(fstart)
+    f64 = np.zeros((U * 2 + N, L, 4), dtype=np.float64)         # rel_boxes [U,2,L,4], then trk_boxes [N,L,4]
+    i32 = np.zeros((U * 5 + P * 4,), dtype=np.int32)            # rel_range [U,2,2], rel_fend [U], pred_pair, pred_span [P,2]
+    i64 = np.zeros((U + P, 3), dtype=np.int64)                  # rel_triplet [U,3], pred_triplet [P,3]
+    rng = i32[:U * 4].reshape(U, 2, 2)
+    for u, r in enumerate(rows):
+        for c, t in enumerate((r.straj, r.otraj)):
+            rng[u, c] = max(t.pstart - fstart, 0), max(t.pend - fstart, 0)
+            lo, hi = max(t.pstart, fstart), min(t.pend, fend)
+            if hi > lo:                                          # the relation's boxes on this segment's frames
+                f64[2 * u + c, lo - fstart:hi - fstart] = t.rois[lo - t.pstart:hi - t.pstart]
+        i32[U * 4 + u] = r.fend - fstart
+        i64[u] = _triplet_key(r.triplet())
+    for j, t in enumerate(trajs):
+        if t.rois.shape[0] != L:
+            raise ValueError(f"tracklet {j} of segment [{fstart}, {fend}) has {t.rois.shape[0]} boxes")
+        f64[2 * U + j] = t.rois
+    pair, span = i32[U * 5:U * 5 + P * 2].reshape(P, 2), i32[U * 5 + P * 2:].reshape(P, 2)
+    for p, pred in enumerate(preds):
+        i64[U + p] = _triplet_key(pred[1])
+        pair[p] = [int(v) % N for v in pred[2]]                  # checked by the caller; a negative index counts from the end
+        span[p] = np.asarray(pred[3]).tolist()
+    dev = torch.device(device)
+    d64, d32, dtr = (torch.from_numpy(x).to(dev) for x in (f64, i32, i64))
+    match, _ = ops.span_match(d64[:2 * U].view(U, 2, L, 4), d32[:U * 4].view(U, 2, 2), d32[U * 4:U * 5], dtr[:U],
+                              d64[2 * U:], dtr[U:], d32[U * 5:U * 5 + P * 2].view(P, 2), d32[U * 5 + P * 2:].view(P, 2))
+    return match.cpu().numpy()
+
+
 def greedy_relational_association(dataset, short_term_relations, max_traj_num_in_clip=100, trajectories=None,
-                                  device=None, stats=None):
+                                  device=None, stats=None, device_spans=False):
     """Reference `greedy_relational_association` (association.py:117-175).
 
     `short_term_relations`: list of `((vid, fstart, fend), (pred_list, iou, trackid))` with
@@ -317,9 +360,16 @@ def greedy_relational_association(dataset, short_term_relations, max_traj_num_in
     relation `r` of the previous segment only if its trajectories start inside r's and end no earlier
     (r.straj.pstart <= pstart < r.straj.pend <= pend, the same for the object) - so a span that stops before its
     segment's end is not continued - and otherwise opens a new relation; the IoU test and everything else are as for
-    3-tuples, which take the reference's path unchanged.  `device=` cannot serve 4-tuples (ValueError): its IoU table
-    holds one row per whole tracklet of the segment, not per prediction's cut.
-    `stats`: optional dict, receives counters (`iou_launches`, `iou_lookups`, `iou_host_rows`, `segments`).
+    3-tuples, which take the reference's path unchanged.  `device=` alone cannot serve 4-tuples (ValueError): its IoU
+    table holds one row per whole tracklet of the segment, not per prediction's cut.
+    `device_spans=True` (needs `device`): a video of 4-tuples only is matched on the device, one `ops.span_match` call per
+    segment that decides every prediction of the segment at once (the IoUs on each prediction's own window, the gate
+    tests and the greedy scan over the candidates); the loop then only cuts and merges; same results as `device=None`.  A
+    video of 3-tuples only takes the `device=` path unchanged; a video that mixes both is refused (ValueError): 3-tuples
+    share trajectories between relations, which the one-call match cannot see - `device=None` serves such a video.
+    `stats`: optional dict, receives counters (`iou_launches`, `iou_lookups`, `iou_host_rows`, `segments`); with
+    `device_spans` on a spanned video `iou_launches` counts the `span_match` calls, `iou_lookups` the (relation,
+    prediction) pairs they decided and `iou_host_rows` is 0.
     Returns the list of serialised video relations (`dataset` supplies the names; None keeps ids)."""
     if trajectories is None:
         provider = load_trajectories
@@ -327,7 +377,16 @@ def greedy_relational_association(dataset, short_term_relations, max_traj_num_in
         provider = trajectories
     else:
         provider = lambda vid, fs, fe: trajectories[(vid, fs, fe)]  # noqa: E731
-    if device is not None and any(len(p) == 4 for _, prediction in short_term_relations for p in prediction[0]):
+    spanned_video = False
+    if device_spans:
+        if device is None:
+            raise ValueError("greedy_relational_association: device_spans=True needs a device")
+        sizes = {len(p) for _, prediction in short_term_relations for p in prediction[0]}
+        if 3 in sizes and 4 in sizes:
+            raise ValueError("greedy_relational_association: device_spans=True cannot serve a video that mixes whole-segment "
+                             "(3-tuple) and span-bounded (4-tuple) predictions: use device=None")
+        spanned_video = 4 in sizes
+    elif device is not None and any(len(p) == 4 for _, prediction in short_term_relations for p in prediction[0]):
         raise ValueError("greedy_relational_association: span-bounded predictions (4-tuples) need device=None: the batched "
                          "IoU table is per whole tracklet")
     short_term_relations.sort(key=lambda x: int(x[0][1]))   # in place, like the reference
@@ -348,19 +407,45 @@ def greedy_relational_association(dataset, short_term_relations, max_traj_num_in
         # the sort is stable, so once per segment gives the same order; likewise the same-triplet scan, grouped once
         by_triplet = {}
         table = None
+        match = rows = cuts = None
         if i > 0 and sorted_pred_list:
             last_modify_rel_list.sort(key=lambda r: r.mean_confs(), reverse=True)
             for r in last_modify_rel_list:
                 by_triplet.setdefault(_triplet_key(r.triplet()), []).append(r)
-            if device is not None and last_modify_rel_list:
+            if spanned_video and last_modify_rel_list:
+                # every decision of this segment's loop in one call: the spans and pair indices are checked first, in the
+                # loop's order (the host path's errors), then the relations a prediction can meet, in candidate order
+                cuts = []
+                for pred in sorted_pred_list:
+                    straj, otraj = trajs[int(pred[2][0])], trajs[int(pred[2][1])]
+                    cuts.append((_span_cut(straj, fstart, pred[3]), _span_cut(otraj, fstart, pred[3])))
+                wanted = {_triplet_key(p[1]) for p in sorted_pred_list}
+                rows = [r for r in last_modify_rel_list if _triplet_key(r.triplet()) in wanted]
+                if rows:
+                    match = _span_match_segment(device, rows, sorted_pred_list, trajs, fstart, fend)
+                    launches += 1
+                    lookups += len(rows) * len(sorted_pred_list)
+                else:                                            # no relation carries a triplet of this segment
+                    match = np.full((len(sorted_pred_list),), -1, dtype=np.int32)
+            elif device is not None and last_modify_rel_list:
                 table = _SegmentIoUTable(device, trajs, fstart, fend)
                 wanted = {_triplet_key(p[1]) for p in sorted_pred_list}
                 for key in wanted:                                   # only relations a prediction can meet
                     for r in by_triplet.get(key, ()):
                         table.add((r.straj, r.otraj))
-        for pred in sorted_pred_list:
+        for k, pred in enumerate(sorted_pred_list):
             conf_score = pred[0]
             s_cid, pid, o_cid = pred[1]
+            if match is not None:                                # decided on the device: cut, then extend or open
+                straj, otraj = cuts[k]
+                if match[k] >= 0:
+                    r = rows[match[k]]
+                    r.extend(straj, otraj, conf_score)
+                else:
+                    r = VideoRelation(vid, s_cid, pid, o_cid, straj, otraj)   # confs = 1 (reference default)
+                    video_relation_list.append(r)
+                cur_modify_rel_list.append(r)
+                continue
             s_idx, o_idx = pred[2]
             straj, otraj = trajs[int(s_idx)], trajs[int(o_idx)]
             spanned = len(pred) == 4
@@ -435,7 +520,7 @@ def short_term_relations_from_arrays(segments, scores, triplets, pairs, boxes=No
     return rels, trajs
 
 
-def _worker_main(conn, device, max_traj_num_in_clip):
+def _worker_main(conn, device, max_traj_num_in_clip, device_spans=False):
     import contextlib
     import time
     scope = contextlib.nullcontext
@@ -460,7 +545,8 @@ def _worker_main(conn, device, max_traj_num_in_clip):
                 rels, trajs = short_term_relations_from_arrays(**rels)
             with scope():
                 out = greedy_relational_association(None, rels, max_traj_num_in_clip=max_traj_num_in_clip,
-                                                    trajectories=trajs, device=device, stats=stats)
+                                                    trajectories=trajs, device=device, stats=stats,
+                                                    device_spans=device_spans)
             if out_path:
                 with open(out_path, "w") as fh:                 # what the reference's driver stores per video (base.py:107-113)
                     json.dump(out, fh)
@@ -469,17 +555,18 @@ def _worker_main(conn, device, max_traj_num_in_clip):
             conn.send((key, None, (time.perf_counter() - t0) * 1e3, {}, f"{type(exc).__name__}: {exc}"))
 
 
-def _worker_connect(address, authkey, device, max_traj_num_in_clip):
+def _worker_connect(address, authkey, device, max_traj_num_in_clip, device_spans=False):
     """Entry point of the worker process (started by AssociationWorker)."""
     from multiprocessing.connection import Client
     with Client(address, family="AF_UNIX", authkey=authkey) as conn:
-        _worker_main(conn, device, max_traj_num_in_clip)
+        _worker_main(conn, device, max_traj_num_in_clip, device_spans)
 
 
 class AssociationWorker:
     """`greedy_relational_association` of whole videos in a worker process (same results: it IS that function).
 
         w = AssociationWorker(device="cuda:0")            # device=None: host IoUs
+        w = AssociationWorker(device="cuda:0", device_spans=True)   # span-bounded predictions matched on the device
         w.submit(vid, short_term_relations, trajectories) # returns at once; jobs run in order
         vid, relations, ms, stats = w.result()            # blocks (without the interpreter lock) until the oldest job is done
 
@@ -488,7 +575,7 @@ class AssociationWorker:
     comes back (a VidOR-scale video's relations are ~30 MB of Python lists: leave them in the worker when the file is
     what is wanted).  The worker owns its own HIP context and stream when `device` is given."""
 
-    def __init__(self, device=None, max_traj_num_in_clip=100):
+    def __init__(self, device=None, max_traj_num_in_clip=100, device_spans=False):
         # A plain child process that connects back over a Unix socket -- not multiprocessing.Process: its spawn method
         # re-imports the parent's __main__ in the child (a second run of the driver script unless it is guarded; impossible
         # from an interactive parent), and fork would copy a process that holds a HIP context.
@@ -502,8 +589,9 @@ class AssociationWorker:
         authkey = secrets.token_bytes(16)
         root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         code = ("import sys; sys.path.insert(0, %r); import tspn_mi355x; "
-                "tspn_mi355x.association._worker_connect(%r, bytes.fromhex(%r), %r, %d)"
-                % (root, address, authkey.hex(), None if device is None else str(device), int(max_traj_num_in_clip)))
+                "tspn_mi355x.association._worker_connect(%r, bytes.fromhex(%r), %r, %d, %r)"
+                % (root, address, authkey.hex(), None if device is None else str(device), int(max_traj_num_in_clip),
+                   bool(device_spans)))
         with Listener(address, family="AF_UNIX", authkey=authkey) as listener:
             self._proc = subprocess.Popen([sys.executable, "-c", code])
             listener._listener._socket.settimeout(120)          # a child that dies before connecting must not hang us
@@ -526,7 +614,7 @@ class AssociationWorker:
         pickling a VidOR-scale video's 12 000 predictions as tuples of small arrays costs the driving process ~80 ms
         and the worker as much again; as five arrays it is under a millisecond."""
         arrays = {"segments": list(segments), "scores": scores, "triplets": triplets, "pairs": pairs, "boxes": boxes}
-        if spans is not None:                                    # span-bounded predictions: a worker with device=None only
+        if spans is not None:                                    # span-bounded predictions: a host worker, or device_spans=True
             arrays["spans"] = spans
         self._conn.send((key, arrays, None, out_path, bool(return_relations)))
         self._inflight += 1

@@ -17,7 +17,7 @@ __all__ = [
     "pair_gather", "pack_conv3", "conv3", "conv3_tc", "pack_conv3_wino63", "conv3_tc_wino63", "pack_conv3_wino63_f16x3", "conv3_tc_wino63_f16x3", "heads", "heads_pairgrid", "heads_pairgrid_f16x3", "heads_pairgrid_f16x3_split_bytes",
     "heads_pairgrid_f16x3_set_force_exact", "heads_pair_f16x3_set_diag_skip","temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
     "forward_fused", "temporal_encoder_heads", "fused_workspace_bytes", "fused_bf16_workspace_bytes", "decode_topk", "decode_spans", "decode_span_relations",
-    "span_anchor_labels", "span_loss", "span_anchor_sample", "pair_labels",
+    "span_anchor_labels", "span_loss", "span_anchor_sample", "pair_labels", "span_match",
     "cast_bf16", "pack_conv3_bf16", "pack_heads_bf16", "conv3_tc_bf16", "heads_pairgrid_bf16",
     "pair_plan", "heads_pairlist_bf16",
     "transpose_cast_bf16", "temporal_encoder_heads_bf16",
@@ -925,6 +925,49 @@ def pair_labels(pairs, trackid, iou, insts, num_predicates, iou_thres=0.5, merge
                                                PAIR_LABEL_MERGES[merge], _p(labels), _p(spans), _p(span_count),
                                                _p(inst_cols), _stream()))
     return labels, spans, span_count, inst_cols
+
+
+def span_match(rel_boxes, rel_range, rel_fend, rel_triplet, trk_boxes, pred_triplet, pred_pair, pred_span, iou_thr=0.5):
+    """Span-bounded association of one segment (tspn_span_match_f64, DESIGN.md §2 "span match"): which relation of the
+    previous segment every span-bounded prediction extends, in one call.
+
+    rel_boxes float64 [U,2,L,4] (role 0 subject, 1 object; index f = frame f of this segment), rel_range int32 [U,2,2]
+    (per role [start, end) in segment-local frames), rel_fend int32 [U], rel_triplet int64 [U,3]: the candidate relations
+    in candidate order; trk_boxes float64 [N,L,4]: the segment's tracklets; pred_triplet int64 [P,3], pred_pair int32
+    [P,2], pred_span int32 [P,2] = [a, e): the predictions in score order.
+    Returns (match int32 [P], iou float32 [U,P,2]): match[p] = the first relation still free whose two window IoUs reach
+    iou_thr, -1 for none; iou = -1 for a pair the gates refuse.  Nothing is synchronised."""
+    who = "span_match"
+    _dev(rel_boxes, f"{who}: rel_boxes", torch.float64); _dev(trk_boxes, f"{who}: trk_boxes", torch.float64)
+    _dev(rel_range, f"{who}: rel_range", torch.int32); _dev(rel_fend, f"{who}: rel_fend", torch.int32)
+    _dev(rel_triplet, f"{who}: rel_triplet", torch.int64); _dev(pred_triplet, f"{who}: pred_triplet", torch.int64)
+    _dev(pred_pair, f"{who}: pred_pair", torch.int32); _dev(pred_span, f"{who}: pred_span", torch.int32)
+    if rel_boxes.dim() != 4 or rel_boxes.shape[1] != 2 or rel_boxes.shape[3] != 4 or trk_boxes.dim() != 3 \
+            or trk_boxes.shape[2] != 4 or trk_boxes.shape[1] != rel_boxes.shape[2]:
+        raise ValueError(f"{who}: rel_boxes [U,2,L,4] and trk_boxes [N,L,4] expected, got {tuple(rel_boxes.shape)} and "
+                         f"{tuple(trk_boxes.shape)}")
+    U, _, L, _ = rel_boxes.shape
+    N = trk_boxes.shape[0]
+    if rel_range.shape != (U, 2, 2) or rel_fend.shape != (U,) or rel_triplet.shape != (U, 3):
+        raise ValueError(f"{who}: rel_range must be [{U},2,2], rel_fend [{U}] and rel_triplet [{U},3], got "
+                         f"{tuple(rel_range.shape)}, {tuple(rel_fend.shape)}, {tuple(rel_triplet.shape)}")
+    if pred_triplet.dim() != 2 or pred_triplet.shape[1] != 3:
+        raise ValueError(f"{who}: pred_triplet must be [P,3], got {tuple(pred_triplet.shape)}")
+    P = pred_triplet.shape[0]
+    if pred_pair.shape != (P, 2) or pred_span.shape != (P, 2):
+        raise ValueError(f"{who}: pred_pair and pred_span must be [{P},2], got {tuple(pred_pair.shape)} and "
+                         f"{tuple(pred_span.shape)}")
+    thr = float(iou_thr)
+    if thr != thr or thr in (float("inf"), float("-inf")):
+        raise ValueError(f"{who}: iou_thr must be finite, got {iou_thr}")
+    if U > 65536 or U * P >= 2 ** 31:
+        raise ValueError(f"{who}: needs U <= 65536 and U * P < 2^31, got U = {U}, P = {P}")
+    iou = torch.empty((U, P, 2), dtype=torch.float32, device=rel_boxes.device)
+    match = torch.empty((P,), dtype=torch.int32, device=rel_boxes.device)
+    _abi.check(_abi.lib().tspn_span_match_f64(_p(rel_boxes), _p(rel_range), _p(rel_fend), _p(rel_triplet), _p(trk_boxes),
+                                              _p(pred_triplet), _p(pred_pair), _p(pred_span), U, P, N, L, thr, _p(iou),
+                                              _p(match), _stream()))
+    return match, iou
 
 
 def _fused_desc(feats, pairs, B, N, conv_packed, conv_bias, head_w, head_b, cls_w, cls_b):
