@@ -920,6 +920,38 @@ int tspn_eval_viou_f64(const double* boxes, const int64_t* traj, const double* v
 int tspn_eval_greedy_match_f64(const double* ov, const int64_t* groups, int64_t n_groups, int64_t max_group_gt,
                                double viou_threshold, uint8_t* det_ws, int8_t* hit, int32_t* match, void* stream);
 
+/* ---- video object detection evaluation (csrc/evalobj/tspn_eval_objects.hip) -------------------------------------
+ * The O(|pred| x |gt| x frames) core of the reference's trajectory mAP (lib/evaluation/video_object_detection.py:12-106,
+ * common.py:40-62; DESIGN.md 2 "object detection evaluation"), float64, every result bit-equal to the reference's.
+ * Operands (packed by evaluation_detection.py):
+ *   boxes [F,4] float64 (32-byte aligned), one row per (trajectory, frame); frames [F] int32 = the frame id of each
+ *   row, ascending inside a trajectory (frame sets may have gaps; two trajectories share a frame when the ids are
+ *   equal); traj [T,2] int64 = (first row, number of rows); predictions are trajectories 0..P-1, in score order inside
+ *   their group, ground truths follow; groups [G,5] int64 = (first prediction, #predictions, first ground-truth
+ *   trajectory, #ground truths, offset of the group's row-major #pred x #gt block in tiou) per (video, class);
+ *   pred_group [P] int32.
+ * tspn_evalobj_tiou_f64: per (prediction, group ground truth) pair, total = |frames of either|, and over the common
+ *   frames sIoU = ov_w * ov_h * 1.0 / (area_g + area_p - ov) with the + 1 widths, max(0, .) on the overlap sides and
+ *   Python's max / min; tIoU = (#(sIoU >= 0.5) + #(sIoU >= 0.7) + #(sIoU >= 0.9)) * 1.0 / (3 * total).  tiou [C]
+ *   float64 receives every pair's value (NULL: not stored).  best [P] float64 / best_index [P] int32 = the running
+ *   maximum over the group's ground truths in index order, from (0, 0) with a strict `>`: a tie keeps the lower index,
+ *   an all-zero row or a group without ground truths gives (0.0, 0).  flags [P] int32: bit 0 = a common frame with a
+ *   zero sIoU denominator, bit 1 = a pair with total == 0 (its tIoU is stored as 0); the reference raises
+ *   ZeroDivisionError at both.  Every element of best, best_index, flags (and tiou) is written.
+ * tspn_evalobj_claim: a prediction qualifies when best >= thresh_t and its group has a ground truth; claim [n_gt]
+ *   int32 (ground truth k of the chunk = trajectory n_pred + k) = the smallest position inside its group of a
+ *   qualifying prediction that names this ground truth, INT32_MAX for none; hit [P] int8 = 1 for a qualifying
+ *   prediction whose position is its ground truth's claim, else 0 (the reference's det[] flags: a prediction whose
+ *   best ground truth is taken is a false positive, it does not fall back to its second best).  claim is an output:
+ *   the entry fills it (a kernel on `stream`) before the integer atomicMin pass, so the result is deterministic and
+ *   does not depend on what claim held.  The contents of traj / groups / pred_group are trusted; a best_index outside
+ *   its group never qualifies.  n_pred == 0 still fills claim. */
+int tspn_evalobj_tiou_f64(const double* boxes, const int32_t* frames, const int64_t* traj, const int64_t* groups,
+                          const int32_t* pred_group, int64_t n_pred, double* tiou, double* best, int32_t* best_index,
+                          int32_t* flags, void* stream);
+int tspn_evalobj_claim(const double* best, const int32_t* best_index, const int64_t* groups, const int32_t* pred_group,
+                       int64_t n_pred, int64_t n_gt, double thresh_t, int32_t* claim, int8_t* hit, void* stream);
+
 /* ---- training the span heads: anchor targets and losses (csrc/spanloss/tspn_span_loss.hip) ----------------------
  * Build-defined (the reference's make_dpn_loss_evaluator, relpn/dpn_anchor.py:50-70, does not exist): the
  * RPN scheme in one dimension, on the parametrisation tspn_decode_spans_f32 decodes.  One call serves one segment of P

@@ -200,6 +200,8 @@ PROTOTYPES = {
     "tspn_eval_traj_volume_f64": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "tspn_eval_viou_f64": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "tspn_eval_greedy_match_f64": (_int, [_vp, _vp, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _vp]),
+    "tspn_evalobj_tiou_f64": (_int, [_vp] * 5 + [_i64] + [_vp] * 5),
+    "tspn_evalobj_claim": (_int, [_vp] * 4 + [_i64, _i64, ctypes.c_double, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -21,6 +21,9 @@ Deliberate additions to the reference's behaviour:
     reference raises it only for the pairs its loop reaches).
 Where the reference raises, the same exception type is raised: a ground-truth video missing from the predictions
 raises KeyError, and no prediction in any video with ground truth raises IndexError (the reference's `rec[-1]`).
+
+The reference's two other evaluators, video object detection and action detection, live in evaluation_detection.py and
+are re-exported here (`evaluate_objects`, `evaluate_actions`, `object_instances`, `action_instances`).
 """
 import itertools
 import json
@@ -85,9 +88,17 @@ def load_prediction(path):
 
 
 # ---------------------------------------------------------------------------------------------------- host metrics
-def voc_ap(rec, prec):
-    """Non-07 VOC AP of the reference (lib/evaluation/common.py:4-37).  The precision envelope is a reversed running
-    maximum, which np.maximum.accumulate computes exactly."""
+def voc_ap(rec, prec, use_07_metric=False):
+    """VOC AP of the reference (lib/evaluation/common.py:4-37).  Non-07 (the default): the precision envelope is a
+    reversed running maximum, which np.maximum.accumulate computes exactly.  `use_07_metric`: the 11-point form, the
+    largest precision at a recall >= t (0 where there is none) over np.arange(0., 1.1, 0.1), each divided by 11. and added
+    in that order to a Python 0. (so a curve that never reaches recall 0 gives a Python float, any other an np.float64)."""
+    if use_07_metric:
+        ap = 0.
+        for t in np.arange(0., 1.1, 0.1):
+            reached = rec >= t
+            ap = ap + (np.max(prec[reached]) if np.sum(reached) != 0 else 0) / 11.
+        return ap
     mrec = np.concatenate(([0.], rec, [1.]))
     mpre = np.concatenate(([0.], prec, [0.]))
     mpre = np.maximum.accumulate(mpre[::-1])[::-1]
@@ -424,3 +435,9 @@ def evaluate_zeroshot(groundtruth, prediction, train_triplets, old=False, **kwar
             gt[vid] = zs
             pred[vid] = prediction[vid] if old else [r for r in prediction[vid] if tuple(r["triplet"]) in zeroshot]
     return evaluate(gt, pred, **kwargs)
+
+
+# object and action detection (evaluation_detection.py builds on the helpers above, hence the late import)
+from .evaluation_detection import action_instances, evaluate_actions, evaluate_objects, object_instances  # noqa: E402
+
+__all__ += ["evaluate_objects", "evaluate_actions", "object_instances", "action_instances"]

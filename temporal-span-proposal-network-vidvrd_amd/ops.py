@@ -26,7 +26,7 @@ __all__ = [
     "proposal_pair_filter", "gather_rows", "wino63_set_piece_form", "wino63_f16x3_set_tail_split", "conv3_spot_check",
     "wino63_f16x3_set_input_form", "wino63_f16x3_input_form", "wino63_f16x3_input",
     "pack_conv2d", "pack_conv2d_frag", "conv2d_nhwc", "roi_align_nhwc", "pack_conv2d_frag_bf16", "conv2d_nhwc_bf16", "max_pool_nhwc", "pack_conv2d_frag_cin4", "conv2d_nhwc_cin4", "max_pool_nhwc_bf16", "pack_stem_bf16", "stem_conv_bf16", "stem_pool_bf16", "bottleneck_tail_bf16",
-    "eval_traj_volume", "eval_viou", "eval_greedy_match",
+    "eval_traj_volume", "eval_viou", "eval_greedy_match", "evalobj_tiou", "evalobj_claim",
     "status_words", "status_fault", "status_clear", "status_selftest",
 ]
 
@@ -1953,6 +1953,71 @@ def eval_greedy_match(ov, groups, n_pred, viou_threshold, max_group_gt, det_ws=N
     _abi.check(_abi.lib().tspn_eval_greedy_match_f64(_p(ov), _p(groups), groups.shape[0], int(max_group_gt),
                                                      float(viou_threshold), _p(det_ws), _p(hit), _p(match), _stream()))
     return hit, match
+
+
+# ---- video object detection evaluation (csrc/evalobj/tspn_eval_objects.hip; packed by evaluation_detection.py)
+def _evalobj_groups(who, groups, pred_group):
+    _dev(groups, "groups", torch.int64), _dev(pred_group, "pred_group", torch.int32)
+    if groups.dim() != 2 or groups.shape[1] != 5 or pred_group.dim() != 1:
+        raise ValueError(f"{who}: groups [G,5] and pred_group [P] expected, got {tuple(groups.shape)} and "
+                         f"{tuple(pred_group.shape)}")
+    if pred_group.shape[0] and not groups.shape[0]:
+        raise ValueError(f"{who}: {pred_group.shape[0]} predictions and no group")
+    return pred_group.shape[0]
+
+
+def _evalobj_out(who, t, name, n, dtype, dev):
+    if t is None:
+        return torch.empty(int(n), dtype=dtype, device=dev)
+    if _dev(t, name, dtype).shape != (int(n),):
+        raise ValueError(f"{who}: {name} must be [{int(n)}]")
+    return t
+
+
+def evalobj_tiou(boxes, frames, traj, groups, pred_group, n_cand=None, tiou=None, best=None, best_index=None, flags=None):
+    """The reference's trajectory overlap (video_object_detection.py:12-43) of every prediction of a packed chunk against
+    the ground truths of its (video, class) group: boxes [F,4] float64, frames [F] int32 (ascending inside a trajectory),
+    traj [T,2] int64 (first row, rows), groups [G,5] int64, pred_group [P] int32 (include/tspn_mi355x.h).  Returns
+    (tiou, best, best_index, flags): tiou [n_cand] float64, every pair's tIoU in row-major group blocks (None unless
+    `n_cand` or `tiou` is given), best [P] float64 and best_index [P] int32 (max_overlap, max_index), flags [P] int32
+    (bit 0: a zero sIoU denominator, bit 1: a pair of two empty trajectories)."""
+    who = "evalobj_tiou"
+    _dev(boxes, "boxes", torch.float64), _dev(frames, "frames", torch.int32), _dev(traj, "traj", torch.int64)
+    if boxes.dim() != 2 or boxes.shape[1] != 4 or frames.shape != (boxes.shape[0],) or traj.dim() != 2 or traj.shape[1] != 2:
+        raise ValueError(f"{who}: boxes [F,4], frames [F] and traj [T,2] expected, got {tuple(boxes.shape)}, "
+                         f"{tuple(frames.shape)} and {tuple(traj.shape)}")
+    if boxes.data_ptr() % 32:
+        raise ValueError(f"{who}: boxes must be 32-byte aligned")
+    P = _evalobj_groups(who, groups, pred_group)
+    if P > traj.shape[0]:
+        raise ValueError(f"{who}: {P} predictions need {P} trajectories, traj has {traj.shape[0]}")
+    dev = boxes.device
+    if tiou is not None or n_cand is not None:
+        tiou = _evalobj_out(who, tiou, "tiou", tiou.shape[0] if n_cand is None else n_cand, torch.float64, dev)
+    best = _evalobj_out(who, best, "best", P, torch.float64, dev)
+    best_index = _evalobj_out(who, best_index, "best_index", P, torch.int32, dev)
+    flags = _evalobj_out(who, flags, "flags", P, torch.int32, dev)
+    _abi.check(_abi.lib().tspn_evalobj_tiou_f64(_p(boxes), _p(frames), _p(traj), _p(groups), _p(pred_group), P, _p(tiou),
+                                                _p(best), _p(best_index), _p(flags), _stream()))
+    return tiou, best, best_index, flags
+
+
+def evalobj_claim(best, best_index, groups, pred_group, n_gt, thresh_t, claim=None, hit=None):
+    """The reference's true-positive rule (video_object_detection.py:93-106) from `evalobj_tiou`'s best / best_index: a
+    prediction with best >= thresh_t claims its ground truth with its position inside its group, the smallest position
+    wins.  Returns (claim, hit): claim [n_gt] int32 (INT32_MAX: unclaimed; written in full by the call), hit [P] int8."""
+    who = "evalobj_claim"
+    _dev(best, "best", torch.float64), _dev(best_index, "best_index", torch.int32)
+    P = _evalobj_groups(who, groups, pred_group)
+    if best.shape != (P,) or best_index.shape != (P,):
+        raise ValueError(f"{who}: best and best_index must be [{P}]")
+    if int(n_gt) < 0 or not float(thresh_t) == float(thresh_t):
+        raise ValueError(f"{who}: n_gt must be >= 0 and thresh_t a number")
+    claim = _evalobj_out(who, claim, "claim", n_gt, torch.int32, best.device)
+    hit = _evalobj_out(who, hit, "hit", P, torch.int8, best.device)
+    _abi.check(_abi.lib().tspn_evalobj_claim(_p(best), _p(best_index), _p(groups), _p(pred_group), P, int(n_gt),
+                                             float(thresh_t), _p(claim), _p(hit), _stream()))
+    return claim, hit
 
 # every public operator runs with the device of its operands made current (see _on_tensor_device)
 for _name in __all__:
