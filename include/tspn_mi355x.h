@@ -1071,6 +1071,58 @@ int tspn_span_match_f64(const double* rel_boxes, const int32_t* rel_range, const
                         const int32_t* pred_pair, const int32_t* pred_span, int64_t U, int64_t P, int64_t N, int64_t L,
                         double iou_thr, float* iou, int32_t* match, void* stream);
 
+/* ---- training the predicate head on ground-truth-span-pooled features (csrc/spancls/tspn_span_cls.hip) ------------
+ * Build-defined (DESIGN.md 2 "span-pooled predicate training"; the reference's RelOIPool, lib/modeling/model.py:68-73,
+ * is a stub).  Row r = p G + g of pair p and span row g; with c = span_count[p] of tspn_pair_labels_f32:
+ *   c >= 1 and g < min(c, G): a row over the frames spans[p, g];  c == 0 and g == 0: a negative pair, a row over [0, T)
+ *   with a zero label;  anything else is no row (c < 0, g past the count, the rows dropped by a saturated count).
+ *
+ * tspn_span_labels_f32: every operand of tspn_pair_labels_f32 in its order, then that entry's outputs spans int64
+ *   [P, G, 2], span_count int32 [P], inst_cols int32 [R, 2] as inputs -> span_labels fp32 [P, G, K].  For
+ *   g < min(span_count[p], G), row (p, g) collects the live instances that cover pair p (the test of the pair labels: the
+ *   fp32 threshold compare, NaN never covers, columns from inst_cols) and whose clipped span
+ *   [max(begin, fstart) - fstart, min(end, fend) - fstart) equals spans[p, g]: merge 1 ("or") sets the pred of each,
+ *   merge 0 ("last") the one-hot of the one with the largest r.  Every other row is zero.  One launch; every element
+ *   written exactly once; no host synchronisation, atomic, memset or scratch.  Limits: 1 <= K <= 512, 1 <= G <= 16, S, P,
+ *   M, R < 2^31, iou_thres finite.  P == 0 launches nothing.
+ *
+ * tspn_span_predicate_loss_f32 + tspn_span_predicate_loss_finish: feats fp32 [NT, T, D], pairs int64 [P, 2] (global
+ *   tracklet ids, as tspn_span_predicate_f32 takes them), pair_off int64 [S + 1] on the device (NULL: one segment),
+ *   cls_w fp32 [K, 2D], cls_b fp32 [K] or NULL.  For a row, v[r, k] = the float64 value tspn_span_predicate_f32 passes
+ *   through its sigmoid for (pairs[p], spans[p, g]) ([0, T) for a negative pair), y = span_labels[r, k] (0 for a negative
+ *   pair), l = max(v, 0) - v y + log1p(exp(-|v|)) in float64.  Outputs: q fp32 [P G, K] = (float)sigmoid(v), dv fp32
+ *   [P G, K] = (sigmoid(v) - y) / (K rows_s) with rows_s the rows of the pair's segment, both 0 where there is no row;
+ *   partials double [P G] = the row sums of l; seg_rows double [S] = rows_s.  A pair naming a tracklet outside [0, NT)
+ *   has no rows.  Rows are selected, not masked: nothing is read through a row that is none.
+ *   tspn_span_predicate_loss_finish: out double [1 + S]: out[1 + s] = sum of segment s's partials / (K rows_s), 0 for a
+ *   segment without rows; out[0] = their sum in segment order (loss_rel).  Fixed summation orders: bit-reproducible.
+ *   prefix_scratch: at least tspn_span_predicate_workspace_bytes(NT, T, D, K) bytes (TSPN_EWORKSPACE otherwise), 8-byte
+ *   aligned; it holds the projections and their prefix sums until the loss kernel has run.
+ *
+ * tspn_span_predicate_grad_f32: db fp32 [K] = sum over r of dv[r, k] (float64, rows in ascending order); dG fp32
+ *   [NT, T, 2K], the gradient with respect to the per-frame projections G[n, t, 2k + h] = feats[n, t, :] .
+ *   cls_w[k, hD:(h+1)D]: dG[n, t, 2k + h] = sum of dv[r, k] / (e_r - a_r) over the rows r with pairs[p_r][h] == n and
+ *   a_r <= t < e_r, accumulated per column in float64 through a difference array in ascending row order and a running
+ *   sum over t (a non-finite dv therefore reaches the later frames of its columns too).  No atomics; every element of
+ *   dG is written.  prefix_scratch: at least NT (T + 1) 2K doubles (the loss entries' scratch is large enough and free
+ *   again).  The classifier gradient is dW[k, hD + c] = sum over (n, t) of dG[n, t, 2k + h] feats[n, t, c], a GEMM.
+ * Limits of the three: T < 2^30, K < 2^20, 1 <= G <= 16, P G < 2^31.  No host synchronisation and no memset. */
+int tspn_span_labels_f32(const int64_t* pairs, const int64_t* pair_off, const int64_t* trackid,
+                         const int64_t* track_off, const float* iou, const int64_t* iou_off, const int64_t* insts,
+                         const int64_t* inst_off, const int64_t* seg_frames, int64_t S, int64_t P, int64_t M, int64_t R,
+                         int64_t K, int64_t G, double iou_thres, int merge, const int64_t* spans,
+                         const int32_t* span_count, const int32_t* inst_cols, float* span_labels, void* stream);
+int tspn_span_predicate_loss_f32(const float* feats, int64_t NT, int64_t T, int64_t D, const int64_t* pairs,
+                                 const int64_t* pair_off, int64_t S, int64_t P, const int64_t* spans,
+                                 const int32_t* span_count, const float* span_labels, int64_t G, const float* cls_w,
+                                 const float* cls_b, int64_t K, float* q, float* dv, double* partials, double* seg_rows,
+                                 void* prefix_scratch, size_t prefix_scratch_bytes, void* stream);
+int tspn_span_predicate_loss_finish(const double* partials, const double* seg_rows, const int64_t* pair_off, int64_t S,
+                                    int64_t P, int64_t G, int64_t K, double* out, void* stream);
+int tspn_span_predicate_grad_f32(const float* dv, const int64_t* pairs, const int64_t* spans, const int32_t* span_count,
+                                 int64_t NT, int64_t T, int64_t P, int64_t G, int64_t K, float* db, float* dG,
+                                 void* prefix_scratch, size_t prefix_scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -197,6 +197,11 @@ PROTOTYPES = {
     "tspn_span_anchor_sample": (_int, [_vp, _i64, ctypes.c_uint64, _int, _i64, _i64, _vp, _vp, _vp, _vp]),
     "tspn_pair_labels_f32": (_int, [_vp] * 9 + [_i64] * 6 + [ctypes.c_double, _int, _vp, _vp, _vp, _vp, _vp]),
     "tspn_span_match_f64": (_int, [_vp] * 8 + [_i64] * 4 + [ctypes.c_double, _vp, _vp, _vp]),
+    "tspn_span_labels_f32": (_int, [_vp] * 9 + [_i64] * 6 + [ctypes.c_double, _int, _vp, _vp, _vp, _vp, _vp]),
+    "tspn_span_predicate_loss_f32": (_int, [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i64,
+                                           _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "tspn_span_predicate_loss_finish": (_int, [_vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp]),
+    "tspn_span_predicate_grad_f32": (_int, [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
     "tspn_eval_traj_volume_f64": (_int, [_vp, _vp, _i64, _vp, _vp]),
     "tspn_eval_viou_f64": (_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "tspn_eval_greedy_match_f64": (_int, [_vp, _vp, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _vp]),

@@ -60,6 +60,9 @@ _DEFAULTS = {
                 # build extension (not in the reference's defaults.py): RelOIPool restricted to each
                 # pair's top temporal span instead of the whole segment (model.py:68-73 is a stub)
                 "POOL_TOP_SPAN": False,
+                # build extension: in training, loss_rel of tracklet samples comes from the predicate head pooled over
+                # each pair's ground-truth spans (target fields 'spans', 'span_count', 'span_labels')
+                "POOL_GT_SPAN": False,
                 # build extension: forward also returns the relative box geometry [P,8,T] of every pair
                 # (TemporalProposals.geom, the bbox half of the pair builder); nothing downstream reads it
                 "PAIR_GEOMETRY": False,

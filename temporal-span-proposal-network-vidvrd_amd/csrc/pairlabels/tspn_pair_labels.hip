@@ -32,6 +32,7 @@
 #include <cmath>
 
 #include "tspn_common.h"
+#include "tspn_pair_tables.h"
 
 namespace {
 
@@ -41,32 +42,8 @@ constexpr int MAX_WORDS = MAX_K / 64;              // 64-bit mask words per pair
 constexpr int MAX_G = 16;
 constexpr int MERGE_LAST = 0, MERGE_OR = 1;
 
-struct Tables {
-  const int64_t* pairs;        // [P, 2]
-  const int64_t* pair_off;     // [S + 1] or null (S == 1)
-  const int64_t* trackid;      // [M]
-  const int64_t* track_off;
-  const float* iou;            // segment s: [M_s, M_s] from iou_off[s] on
-  const int64_t* iou_off;
-  const int64_t* insts;        // [R, 5]
-  const int64_t* inst_off;
-  const int64_t* seg_frames;   // [S, 2] or null (G == 0)
-  int64_t S, P, M, R;
-};
-
-// the largest s in [0, S) with off[s] <= i, for off[0] <= i < off[S]: the segment that holds element i (empty segments
-// in front of it share its offset and lose)
-__device__ __forceinline__ int64_t segment_of(const int64_t* __restrict__ off, int64_t S, int64_t i) {
-  int64_t lo = 0, hi = S;
-  while (hi - lo > 1) {
-    const int64_t mid = lo + (hi - lo) / 2;
-    if (off[mid] <= i)
-      lo = mid;
-    else
-      hi = mid;
-  }
-  return lo;
-}
+using Tables = tspn::PairTables;
+using tspn::segment_of;
 
 __global__ __launch_bounds__(TILE) void pair_labels_resolve_kernel(Tables t, int64_t K, int32_t* __restrict__ inst_cols) {
   const int64_t r = (int64_t)blockIdx.x * TILE + threadIdx.x;
@@ -101,32 +78,15 @@ __global__ __launch_bounds__(TILE) void pair_labels_kernel(Tables t, int K, int 
   const int64_t p0 = (int64_t)blockIdx.x * TILE, p = p0 + threadIdx.x;
   for (int w = 0; w < words; ++w) lds_mask[w * TILE + threadIdx.x] = 0;
   if (p < t.P) {
-    int64_t s = 0, m0 = 0, M = t.M, i0 = 0, r0 = 0, r1 = t.R;
-    if (t.pair_off) {
-      s = segment_of(t.pair_off, t.S, p);
-      m0 = t.track_off[s];
-      M = t.track_off[s + 1] - m0;
-      i0 = t.iou_off[s];
-      r0 = t.inst_off[s];
-      r1 = t.inst_off[s + 1];
-    }
-    const int64_t a = t.pairs[2 * p], b = t.pairs[2 * p + 1];
-    const bool inside = a >= 0 && a < M && b >= 0 && b < M;
-    const bool open = inside && a != b && t.trackid[m0 + a] < 0 && t.trackid[m0 + b] < 0;
-    int64_t fstart = 0, fend = 0;
-    if (G > 0) {
-      fstart = t.seg_frames[2 * s];
-      fend = t.seg_frames[2 * s + 1];
-    }
-    const float* row_a = t.iou + i0 + a * M;
-    const float* row_b = t.iou + i0 + b * M;
+    const tspn::PairScope v = tspn::pair_scope(t, p, G > 0);
+    const bool inside = v.inside, open = v.open;
+    const int64_t fstart = v.fstart, fend = v.fend, r0 = v.r0, r1 = v.r1;
     int64_t* my_spans = spans + p * (int64_t)G * 2;       // formed, not read, when G == 0
     int last = -1, count = 0;
     if (open) {
       for (int64_t r = r0; r < r1; ++r) {
         const int cs = inst_cols[2 * r], co = inst_cols[2 * r + 1];
-        if (cs < 0 || co < 0) continue;
-        if (!(row_a[cs] >= thr && row_b[co] >= thr)) continue;
+        if (!tspn::covers(v, cs, co, thr)) continue;
         const int pred = (int)t.insts[5 * r + 2];          // in [0, K): the instance is live
         last = pred;
         if (merge == MERGE_OR) lds_mask[(pred >> 6) * TILE + threadIdx.x] |= 1ull << (pred & 63);
@@ -159,26 +119,8 @@ __global__ __launch_bounds__(TILE) void pair_labels_kernel(Tables t, int K, int 
   // the tile's label elements, flat: element e = row * K + k of the rows p0 .. p0 + rows - 1
   const int64_t left = t.P - p0;
   const int rows = left < TILE ? (int)left : TILE;
-  const int n = rows * K;                                    // <= 256 * 512
-  float* out = labels + p0 * K;                              // p0 * K * 4 bytes: a multiple of 1024
-  const int n4 = aligned ? n >> 2 : 0;
-  for (int i = threadIdx.x; i < n4; i += TILE) {
-    int row = (4 * i) / K, k = 4 * i - row * K;
-    float v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      v[j] = (float)((lds_mask[(k >> 6) * TILE + row] >> (k & 63)) & 1ull);
-      if (++k == K) {
-        k = 0;
-        ++row;
-      }
-    }
-    reinterpret_cast<float4*>(out)[i] = make_float4(v[0], v[1], v[2], v[3]);
-  }
-  for (int e = 4 * n4 + threadIdx.x; e < n; e += TILE) {
-    const int row = e / K, k = e - row * K;
-    out[e] = (float)((lds_mask[(k >> 6) * TILE + row] >> (k & 63)) & 1ull);
-  }
+  // p0 * K * 4 bytes is a multiple of 1024: the tile starts 16-byte aligned where labels does
+  tspn::store_mask_rows<TILE>(lds_mask, labels + p0 * K, rows, K, aligned);
 }
 
 }  // namespace

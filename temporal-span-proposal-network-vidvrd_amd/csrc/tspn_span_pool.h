@@ -25,11 +25,12 @@ __device__ inline double span_sum_frames(const float* __restrict__ g, int64_t K2
   return acc;
 }
 
-// sigmoid(mean over the frames of span (a0, e0) of G[s, :, 2k] + G[o, :, 2k+1], + b[k]) of global tracklets (s, o):
-// PS [NT, T+1, 2K] float64 prefix sums of G [NT, T, 2K] over time.
-__device__ inline float span_logit(const double* __restrict__ PS, const float* __restrict__ G, int64_t s, int64_t o,
-                                   int64_t a0, int64_t e0, int T, int64_t K2, int64_t k,
-                                   const float* __restrict__ b) {
+// The float64 value span_logit passes through the sigmoid: the mean over the frames of span (a0, e0) of
+// G[s, :, 2k] + G[o, :, 2k+1], + b[k], of global tracklets (s, o); PS [NT, T+1, 2K] float64 prefix sums of G [NT, T, 2K]
+// over time.  The span-pooled training loss (spancls/tspn_span_cls.hip) takes its loss and gradient from this value.
+__device__ inline double span_value(const double* __restrict__ PS, const float* __restrict__ G, int64_t s, int64_t o,
+                                    int64_t a0, int64_t e0, int T, int64_t K2, int64_t k,
+                                    const float* __restrict__ b) {
   int64_t a, e;
   span_frames(a0, e0, T, a, e);
   const double* ps = PS + (s * (T + 1)) * K2 + 2 * k;
@@ -42,6 +43,14 @@ __device__ inline float span_logit(const double* __restrict__ PS, const float* _
   if (!isfinite(po[e * K2])) dob = span_sum_frames(G + (o * T) * K2 + 2 * k + 1, K2, a, e);
   double v = (ds + dob) / (double)(e - a);
   if (b != nullptr) v += (double)b[k];
+  return v;
+}
+
+// sigmoid of span_value, rounded to fp32: what span pooling returns per (row, predicate)
+__device__ inline float span_logit(const double* __restrict__ PS, const float* __restrict__ G, int64_t s, int64_t o,
+                                   int64_t a0, int64_t e0, int T, int64_t K2, int64_t k,
+                                   const float* __restrict__ b) {
+  const double v = span_value(PS, G, s, o, a0, e0, T, K2, k, b);
   return (float)(1.0 / (1.0 + exp(-v)));
 }
 

@@ -61,7 +61,7 @@ def select_proposal_pairs(pairs, trackid, device=None):
 
 def proposal_pair_list(pairs, feats, iou, trackid, cls_logits, pred_labels=None, preprocess=True,
                        device=None, gt_rel_insts=None, segment=None, max_spans=0, iou_thres=0.5, merge="last",
-                       num_predicates=132):
+                       num_predicates=132, span_labels=False):
     """One segment's (PairList, TargetList | None) as `VRDataset.__getitem__` builds them
     (vrdataset.py:64-83), resident on the HIP device.
 
@@ -72,8 +72,10 @@ def proposal_pair_list(pairs, feats, iou, trackid, cls_logits, pred_labels=None,
     int64 [R,3] = (sub_tid, obj_tid, pred), labelled on the device (`ops.pair_labels` on the kept pair table, `iou_thres`,
     `merge`, K = `num_predicates`; DESIGN.md §2 "pair labels").  [R,5] = (.., begin, end) with `segment=(fstart, fend)` and
     `max_spans=G` also gives the TargetList the fields 'spans' int64 [P',G,2] (the target of the span heads) and
-    'span_count' int32 [P']."""
+    'span_count' int32 [P']; `span_labels=True` adds 'span_labels' fp32 [P',G,K], a label row per (pair, ground-truth
+    span) (`ops.span_labels`; DESIGN.md §2 "span-pooled predicate training")."""
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    _span_labels_wanted(span_labels, max_spans, gt_rel_insts is not None)
     p_all = _to_dev(pairs, device, torch.int64).reshape(-1, 2)
     f_all = _to_dev(feats, device, torch.float32)
     if f_all.dim() != 2 or f_all.shape[0] != p_all.shape[0]:
@@ -85,11 +87,18 @@ def proposal_pair_list(pairs, feats, iou, trackid, cls_logits, pred_labels=None,
     plist, tlist = _assemble(p_all, f_all, idx, num_tracks, iou, trackid, cls_logits, pred_labels, preprocess, device)
     if insts is not None:
         iou_dev = _to_dev(iou, device, torch.float32)
-        out = ops.pair_labels(plist.get_field("tracklet_pairs"), tid, iou_dev, torch.from_numpy(insts).to(device),
-                              num_predicates, iou_thres, merge, max_spans,
-                              torch.from_numpy(frames).to(device) if max_spans else None)
-        tlist = _label_targets(out[0], out[1], out[2])
+        insts_dev, frames_dev = torch.from_numpy(insts).to(device), torch.from_numpy(frames).to(device) if max_spans else None
+        out = ops.pair_labels(plist.get_field("tracklet_pairs"), tid, iou_dev, insts_dev, num_predicates, iou_thres, merge,
+                              max_spans, frames_dev)
+        rows = ops.span_labels(plist.get_field("tracklet_pairs"), tid, iou_dev, insts_dev, num_predicates, out[1], out[2],
+                               out[3], frames_dev, iou_thres, merge) if span_labels else None
+        tlist = _label_targets(out[0], out[1], out[2], rows)
     return plist, tlist
+
+
+def _span_labels_wanted(span_labels, max_spans, has_insts):
+    if span_labels and not (max_spans and has_insts):
+        raise ValueError("span_labels=True needs gt_rel_insts [R,5], segment=(fstart, fend) and max_spans > 0")
 
 
 def _relation_instances(gt_rel_insts, segment, max_spans, pred_labels):
@@ -112,11 +121,13 @@ def _relation_instances(gt_rel_insts, segment, max_spans, pred_labels):
     return np.ascontiguousarray(a), frames
 
 
-def _label_targets(labels, spans, span_count):
+def _label_targets(labels, spans, span_count, span_labels=None):
     tlist = TargetList(labels)
     if spans is not None:
         tlist.add_field("spans", spans)
         tlist.add_field("span_count", span_count)
+    if span_labels is not None:
+        tlist.add_field("span_labels", span_labels)
     return tlist
 
 
@@ -147,16 +158,18 @@ def _assemble(p_all, f_all, idx, num_tracks, iou, trackid, cls_logits, pred_labe
 
 
 def proposal_pair_lists(segments, preprocess=True, device=None, max_spans=0, iou_thres=0.5, merge="last",
-                        num_predicates=132):
+                        num_predicates=132, span_labels=False):
     """A batch of segments at once: `segments` = sequence of dicts with the keys of `proposal_pair_list`
     (pairs, feats, iou, trackid, cls_logits[, pred_labels | gt_rel_insts[, segment]]).  The pair filter of ALL segments is
     ONE launch (`pair_off` / `track_off` form of tspn_proposal_pair_filter_i64) and the loader pays ONE host sync per
     batch (the kept-row counts) instead of several per segment.  The segments with a "gt_rel_insts" key are labelled by
     ONE `ops.pair_labels` call over their kept pair tables, after that sync (`max_spans`, `iou_thres`, `merge`,
-    `num_predicates` as in `proposal_pair_list`).  Returns [(PairList, TargetList | None)]."""
+    `num_predicates` as in `proposal_pair_list`), and `span_labels=True` adds ONE `ops.span_labels` call over the same
+    tables (the target field 'span_labels').  Returns [(PairList, TargetList | None)]."""
     device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
     if not len(segments):
         return []
+    _span_labels_wanted(span_labels, max_spans, any(s.get("gt_rel_insts") is not None for s in segments))
     p_all = [_to_dev(s["pairs"], device, torch.int64).reshape(-1, 2) for s in segments]
     f_all = [_to_dev(s["feats"], device, torch.float32) for s in segments]
     tids = [_to_dev(s["trackid"], device, torch.int64).reshape(-1) for s in segments]
@@ -188,15 +201,19 @@ def proposal_pair_lists(segments, preprocess=True, device=None, max_spans=0, iou
         for k, v in zip(ks, ious):
             if v.numel() != tids[k].shape[0] ** 2:
                 raise ValueError(f"proposal_pair_lists: segment {k}: iou must be [M,M] with M = {tids[k].shape[0]}")
-        labels, spans, span_count, _ = ops.pair_labels(
-            torch.cat([out[k][0].get_field("tracklet_pairs") for k in ks]), torch.cat([tids[k] for k in ks]), torch.cat(ious),
-            torch.from_numpy(np.concatenate([insts[k][0] for k in ks])).to(device), num_predicates, iou_thres, merge,
-            max_spans, torch.from_numpy(np.concatenate([insts[k][1] for k in ks])).to(device) if max_spans else None,
-            offs[0], offs[1], offs[2], offs[3])
+        kept, tid_cat, iou_cat = torch.cat([out[k][0].get_field("tracklet_pairs") for k in ks]), torch.cat([tids[k] for k in ks]), \
+            torch.cat(ious)
+        insts_dev = torch.from_numpy(np.concatenate([insts[k][0] for k in ks])).to(device)
+        frames_dev = torch.from_numpy(np.concatenate([insts[k][1] for k in ks])).to(device) if max_spans else None
+        labels, spans, span_count, inst_cols = ops.pair_labels(kept, tid_cat, iou_cat, insts_dev, num_predicates, iou_thres,
+                                                               merge, max_spans, frames_dev, offs[0], offs[1], offs[2], offs[3])
+        rows = ops.span_labels(kept, tid_cat, iou_cat, insts_dev, num_predicates, spans, span_count, inst_cols, frames_dev,
+                               iou_thres, merge, offs[0], offs[1], offs[2], offs[3]) if span_labels else None
         for j, k in enumerate(ks):
             lo, hi = int(sizes[:j, 0].sum()), int(sizes[:j + 1, 0].sum())
             out[k] = (out[k][0], _label_targets(labels[lo:hi], spans[lo:hi] if max_spans else None,
-                                                span_count[lo:hi] if max_spans else None))
+                                                span_count[lo:hi] if max_spans else None,
+                                                rows[lo:hi] if span_labels else None))
     return out
 
 

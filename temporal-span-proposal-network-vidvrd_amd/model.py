@@ -362,8 +362,10 @@ class _TemporalHeadsTrackletFn(torch.autograd.Function):
             act = torch.relu(u[s] + v[o])
             dz, dhw = _heads_backward(head_w, gb, act)
             d_head_w += dhw
-            du.index_add_(0, s, dz)
-            dv.index_add_(0, o, dz)
+            # accumulate=True takes torch's sort-based scatter: rows of one tracklet are added in a fixed order, so the
+            # gradients of a step are the same bits in every run (index_add_ adds them with atomics, in any order)
+            du.index_put_((s,), dz, accumulate=True)
+            dv.index_put_((o,), dz, accumulate=True)
         x_cf = feats.transpose(1, 2)
         d_conv_w = torch.cat([_conv3_weight_grad(x_cf, du), _conv3_weight_grad(x_cf, dv)], dim=1)
         return None, None, d_conv_w, du.sum((0, 2)), d_head_w, g.sum((0, 2))
@@ -393,6 +395,39 @@ class _SpanLossFn(torch.autograd.Function):
         a = ctx.num_anchors
         scale = torch.cat([g_rel.reshape(1).expand(a), g_reg.reshape(1).expand(2 * a)]).to(dheads.dtype)
         return dheads * scale.view(1, 3 * a, 1), None, None, None, None, None, None
+
+
+def _span_cls_weight_grad(dG, feats):
+    """dW [K,2D] of the span-pooled predicate head from dG [NT,T,2K] (ops.span_predicate_grad) and feats [NT,T,D]:
+    dW[k, h D + c] = sum over (n, t) of dG[n, t, 2k + h] feats[n, t, c], one product dG^T [2K, NT T] . feats^T [D, NT T]^T on
+    the library's HIP GEMM; row 2k + h of the product is half h of row k of dW."""
+    nt, t, k2 = dG.shape
+    d = feats.shape[2]
+    return _nt(_tr(dG.reshape(nt * t, k2)), _tr(feats.reshape(nt * t, d))).reshape(k2 // 2, 2 * d)
+
+
+class _SpanPredicateLossFn(torch.autograd.Function):
+    """loss_rel of one shape group of tracklet segments from the predicate head pooled over each pair's ground-truth spans
+    (DESIGN.md §2 "span-pooled predicate training"): feats [NT,T,D] (the group's tracklets back to back), pairs [P,2]
+    global ids, the target fields spans [P,G,2] / span_count [P] / span_labels [P,G,K], pair_off [S+1] or None.  The
+    forward holds d loss / d v of every row (ops.span_predicate_loss); the backward turns it into the gradients of the
+    classifier (ops.span_predicate_grad and one GEMM).  The features get no gradient, as with the segment-pooled rows."""
+
+    @staticmethod
+    def forward(ctx, feats, pairs, spans, span_count, span_labels, w, b, pair_off):
+        out, _, dv, _, scratch = ops.span_predicate_loss(feats, pairs, spans, span_count, span_labels, w, b,
+                                                         pair_off=pair_off)
+        ctx.save_for_backward(feats, pairs, spans, span_count, dv)
+        ctx.scratch = scratch
+        return out[0].float()
+
+    @staticmethod
+    def backward(ctx, g):
+        feats, pairs, spans, span_count, dv = ctx.saved_tensors
+        db, dG = ops.span_predicate_grad(dv, pairs, spans, span_count, feats.shape[0], feats.shape[1], scratch=ctx.scratch)
+        gw = _span_cls_weight_grad(dG, feats) * g if ctx.needs_input_grad[5] else None
+        gb = db * g if ctx.needs_input_grad[6] else None
+        return None, None, None, None, None, gw, gb, None
 
 
 class RelationPredictor(nn.Module):
@@ -1033,6 +1068,8 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
                                             out_channels=cfg.PREDICT.PREDICATE_NUM,
                                             fuse_preprocess=getattr(cfg.PREDICT, "FUSE_PREPROCESS", False))
         self.pool_top_span = bool(getattr(cfg.RELPN.DPN, "POOL_TOP_SPAN", False))
+        # build extension: train the predicate head of tracklet samples on ground-truth-span-pooled rows
+        self.pool_gt_span = bool(getattr(cfg.RELPN.DPN, "POOL_GT_SPAN", False))
         # build extension: also return the bbox half of the pair builder (relative geometry [P,8,T]) from the
         # eval forward.  Nothing downstream of forward consumes it, so it is off unless asked for
         # (`model.pair_geometry(pair_list)` computes it on demand).
@@ -1138,12 +1175,59 @@ class BaseModel(_CachedWeightsMixin, nn.Module):
             feats = [self._pooled_pair_feats(p, dev) if self._is_tracklet_sample(p) else _f32(p.features, dev)
                      for p in pair_list]
         reloi_feats = self.rel_of_interest_pool(feats, duration_proposals)
-        loss_relation = 0
-        for reloi_feat, target in zip(reloi_feats, targets):
+        # RELPN.DPN.POOL_GT_SPAN: tracklet samples train the head on ground-truth-span-pooled rows;
+        # samples in the [P,F] baseline form keep the rows they bring
+        spanned = {i for i, p in enumerate(pair_list) if self.pool_gt_span and self._is_tracklet_sample(p)}
+        loss_relation = self._span_pooled_loss_rel(pair_list, target_list, sorted(spanned)) if spanned else 0
+        for i, (reloi_feat, target) in enumerate(zip(reloi_feats, targets)):
+            if i in spanned:
+                continue
             rel_logit = self.classifier(reloi_feat)
             loss_relation = loss_relation + F.binary_cross_entropy(rel_logit, target)
         loss_dict["loss_rel"] = loss_relation
         return loss_dict
+
+    SPAN_TARGET_FIELDS = (("spans", torch.int64), ("span_count", torch.int32), ("span_labels", torch.float32))
+
+    def _span_pooled_loss_rel(self, pair_list, target_list, members):
+        """loss_rel of the tracklet samples `members` under RELPN.DPN.POOL_GT_SPAN: per group of equal-shape segments one
+        _SpanPredicateLossFn call over the group's tracklets back to back, its pair tables with global ids and the
+        target fields 'spans' [P,G,2], 'span_count' [P] and 'span_labels' [P,G,K] of its segments; the sum over the
+        segments, like every loss_rel."""
+        w, b = self.classifier.rel_predictor.weight, self.classifier.rel_predictor.bias
+        if not w.is_cuda:
+            raise RuntimeError("training needs the model on the HIP device (model.cuda())")
+        dev, groups = w.device, {}
+        for i in members:
+            f = _f32(pair_list[i].get_field("tracklet_feats"), dev)
+            if f.dim() != 3:
+                raise ValueError(f"tracklet_feats must be [N,T,D], got {tuple(f.shape)}")
+            groups.setdefault(tuple(f.shape), []).append((i, f))
+        loss = 0
+        for (n, _, _), group in groups.items():
+            feats = _consecutive_view([f for _, f in group])
+            if feats is None:
+                feats = torch.cat([f for _, f in group])
+            pairs, offsets, fields = [], [0], {name: [] for name, _ in self.SPAN_TARGET_FIELDS}
+            for k, (i, _) in enumerate(group):
+                p = _segment_pairs(pair_list[i], n, dev)
+                for name, dtype in self.SPAN_TARGET_FIELDS:
+                    if not target_list[i].has_field(name):
+                        raise ValueError(f"RELPN.DPN.POOL_GT_SPAN needs the target field '{name}' (dataset.proposal_pair_list "
+                                         "with gt_rel_insts, max_spans and span_labels=True)")
+                    v = target_list[i].get_field(name)
+                    if not isinstance(v, torch.Tensor) or v.dtype != dtype or v.shape[0] != p.shape[0]:
+                        raise ValueError(f"target field '{name}' must be a {dtype} tensor with P = {p.shape[0]} rows")
+                    fields[name].append(v.to(dev))
+                pairs.append(p + k * n)
+                offsets.append(offsets[-1] + p.shape[0])
+            one = len(group) == 1
+            cat = lambda ts: ts[0].contiguous() if one else torch.cat(ts)   # noqa: E731
+            pair_off = None if one else torch.tensor(offsets, dtype=torch.int64, device=dev)
+            loss = loss + _SpanPredicateLossFn.apply(feats.contiguous(), cat(pairs), cat(fields["spans"]),
+                                                     cat(fields["span_count"]), cat(fields["span_labels"]),
+                                                     w.contiguous(), b.contiguous(), pair_off)
+        return loss
 
     # ------------------------------------------------------------------- eval
     @staticmethod

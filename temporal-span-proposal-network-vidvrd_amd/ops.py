@@ -18,6 +18,7 @@ __all__ = [
     "heads_pairgrid_f16x3_set_force_exact", "heads_pair_f16x3_set_diag_skip","temporal_mean", "temporal_sum", "pair_rows", "transpose_td",
     "forward_fused", "temporal_encoder_heads", "fused_workspace_bytes", "fused_bf16_workspace_bytes", "decode_topk", "decode_spans", "decode_span_relations",
     "span_anchor_labels", "span_loss", "span_anchor_sample", "pair_labels", "span_match",
+    "span_labels", "span_predicate_loss", "span_predicate_grad",
     "cast_bf16", "pack_conv3_bf16", "pack_heads_bf16", "conv3_tc_bf16", "heads_pairgrid_bf16",
     "pair_plan", "heads_pairlist_bf16",
     "transpose_cast_bf16", "temporal_encoder_heads_bf16",
@@ -925,6 +926,134 @@ def pair_labels(pairs, trackid, iou, insts, num_predicates, iou_thres=0.5, merge
                                                PAIR_LABEL_MERGES[merge], _p(labels), _p(spans), _p(span_count),
                                                _p(inst_cols), _stream()))
     return labels, spans, span_count, inst_cols
+
+
+def span_labels(pairs, trackid, iou, insts, num_predicates, spans, span_count, inst_cols, seg_frames, iou_thres=0.5,
+                merge="last", pair_off=None, track_off=None, iou_off=None, inst_off=None):
+    """A predicate label row per (pair, ground-truth span) (tspn_span_labels_f32, DESIGN.md §2 "span-pooled predicate
+    training"): the operands of pair_labels (one segment, or several with the four offsets) and its outputs spans int64
+    [P,G,2], span_count int32 [P], inst_cols int32 [R,2].  Row (p, g), g < min(span_count[p], G), holds the predicates of
+    the instances that cover pair p and whose clipped span is spans[p, g] (merge "or": all of them, "last": the one of the
+    largest r); every other row is zero.  Returns span_labels fp32 [P,G,K].  Nothing is synchronised."""
+    who = "span_labels"
+    _dev(pairs, f"{who}: pairs", torch.int64); _dev(trackid, f"{who}: trackid", torch.int64)
+    _dev(iou, f"{who}: iou"); _dev(insts, f"{who}: insts", torch.int64)
+    _dev(spans, f"{who}: spans", torch.int64); _dev(span_count, f"{who}: span_count", torch.int32)
+    _dev(inst_cols, f"{who}: inst_cols", torch.int32); _dev(seg_frames, f"{who}: seg_frames", torch.int64)
+    if pairs.dim() != 2 or pairs.shape[1] != 2 or trackid.dim() != 1 or insts.dim() != 2 or insts.shape[1] != 5:
+        raise ValueError(f"{who}: pairs must be [P,2], trackid [M] and insts [R,5], got {tuple(pairs.shape)}, "
+                         f"{tuple(trackid.shape)}, {tuple(insts.shape)}")
+    if merge not in PAIR_LABEL_MERGES:
+        raise ValueError(f"{who}: merge must be 'last' or 'or', got {merge!r}")
+    P, M, R = pairs.shape[0], trackid.shape[0], insts.shape[0]
+    if spans.dim() != 3 or spans.shape[0] != P or spans.shape[2] != 2 or span_count.shape != (P,) or inst_cols.shape != (R, 2):
+        raise ValueError(f"{who}: spans must be [P,G,2], span_count [P] and inst_cols [R,2] with P = {P}, R = {R}, got "
+                         f"{tuple(spans.shape)}, {tuple(span_count.shape)}, {tuple(inst_cols.shape)}")
+    K, G, thr = int(num_predicates), spans.shape[1], float(iou_thres)
+    if not 1 <= K <= 512 or not 1 <= G <= 16:
+        raise ValueError(f"{who}: needs 1 <= num_predicates <= 512 and 1 <= G <= 16, got {K}, {G}")
+    if thr != thr or thr in (float("inf"), float("-inf")):
+        raise ValueError(f"{who}: iou_thres must be finite, got {iou_thres}")
+    offs = (pair_off, track_off, iou_off, inst_off)
+    if all(o is None for o in offs):
+        S = 1
+        if iou.shape != (M, M):
+            raise ValueError(f"{who}: iou must be [M,M] with M = {M}, got {tuple(iou.shape)}")
+    elif any(o is None for o in offs):
+        raise ValueError(f"{who}: pair_off, track_off, iou_off and inst_off go together")
+    else:
+        for name, o in zip(("pair_off", "track_off", "iou_off", "inst_off"), offs):
+            _dev(o, f"{who}: {name}", torch.int64)
+        if any(o.dim() != 1 or o.shape != pair_off.shape for o in offs) or pair_off.numel() < 1:
+            raise ValueError(f"{who}: the offsets must be int64 [S+1]")
+        S = pair_off.numel() - 1
+        if iou.dim() != 1:
+            raise ValueError(f"{who}: iou of several segments must be flat, got {tuple(iou.shape)}")
+    if tuple(seg_frames.shape) != (S, 2):
+        raise ValueError(f"{who}: seg_frames must be [S,2] with S = {S}, got {tuple(seg_frames.shape)}")
+    out = torch.empty((P, G, K), dtype=torch.float32, device=pairs.device)
+    _abi.check(_abi.lib().tspn_span_labels_f32(_p(pairs), _p(pair_off), _p(trackid), _p(track_off), _p(iou), _p(iou_off),
+                                               _p(insts), _p(inst_off), _p(seg_frames), S, P, M, R, K, G, thr,
+                                               PAIR_LABEL_MERGES[merge], _p(spans), _p(span_count), _p(inst_cols), _p(out),
+                                               _stream()))
+    return out
+
+
+def _span_cls_rows(who, pairs, spans, span_count):
+    """(P, G) of the row operands of the span-pooled predicate training: pairs int64 [P,2], spans int64 [P,G,2],
+    span_count int32 [P]."""
+    _dev(pairs, f"{who}: pairs", torch.int64); _dev(spans, f"{who}: spans", torch.int64)
+    _dev(span_count, f"{who}: span_count", torch.int32)
+    P = pairs.shape[0]
+    if tuple(pairs.shape) != (P, 2) or spans.dim() != 3 or spans.shape[0] != P or spans.shape[2] != 2 \
+            or span_count.shape != (P,) or not 1 <= spans.shape[1] <= 16:
+        raise ValueError(f"{who}: pairs must be [P,2], spans [P,G,2] with 1 <= G <= 16 and span_count [P], got "
+                         f"{tuple(pairs.shape)}, {tuple(spans.shape)}, {tuple(span_count.shape)}")
+    return P, spans.shape[1]
+
+
+def span_predicate_loss(feats, pairs, spans, span_count, span_labels, cls_w, cls_b, pair_off=None, scratch=None):
+    """Loss of the span-pooled predicate head on the ground-truth span rows (tspn_span_predicate_loss_f32 +
+    tspn_span_predicate_loss_finish, DESIGN.md §2 "span-pooled predicate training"): feats fp32 [NT,T,D], pairs int64 [P,2]
+    global tracklet ids, spans / span_count / span_labels [P,G,K] as pair_labels and span_labels return them, cls_w
+    [K,2D], cls_b [K] or None, pair_off int64 [S+1] on the device (None: one segment).
+    Returns (out float64 [1+S] = (loss_rel, the loss of each segment), q fp32 [P*G,K] = the sigmoid of every row, dv fp32
+    [P*G,K] = d loss_rel / d v, seg_rows float64 [S], scratch uint8 = the projection scratch, free again and large enough
+    for span_predicate_grad).  Nothing is synchronised."""
+    who = "span_predicate_loss"
+    _dev(feats, f"{who}: feats"); _dev(cls_w, f"{who}: cls_w"); _dev(span_labels, f"{who}: span_labels")
+    if cls_b is not None:
+        _dev(cls_b, f"{who}: cls_b")
+    P, G = _span_cls_rows(who, pairs, spans, span_count)
+    if feats.dim() != 3 or cls_w.dim() != 2 or cls_w.shape[1] != 2 * feats.shape[2] or \
+            (cls_b is not None and cls_b.shape != (cls_w.shape[0],)):
+        raise ValueError(f"{who}: feats must be [NT,T,D], cls_w [K,2D] and cls_b [K], got {tuple(feats.shape)}, "
+                         f"{tuple(cls_w.shape)}")
+    NT, T, D = feats.shape
+    K = cls_w.shape[0]
+    if tuple(span_labels.shape) != (P, G, K):
+        raise ValueError(f"{who}: span_labels must be [P,G,K] = {(P, G, K)}, got {tuple(span_labels.shape)}")
+    S = 1
+    if pair_off is not None:
+        _dev(pair_off, f"{who}: pair_off", torch.int64)
+        if pair_off.dim() != 1 or pair_off.numel() < 1:
+            raise ValueError(f"{who}: pair_off must be int64 [S+1]")
+        S = pair_off.numel() - 1
+    dev, l, stream = feats.device, _abi.lib(), _stream()
+    scratch = _workspace(scratch, l.tspn_span_predicate_workspace_bytes(NT, T, D, K), dev, who)
+    q = torch.empty((P * G, K), dtype=torch.float32, device=dev)
+    dv = torch.empty_like(q)
+    partials = torch.empty((P * G,), dtype=torch.float64, device=dev)
+    seg_rows = torch.empty((S,), dtype=torch.float64, device=dev)
+    out = torch.empty((1 + S,), dtype=torch.float64, device=dev)
+    _abi.check(l.tspn_span_predicate_loss_f32(_p(feats), NT, T, D, _p(pairs), _p(pair_off), S, P, _p(spans), _p(span_count),
+                                              _p(span_labels), G, _p(cls_w), _p(cls_b), K, _p(q), _p(dv), _p(partials),
+                                              _p(seg_rows), _p(scratch), scratch.numel() * scratch.element_size(), stream))
+    _abi.check(l.tspn_span_predicate_loss_finish(_p(partials), _p(seg_rows), _p(pair_off), S, P, G, K, _p(out), stream))
+    return out, q, dv, seg_rows, scratch
+
+
+def span_predicate_grad(dv, pairs, spans, span_count, num_tracklets, num_frames, scratch=None):
+    """Gradient of the span-pooled predicate loss behind dv fp32 [P*G,K] (tspn_span_predicate_grad_f32): db fp32 [K] and
+    dG fp32 [NT,T,2K], the gradient with respect to the per-frame projections (column 2k: the subject half of predicate k,
+    2k+1: the object half); dW[k, h*D + c] = sum over (n, t) of dG[n, t, 2k+h] * feats[n, t, c] is a GEMM the caller runs.
+    `scratch`: uint8 of at least NT*(T+1)*2K*8 bytes (span_predicate_loss returns one).  Nothing is synchronised."""
+    who = "span_predicate_grad"
+    _dev(dv, f"{who}: dv")
+    P, G = _span_cls_rows(who, pairs, spans, span_count)
+    if dv.dim() != 2 or dv.shape[0] != P * G or dv.shape[1] < 1:
+        raise ValueError(f"{who}: dv must be [P*G,K] with P*G = {P * G}, got {tuple(dv.shape)}")
+    NT, T, K = int(num_tracklets), int(num_frames), dv.shape[1]
+    if NT < 0 or T < 1:
+        raise ValueError(f"{who}: needs num_tracklets >= 0 and num_frames >= 1, got {NT}, {T}")
+    dev = dv.device
+    scratch = _workspace(scratch, NT * (T + 1) * 2 * K * 8, dev, who)
+    db = torch.empty((K,), dtype=torch.float32, device=dev)
+    dG = torch.empty((NT, T, 2 * K), dtype=torch.float32, device=dev)
+    _abi.check(_abi.lib().tspn_span_predicate_grad_f32(_p(dv), _p(pairs), _p(spans), _p(span_count), NT, T, P, G, K, _p(db),
+                                                       _p(dG), _p(scratch), scratch.numel() * scratch.element_size(),
+                                                       _stream()))
+    return db, dG
 
 
 def span_match(rel_boxes, rel_range, rel_fend, rel_triplet, trk_boxes, pred_triplet, pred_pair, pred_span, iou_thr=0.5):

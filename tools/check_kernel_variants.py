@@ -4,7 +4,7 @@ tests/eval_kernel_variants.py for csrc/eval/*.hip, tests/relations_kernel_varian
 tests/pairlist_kernel_variants.py for csrc/pairlist/*.hip, tests/spanbf16_kernel_variants.py for csrc/spanbf16/*.hip,
 tests/spanloss_kernel_variants.py for csrc/spanloss/*.hip, tests/spansample_kernel_variants.py for csrc/spansample/*.hip,
 tests/pairlabels_kernel_variants.py for csrc/pairlabels/*.hip, tests/spanmatch_kernel_variants.py for csrc/spanmatch/*.hip,
-tests/evalobj_kernel_variants.py for csrc/evalobj/*.hip).
+tests/evalobj_kernel_variants.py for csrc/evalobj/*.hip, tests/spancls_kernel_variants.py for csrc/spancls/*.hip).
 
     rocprofv3 --kernel-trace --stats -d OUT -o run -- python -m pytest FILE... -q -m gpu
     python tools/check_kernel_variants.py OUT/.../run_kernel_stats.csv FILE...   (or OUT/.../run_results.db)
@@ -29,6 +29,7 @@ import pairlabels_kernel_variants  # noqa: E402
 import pairlist_kernel_variants  # noqa: E402
 import relations_kernel_variants  # noqa: E402
 import spanbf16_kernel_variants  # noqa: E402
+import spancls_kernel_variants  # noqa: E402
 import spanloss_kernel_variants  # noqa: E402
 import spanmatch_kernel_variants  # noqa: E402
 import spansample_kernel_variants  # noqa: E402
@@ -143,7 +144,7 @@ def main(argv):
               + pairlist_kernel_variants.VARIANTS + spanbf16_kernel_variants.VARIANTS
               + spanloss_kernel_variants.VARIANTS + spansample_kernel_variants.VARIANTS
               + pairlabels_kernel_variants.VARIANTS + spanmatch_kernel_variants.VARIANTS
-              + evalobj_kernel_variants.VARIANTS):
+              + evalobj_kernel_variants.VARIANTS + spancls_kernel_variants.VARIANTS):
         if not any(node.partition("::")[0] in files for node in r["tests"]):
             continue
         checked += 1
