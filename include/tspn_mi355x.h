@@ -1123,6 +1123,60 @@ int tspn_span_predicate_grad_f32(const float* dv, const int64_t* pairs, const in
                                  int64_t NT, int64_t T, int64_t P, int64_t G, int64_t K, float* db, float* dG,
                                  void* prefix_scratch, size_t prefix_scratch_bytes, void* stream);
 
+/* ---- per-frame object detection: RPN proposals, box head, box NMS (csrc/detect/tspn_detect.hip) -------------------
+ * Build-defined after detectron2 v0.6's faster_rcnn_R_*_C4 (DESIGN.md 2 "box decode", "box NMS", "proposals",
+ * "detections").  Boxes are fp32 (x1, y1, x2, y2) rows, 16-byte aligned (TSPN_EUNSUPPORTED otherwise; every other operand
+ * at its natural alignment); image_sizes fp32 [B, 2] = (height, width) on the device.  No entry synchronises, allocates or clears memory; every element of every output is written.
+ *
+ * tspn_rpn_decode_f32: logits fp32 [B, H, W, A], deltas fp32 [B, H, W, 4A] (channel 4a + k), cell_anchors fp32 [A, 4].
+ *   cand int64 [B, M]: flat candidate indices b H W A + (h W + w) A + a, as the selection of tspn_box_nms_f32 writes them
+ *   (a value outside image b's range, -1 included, is no candidate); NULL: every anchor in order, M = H W A.  The anchor
+ *   is the cell anchor plus (w, h, w, h) * stride in fp32; Box2BoxTransform.apply_deltas with weights 1 in fp32, dw / dh
+ *   clamped at log(1000 / 16); then the clip to [0, width] x [0, height].  out_boxes fp32 [B, M, 4], out_logits fp32
+ *   [B, M] (the candidate's logit), out_valid uint8 [B, M]: 1 iff the four corners before the clip and the logit are
+ *   finite; a row with 0 holds zeros.
+ *
+ * tspn_box_head_decode_f32: cls_logits fp32 [B R, K+1] (background last), deltas fp32 [B R, 4K], proposals fp32
+ *   [B, R, 4], proposal_count int64 [B] on the device.  Class-major outputs: out_scores fp32 [B, K, R] = softmax score,
+ *   out_boxes fp32 [B, K, R, 4] = apply_deltas with weights (wx, wy, ww, wh) on the proposal, clipped, out_valid uint8
+ *   [B, K, R] = 1 iff r < proposal_count[b], every softmax score and every decoded corner of the proposal's row is
+ *   finite, and score > score_thresh.  Where out_valid is 0 the score is 0: the validity byte is what the selection
+ *   reads.  Rows past the count and non-finite rows hold zero boxes.
+ *
+ * tspn_box_nms_f32: boxes fp32 [n, 4], scores fp32 [n], valid uint8 [n] or NULL (all valid), group_off int64 [G + 1] in
+ *   HOST memory, read before the call returns: group g is the candidates [group_off[g], group_off[g + 1]), ascending
+ *   from 0 to n.  Per group: the pre_topk best scores in selection order (tspn order key: NaN first, then descending,
+ *   lower index first on ties); of those, the rows with valid == 0 and (min_size >= 0) the boxes with width <= min_size
+ *   or height <= min_size are dropped; greedy NMS in that order, a kept box i suppressing a later j iff
+ *   inter / (area_i + area_j - inter) > iou_threshold in fp32 (torchvision's CPU kernel); the first post_topk survivors.
+ *   out_index int64 [G, post_topk]: their flat indices into boxes, best first, -1 past the count; out_count int64 [G];
+ *   out_keep uint8 [n] or NULL: 1 for the candidates listed in out_index, else 0.  boxes == NULL runs the selection
+ *   alone (valid and out_keep must be NULL, iou_threshold and min_size are not read).
+ *   scratch: at least tspn_box_nms_scratch_bytes(group_off, G, pre_topk, boxes == NULL) bytes, 16-byte aligned
+ *   (TSPN_EWORKSPACE otherwise); it may hold anything on entry, nothing outside those bytes is touched, and every byte
+ *   of which the call reads it has written before.  Limits: 1 <= post_topk <= pre_topk <= 8192, n < 2^31, G < 2^24.
+ *   The query returns 0 for what the entry refuses and for G == 0.
+ *
+ * tspn_detections_topk_f32: scores / boxes / keep as tspn_box_head_decode_f32 and tspn_box_nms_f32 (G = B K groups of R)
+ *   leave them.  Per image the D best kept candidates over all classes, best first, ties to the lower r K + c:
+ *   out_boxes fp32 [B, D, 4], out_scores fp32 [B, D], out_classes int64 [B, D], out_count int64 [B]; rows past the count
+ *   are zero.  Limit: D <= 1024. */
+int tspn_rpn_decode_f32(const int64_t* cand, const float* logits, const float* deltas, const float* cell_anchors,
+                        const float* image_sizes, int64_t B, int64_t H, int64_t W, int64_t A, int64_t M, float stride,
+                        float* out_boxes, float* out_logits, uint8_t* out_valid, void* stream);
+int tspn_box_head_decode_f32(const float* cls_logits, const float* deltas, const float* proposals,
+                             const int64_t* proposal_count, const float* image_sizes, int64_t B, int64_t R, int64_t K,
+                             float wx, float wy, float ww, float wh, float score_thresh, float* out_scores,
+                             float* out_boxes, uint8_t* out_valid, void* stream);
+size_t tspn_box_nms_scratch_bytes(const int64_t* group_off, int64_t G, int64_t pre_topk, int select_only);
+int tspn_box_nms_f32(const float* boxes, const float* scores, const uint8_t* valid, int64_t n, const int64_t* group_off,
+                     int64_t G, int64_t pre_topk, float iou_threshold, int64_t post_topk, float min_size,
+                     int64_t* out_index, int64_t* out_count, uint8_t* out_keep, void* scratch, size_t scratch_bytes,
+                     void* stream);
+int tspn_detections_topk_f32(const float* scores, const float* boxes, const uint8_t* keep, int64_t B, int64_t K, int64_t R,
+                             int64_t D, float* out_boxes, float* out_scores, int64_t* out_classes, int64_t* out_count,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

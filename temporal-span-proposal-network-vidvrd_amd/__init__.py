@@ -17,9 +17,11 @@ from .model import (BaseModel, DPN, DPNHead, PPN, PPNHead, RelOIPool, RelPN,  # 
                     RelationPredictor, TemporalProposals, make_relpn)
 from .pair_list import PairList, TargetList  # noqa: F401
 from .sampler import BalancedPositiveNegativePairSampler  # noqa: F401
-from .anchor_generator import AnchorGenerator, generate_anchors, make_anchor_generator  # noqa: F401
+from .anchor_generator import AnchorGenerator, generate_anchors, generate_cell_anchors_2d, make_anchor_generator  # noqa: F401
 from . import dist  # noqa: F401
 from . import roi_head  # noqa: F401
 from .roi_head import Res5RoIHead, ResNetC4  # noqa: F401
+from . import detector  # noqa: F401
+from .detector import BoxPredictor, FasterRCNNC4, RPNHead  # noqa: F401
 
 __version__ = "0.1.0"

@@ -207,6 +207,12 @@ PROTOTYPES = {
     "tspn_eval_greedy_match_f64": (_int, [_vp, _vp, _i64, _i64, ctypes.c_double, _vp, _vp, _vp, _vp]),
     "tspn_evalobj_tiou_f64": (_int, [_vp] * 5 + [_i64] + [_vp] * 5),
     "tspn_evalobj_claim": (_int, [_vp] * 4 + [_i64, _i64, ctypes.c_double, _vp, _vp, _vp]),
+    "tspn_rpn_decode_f32": (_int, [_vp] * 5 + [_i64] * 5 + [ctypes.c_float] + [_vp] * 4),
+    "tspn_box_head_decode_f32": (_int, [_vp] * 5 + [_i64] * 3 + [ctypes.c_float] * 5 + [_vp] * 4),
+    "tspn_box_nms_scratch_bytes": (_sz, [ctypes.POINTER(_i64), _i64, _i64, _int]),
+    "tspn_box_nms_f32": (_int, [_vp] * 3 + [_i64, ctypes.POINTER(_i64), _i64, _i64, ctypes.c_float, _i64, ctypes.c_float]
+                         + [_vp] * 4 + [_sz, _vp]),
+    "tspn_detections_topk_f32": (_int, [_vp] * 3 + [_i64] * 4 + [_vp] * 5),
 }
 
 _lib = None

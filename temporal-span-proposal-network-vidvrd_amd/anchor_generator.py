@@ -5,11 +5,13 @@ An anchor is a (start, end) window: width `sizes[a]` centred on every `anchor_st
 time axis, `0 .. T` inclusive, location-major / size-minor — the candidate order `c = t*A + a` that
 the GPU span decode (`tspn_decode_spans_f32`, stride-1 grid) uses.  Works on numpy >= 1.24 (the
 reference needs the removed `np.float`)."""
+import math
+
 import numpy as np
 import torch
 from torch import nn
 
-__all__ = ["AnchorGenerator", "generate_anchors", "make_anchor_generator"]
+__all__ = ["AnchorGenerator", "generate_anchors", "make_anchor_generator", "generate_cell_anchors_2d"]
 
 
 def generate_anchors(stride=8, sizes=(4, 8, 16)):
@@ -17,6 +19,21 @@ def generate_anchors(stride=8, sizes=(4, 8, 16)):
     (anchor_generator.py:67-104: `stride * (size / stride)` wide)."""
     widths = float(stride) * (np.asarray(sizes, dtype=np.float64) / float(stride))
     return torch.from_numpy(np.stack([0.0 - 0.5 * widths, 0.0 + 0.5 * widths], axis=1))
+
+
+def generate_cell_anchors_2d(sizes=(32, 64, 128, 256, 512), aspect_ratios=(0.5, 1.0, 2.0)):
+    """The 2-D cell anchors of detectron2's DefaultAnchorGenerator (generate_cell_anchors, offset 0) for the per-frame
+    detector: float32 tensor [A,4] of (x1, y1, x2, y2) around the origin, size-major / ratio-minor, computed on the host in
+    Python floats as detectron2 does -- w = sqrt(size^2 / ratio), h = ratio * w.  The anchor of flat index
+    (h W + w) A + a on a stride-s map is row a plus (w s, h s, w s, h s) (DESIGN.md 2 "box decode")."""
+    rows = []
+    for size in sizes:
+        area = size ** 2.0
+        for ratio in aspect_ratios:
+            w = math.sqrt(area / ratio)
+            h = ratio * w
+            rows.append([-w / 2.0, -h / 2.0, w / 2.0, h / 2.0])
+    return torch.tensor(rows, dtype=torch.float32)
 
 
 class AnchorGenerator(nn.Module):

@@ -5,7 +5,8 @@
 //                        span_row_topk_q_kernel (spanbf16/tspn_span_bf16.hip)
 //   select_topk_sorted   segment_topk_kernel (tspn_decode.hip), segment_span_topk_kernel
 //                        (relations/tspn_span_relations.hip): exact top-M of Q keyed candidates by one workgroup, in
-//                        torch's stable descending order
+//                        torch's stable descending order; box_nms_select_kernel (detect/tspn_detect.hip) runs the same
+//                        body at MAXM = kSelectMaxMBig
 //   argmax_first         the class labels of both segment kernels
 #pragma once
 #include "tspn_common.h"
@@ -91,20 +92,24 @@ __device__ __forceinline__ void wave_row_topk(const float (&v)[kRowTopkVPT], int
 
 constexpr int kSelectThreads = 1024;   // the workgroup size select_topk_sorted expects
 constexpr int kSelectMaxM = 1024;
+constexpr int kSelectMaxMBig = 8192;   // the box NMS's capacity (detect/tspn_detect.hip): 64 KB of pairs, dynamic LDS
 
-struct SelectLds {
+template <int MAXM>
+struct SelectLdsT {
   unsigned hist[256];
   unsigned prefix, need, count;
-  unsigned kk[kSelectMaxM];
-  int ki[kSelectMaxM];
+  unsigned kk[MAXM];
+  int ki[MAXM];
 };
+using SelectLds = SelectLdsT<kSelectMaxM>;
+using SelectLdsBig = SelectLdsT<kSelectMaxMBig>;
 
 // Called by all kSelectThreads threads of a workgroup.  key(i), i in [0, Q): the order key of candidate i (larger first,
-// lower i first on ties); at least M <= kSelectMaxM candidates have a key > 0.  Exact radix select of the M-th largest
+// lower i first on ties); at least M <= MAXM candidates have a key > 0.  Exact radix select of the M-th largest
 // key (4 x 8-bit histograms), index-select among the candidates that tie with it, compaction into LDS and a bitonic
 // sort: on return, after a barrier, L.ki[r] is the flat index of the r-th best candidate and L.kk[r] its key, r < M.
-template <class KeyFn>
-__device__ __forceinline__ void select_topk_sorted(SelectLds& L, KeyFn key, int Q, int M) {
+template <int MAXM, class KeyFn>
+__device__ __forceinline__ void select_topk_sorted(SelectLdsT<MAXM>& L, KeyFn key, int Q, int M) {
   const int tid = threadIdx.x;
   // ---- exact M-th largest key by 4 radix passes (most significant byte first)
   if (tid == 0) {
@@ -176,7 +181,7 @@ __device__ __forceinline__ void select_topk_sorted(SelectLds& L, KeyFn key, int 
     const unsigned k = key(i);
     if (k > kth || (k == kth && (unsigned)i <= last_tie_idx)) {
       const unsigned slot = atomicAdd(&L.count, 1u);
-      if (slot < (unsigned)kSelectMaxM) {
+      if (slot < (unsigned)MAXM) {
         L.kk[slot] = k;
         L.ki[slot] = i;
       }

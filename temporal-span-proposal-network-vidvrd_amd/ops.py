@@ -28,6 +28,7 @@ __all__ = [
     "wino63_f16x3_set_input_form", "wino63_f16x3_input_form", "wino63_f16x3_input",
     "pack_conv2d", "pack_conv2d_frag", "conv2d_nhwc", "roi_align_nhwc", "pack_conv2d_frag_bf16", "conv2d_nhwc_bf16", "max_pool_nhwc", "pack_conv2d_frag_cin4", "conv2d_nhwc_cin4", "max_pool_nhwc_bf16", "pack_stem_bf16", "stem_conv_bf16", "stem_pool_bf16", "bottleneck_tail_bf16",
     "eval_traj_volume", "eval_viou", "eval_greedy_match", "evalobj_tiou", "evalobj_claim",
+    "rpn_decode", "box_head_decode", "box_nms", "box_nms_workspace_bytes", "detections_topk", "rpn_proposals", "box_detections",
     "status_words", "status_fault", "status_clear", "status_selftest",
 ]
 
@@ -2147,6 +2148,177 @@ def evalobj_claim(best, best_index, groups, pred_group, n_gt, thresh_t, claim=No
     _abi.check(_abi.lib().tspn_evalobj_claim(_p(best), _p(best_index), _p(groups), _p(pred_group), P, int(n_gt),
                                              float(thresh_t), _p(claim), _p(hit), _stream()))
     return claim, hit
+
+
+# ---- per-frame object detection: RPN proposals, box head, box NMS (csrc/detect/tspn_detect.hip)
+def _image_sizes(who, image_sizes, B):
+    if _dev(image_sizes, "image_sizes").shape != (B, 2):
+        raise ValueError(f"{who}: image_sizes must be fp32 [{B}, 2] = (height, width), got {tuple(image_sizes.shape)}")
+
+
+def _group_off(who, group_off):
+    """Host group offsets (a sequence or a CPU tensor of G + 1 ascending integers) as the int64 array the C entry reads."""
+    if isinstance(group_off, torch.Tensor):
+        if group_off.is_cuda:
+            raise ValueError(f"{who}: group_off lives in host memory (the entry checks it before it launches)")
+        group_off = group_off.tolist()
+    vals = [int(v) for v in group_off]
+    if not vals:
+        raise ValueError(f"{who}: group_off needs G + 1 entries")
+    return (ctypes.c_int64 * len(vals))(*vals), len(vals) - 1
+
+
+def box_nms_workspace_bytes(group_off, pre_topk, select_only=False):
+    """Bytes of scratch tspn_box_nms_f32 needs for these groups (0: a shape it refuses, or no group)."""
+    arr, G = _group_off("box_nms_workspace_bytes", group_off)
+    return int(_abi.lib().tspn_box_nms_scratch_bytes(arr, G, int(pre_topk), 1 if select_only else 0))
+
+
+def box_nms(boxes, scores, group_off, pre_topk, iou_threshold, post_topk, min_size=-1.0, valid=None, want_keep=False,
+            workspace=None):
+    """Greedy 2-D box NMS per contiguous group (tspn_box_nms_f32): boxes fp32 [n,4] (None: the selection alone), scores fp32
+    [n], valid uint8 [n] or None, group_off G + 1 host offsets ascending from 0 to n.  Per group: the pre_topk best scores
+    in selection order, invalid rows and (min_size >= 0) boxes not larger than min_size dropped, torchvision's NMS at
+    iou_threshold, the first post_topk survivors.  Returns (index int64 [G, post_topk] of flat candidate indices, -1 past
+    the count; count int64 [G]; keep uint8 [n] or None).  No host synchronisation."""
+    who = "box_nms"
+    _dev(scores, "scores")
+    n = scores.shape[0]
+    if scores.dim() != 1:
+        raise ValueError(f"{who}: scores must be [n]")
+    if boxes is not None and tuple(_dev(boxes, "boxes").shape) != (n, 4):
+        raise ValueError(f"{who}: boxes must be [{n}, 4], got {tuple(boxes.shape)}")
+    if valid is not None and tuple(_dev(valid, "valid", torch.uint8).shape) != (n,):
+        raise ValueError(f"{who}: valid must be uint8 [{n}]")
+    arr, G = _group_off(who, group_off)
+    pre_topk, post_topk = int(pre_topk), int(post_topk)
+    l = _abi.lib()
+    dev = scores.device
+    index = torch.empty((G, max(post_topk, 0)), dtype=torch.int64, device=dev)
+    count = torch.empty((G,), dtype=torch.int64, device=dev)
+    keep = torch.empty((n,), dtype=torch.uint8, device=dev) if (want_keep and boxes is not None) else None
+    need = l.tspn_box_nms_scratch_bytes(arr, G, pre_topk, 1 if boxes is None else 0)
+    ws = _workspace(workspace, need, dev, who, sizes=True)
+    _abi.check(l.tspn_box_nms_f32(_p(boxes), _p(scores), _p(valid), n, arr, G, pre_topk, float(iou_threshold), post_topk,
+                                  float(min_size), _p(index), _p(count), _p(keep), _p(ws),
+                                  ws.numel() * ws.element_size(), _stream()))
+    return index, count, keep
+
+
+def rpn_decode(cand, logits, deltas, cell_anchors, stride, image_sizes):
+    """Anchors + RPN deltas -> clipped boxes (tspn_rpn_decode_f32): logits fp32 [B,H,W,A], deltas fp32 [B,H,W,4A] (channel
+    4a + k), cell_anchors fp32 [A,4], image_sizes fp32 [B,2] = (height, width); cand int64 [B,M] of flat indices
+    b HWA + (h W + w) A + a (None: every anchor).  Returns (boxes [B,M,4], logits [B,M], valid uint8 [B,M])."""
+    who = "rpn_decode"
+    _dev(logits, "logits"), _dev(deltas, "deltas"), _dev(cell_anchors, "cell_anchors")
+    if logits.dim() != 4 or cell_anchors.shape != (logits.shape[3], 4) or \
+            tuple(deltas.shape) != tuple(logits.shape[:3]) + (4 * logits.shape[3],):
+        raise ValueError(f"{who}: logits [B,H,W,A], deltas [B,H,W,4A] and cell_anchors [A,4] expected, got "
+                         f"{tuple(logits.shape)}, {tuple(deltas.shape)} and {tuple(cell_anchors.shape)}")
+    B, H, W, A = logits.shape
+    _image_sizes(who, image_sizes, B)
+    if cand is not None and (_dev(cand, "cand", torch.int64).dim() != 2 or cand.shape[0] != B):
+        raise ValueError(f"{who}: cand must be int64 [{B}, M]")
+    M = H * W * A if cand is None else cand.shape[1]
+    dev = logits.device
+    boxes = torch.empty((B, M, 4), dtype=torch.float32, device=dev)
+    out_logits = torch.empty((B, M), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, M), dtype=torch.uint8, device=dev)
+    _abi.check(_abi.lib().tspn_rpn_decode_f32(_p(cand), _p(logits), _p(deltas), _p(cell_anchors), _p(image_sizes), B, H, W, A,
+                                              M, float(stride), _p(boxes), _p(out_logits), _p(valid), _stream()))
+    return boxes, out_logits, valid
+
+
+def box_head_decode(cls_logits, deltas, proposals, proposal_count, image_sizes, score_thresh=0.05,
+                    weights=(10.0, 10.0, 5.0, 5.0)):
+    """Softmax scores and class-specific boxes of the box head (tspn_box_head_decode_f32): cls_logits fp32 [B R, K+1]
+    (background last), deltas fp32 [B R, 4K], proposals fp32 [B,R,4], proposal_count int64 [B].  Returns class-major
+    (scores [B,K,R], boxes [B,K,R,4], valid uint8 [B,K,R]); where valid is 0 the score is 0."""
+    who = "box_head_decode"
+    _dev(cls_logits, "cls_logits"), _dev(deltas, "deltas"), _dev(proposals, "proposals")
+    if proposals.dim() != 3 or proposals.shape[2] != 4:
+        raise ValueError(f"{who}: proposals must be [B,R,4], got {tuple(proposals.shape)}")
+    B, R, _ = proposals.shape
+    if cls_logits.dim() != 2 or cls_logits.shape[0] != B * R or cls_logits.shape[1] < 2 or \
+            tuple(deltas.shape) != (B * R, 4 * (cls_logits.shape[1] - 1)):
+        raise ValueError(f"{who}: cls_logits [{B * R}, K+1] and deltas [{B * R}, 4K] expected, got "
+                         f"{tuple(cls_logits.shape)} and {tuple(deltas.shape)}")
+    K = cls_logits.shape[1] - 1
+    if _dev(proposal_count, "proposal_count", torch.int64).shape != (B,):
+        raise ValueError(f"{who}: proposal_count must be int64 [{B}]")
+    _image_sizes(who, image_sizes, B)
+    dev = proposals.device
+    scores = torch.empty((B, K, R), dtype=torch.float32, device=dev)
+    boxes = torch.empty((B, K, R, 4), dtype=torch.float32, device=dev)
+    valid = torch.empty((B, K, R), dtype=torch.uint8, device=dev)
+    wx, wy, ww, wh = (float(v) for v in weights)
+    _abi.check(_abi.lib().tspn_box_head_decode_f32(_p(cls_logits), _p(deltas), _p(proposals), _p(proposal_count),
+                                                   _p(image_sizes), B, R, K, wx, wy, ww, wh, float(score_thresh),
+                                                   _p(scores), _p(boxes), _p(valid), _stream()))
+    return scores, boxes, valid
+
+
+def detections_topk(scores, boxes, keep, detections_per_image=100):
+    """Per image the best NMS survivors over all classes (tspn_detections_topk_f32): scores [B,K,R], boxes [B,K,R,4], keep
+    uint8 [B,K,R] -> (boxes [B,D,4], scores [B,D], classes int64 [B,D], count int64 [B]); ties to the lower r K + c."""
+    who = "detections_topk"
+    _dev(scores, "scores"), _dev(boxes, "boxes"), _dev(keep, "keep", torch.uint8)
+    if scores.dim() != 3 or tuple(boxes.shape) != tuple(scores.shape) + (4,) or keep.shape != scores.shape:
+        raise ValueError(f"{who}: scores [B,K,R], boxes [B,K,R,4] and keep [B,K,R] expected")
+    B, K, R = scores.shape
+    D = int(detections_per_image)
+    dev = scores.device
+    ob = torch.empty((B, D, 4), dtype=torch.float32, device=dev)
+    osc = torch.empty((B, D), dtype=torch.float32, device=dev)
+    oc = torch.empty((B, D), dtype=torch.int64, device=dev)
+    cnt = torch.empty((B,), dtype=torch.int64, device=dev)
+    _abi.check(_abi.lib().tspn_detections_topk_f32(_p(scores), _p(boxes), _p(keep), B, K, R, D, _p(ob), _p(osc), _p(oc),
+                                                   _p(cnt), _stream()))
+    return ob, osc, oc, cnt
+
+
+def rpn_proposals(logits, deltas, cell_anchors, stride, image_sizes, pre_nms_topk=6000, post_nms_topk=1000, nms_thresh=0.7,
+                  min_size=0.0, workspace=None):
+    """detectron2's find_top_rpn_proposals (eval) on one feature level: per image the pre_nms_topk best logits, decoded,
+    non-finite rows dropped, clipped, boxes not larger than min_size dropped, NMS at nms_thresh, the first post_nms_topk.
+    Returns (boxes [B,post,4], logits [B,post], count int64 [B]); rows past the count are zero.  No host synchronisation."""
+    who = "rpn_proposals"
+    _dev(logits, "logits")
+    if logits.dim() != 4:
+        raise ValueError(f"{who}: logits must be [B,H,W,A]")
+    B = logits.shape[0]
+    HWA = logits.shape[1] * logits.shape[2] * logits.shape[3]
+    M = min(int(pre_nms_topk), HWA)
+    post = min(int(post_nms_topk), M)
+    sel_off, nms_off = range(0, (B + 1) * HWA, HWA), range(0, (B + 1) * M, M)
+    need = max(box_nms_workspace_bytes(sel_off, M, True), box_nms_workspace_bytes(nms_off, M))
+    ws = _workspace(workspace, need, logits.device, who, sizes=True)
+    cand, _, _ = box_nms(None, logits.reshape(-1), sel_off, M, 0.0, M, workspace=ws)
+    boxes, lg, valid = rpn_decode(cand, logits, deltas, cell_anchors, stride, image_sizes)
+    index, count, _ = box_nms(boxes.view(-1, 4), lg.view(-1), nms_off, M, nms_thresh, post, min_size=min_size,
+                              valid=valid.view(-1), workspace=ws)
+    live = index >= 0
+    at = index.clamp(min=0)
+    out_boxes = torch.zeros((B, int(post_nms_topk), 4), dtype=torch.float32, device=logits.device)
+    out_logits = torch.zeros((B, int(post_nms_topk)), dtype=torch.float32, device=logits.device)
+    out_boxes[:, :post] = torch.where(live[..., None], boxes.view(-1, 4)[at], out_boxes[:, :post])
+    out_logits[:, :post] = torch.where(live, lg.view(-1)[at], out_logits[:, :post])
+    return out_boxes, out_logits, count
+
+
+def box_detections(cls_logits, deltas, proposals, proposal_count, image_sizes, score_thresh=0.05, nms_thresh=0.5,
+                   detections_per_image=100, weights=(10.0, 10.0, 5.0, 5.0), workspace=None):
+    """detectron2's fast_rcnn_inference per image: softmax, class-specific boxes, clip, score > score_thresh, NMS per class
+    at nms_thresh, the detections_per_image best over all classes.  Returns (boxes [B,D,4], scores [B,D], classes int64
+    [B,D], count int64 [B]).  No host synchronisation."""
+    scores, boxes, valid = box_head_decode(cls_logits, deltas, proposals, proposal_count, image_sizes, score_thresh, weights)
+    B, K, R = scores.shape
+    if R == 0:
+        raise ValueError("box_detections: no proposal rows (R = 0)")
+    _, _, keep = box_nms(boxes.view(-1, 4), scores.view(-1), range(0, (B * K + 1) * R, R), R, nms_thresh, R, min_size=-1.0,
+                         valid=valid.view(-1), want_keep=True, workspace=workspace)
+    return detections_topk(scores, boxes, keep.view(B, K, R), detections_per_image)
+
 
 # every public operator runs with the device of its operands made current (see _on_tensor_device)
 for _name in __all__:

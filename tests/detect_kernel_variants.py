@@ -1,0 +1,66 @@
+"""Which compiled kernel the per-frame detector's post-processing launches, the condition its launcher uses, the
+granularities of each and the tests that reach it: the table of tests/kernel_variants.py, in the same format, for
+temporal-span-proposal-network-vidvrd_amd/csrc/detect/*.hip.
+
+tests/test_detector_reference_host.py keeps this table equal to the sources and its node ids pointing at tests that
+exist; tools/check_kernel_variants.py checks a `rocprofv3 --kernel-trace --stats` run against this table too.
+
+Granularities: the two decode kernels run one thread per (image, candidate) or (image, proposal), 256 to a workgroup
+(1 x 1, 3 x 5 and 9 x 7 maps with 3 and 15 anchors; 1, 65 and 300 proposals); the NMS selection runs one 1024-thread
+workgroup per group (groups of 0, 1, 63 ... 2049 candidates: below, at and past one pass of the workgroup, and past
+pre_topk), the mask kernel one wave per 64 x 64 tile of the upper triangle (1, 2, 3, 17 and 32 column blocks), the scan
+one wave per group with the removed bits of column blocks l and l + 64 on lane l, the offsets kernel 256 offsets per
+launch; the final top-k runs one 1024-thread workgroup per image."""
+
+BN = "tests/test_gpu_box_nms.py::"
+DD = "tests/test_gpu_detect_decode.py::"
+DT = "tests/test_gpu_detector.py::"
+NMS = "tspn_box_nms_f32"
+
+
+def _row(kernel, inst, entry, when, tests, align="no alignment requirement"):
+    return {"kernel": kernel, "inst": inst, "entry": entry, "when": when, "tests": list(tests), "align": align}
+
+
+NMS_TESTS = [BN + "test_one_group_at_the_block_edges", BN + "test_three_unequal_groups_with_an_empty_one",
+             BN + "test_all_none_and_exact_threshold", BN + "test_post_topk_below_and_above_the_survivors",
+             BN + "test_invalid_rows_inside_and_outside_the_topk_and_min_size", BN + "test_nan_and_infinite_scores_and_boxes",
+             BN + "test_the_result_does_not_depend_on_the_scratch", DT + "test_compositions_equal_the_restatement"]
+
+VARIANTS = [
+    # ------------------------------------------------------------------------------------ detect/tspn_detect.hip
+    _row("rpn_decode_f32_kernel", None, "tspn_rpn_decode_f32",
+         "B > 0 and M > 0; one thread per (image, candidate): the anchor of the candidate's flat index, apply_deltas with "
+         "weights 1, the clip, the validity byte",
+         [DD + "test_rpn_decode_is_within_the_derived_bound", DD + "test_rpn_decode_exact_cases",
+          DT + "test_compositions_equal_the_restatement"],
+         align="out_boxes 16-byte aligned (written as float4); every other operand at its natural alignment"),
+    _row("box_head_decode_f32_kernel", None, "tspn_box_head_decode_f32",
+         "B > 0 and R > 0; one thread per (image, proposal): softmax over K + 1 logits, K class boxes, class-major stores",
+         [DD + "test_box_head_decode_is_within_the_derived_bounds", DD + "test_box_head_decode_exact_cases",
+          DT + "test_compositions_equal_the_restatement"],
+         align="proposals and out_boxes 16-byte aligned (float4 rows); every other operand at its natural alignment"),
+    _row("box_nms_offsets_kernel", None, NMS,
+         "G > 0; ceil((G + 1) / 256) launches: the host group offsets, 256 per launch by value, into the scratch",
+         NMS_TESTS + [BN + "test_the_selection_alone"], align="scratch 16-byte aligned"),
+    _row("box_nms_select_kernel", "false", NMS,
+         "G > 0 and boxes != NULL; one workgroup per group: tspn::select_topk_sorted at capacity 8192, then the sorted flat "
+         "indices (-1: invalid or small), the sorted boxes and the count into the scratch; out_keep zeroed",
+         NMS_TESTS, align="boxes 16-byte aligned (float4 rows)"),
+    _row("box_nms_select_kernel", "true", NMS,
+         "G > 0 and boxes == NULL: the selection is the result (out_index, out_count)",
+         [BN + "test_the_selection_alone", DT + "test_compositions_equal_the_restatement"],
+         align="out_index and out_count 8-byte aligned"),
+    _row("box_nms_mask_kernel", None, NMS,
+         "boxes != NULL and the largest group is not empty; G * nb * nb workgroups of one wave, nb = ceil(min(pre_topk, "
+         "largest group) / 64); a tile below the diagonal or past the group's count returns at once",
+         NMS_TESTS, align="scratch 16-byte aligned"),
+    _row("box_nms_scan_kernel", None, NMS,
+         "boxes != NULL; one wave per group: diagonal block in registers, kept rows' words ORed over the later column "
+         "blocks, stops at post_topk survivors; fills out_index past the count with -1",
+         NMS_TESTS, align="out_index and out_count 8-byte aligned"),
+    _row("detections_topk_kernel", None, "tspn_detections_topk_f32",
+         "B > 0; one workgroup per image: counts the kept candidates, tspn::select_topk_sorted over i = r K + c, gathers",
+         [DT + "test_compositions_equal_the_restatement", DT + "test_detections_topk_ties_and_counts"],
+         align="boxes and out_boxes 16-byte aligned"),
+]

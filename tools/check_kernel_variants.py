@@ -4,7 +4,8 @@ tests/eval_kernel_variants.py for csrc/eval/*.hip, tests/relations_kernel_varian
 tests/pairlist_kernel_variants.py for csrc/pairlist/*.hip, tests/spanbf16_kernel_variants.py for csrc/spanbf16/*.hip,
 tests/spanloss_kernel_variants.py for csrc/spanloss/*.hip, tests/spansample_kernel_variants.py for csrc/spansample/*.hip,
 tests/pairlabels_kernel_variants.py for csrc/pairlabels/*.hip, tests/spanmatch_kernel_variants.py for csrc/spanmatch/*.hip,
-tests/evalobj_kernel_variants.py for csrc/evalobj/*.hip, tests/spancls_kernel_variants.py for csrc/spancls/*.hip).
+tests/evalobj_kernel_variants.py for csrc/evalobj/*.hip, tests/spancls_kernel_variants.py for csrc/spancls/*.hip,
+tests/detect_kernel_variants.py for csrc/detect/*.hip).
 
     rocprofv3 --kernel-trace --stats -d OUT -o run -- python -m pytest FILE... -q -m gpu
     python tools/check_kernel_variants.py OUT/.../run_kernel_stats.csv FILE...   (or OUT/.../run_results.db)
@@ -22,6 +23,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import detect_kernel_variants  # noqa: E402
 import eval_kernel_variants  # noqa: E402
 import evalobj_kernel_variants  # noqa: E402
 import kernel_variants  # noqa: E402
@@ -144,7 +146,8 @@ def main(argv):
               + pairlist_kernel_variants.VARIANTS + spanbf16_kernel_variants.VARIANTS
               + spanloss_kernel_variants.VARIANTS + spansample_kernel_variants.VARIANTS
               + pairlabels_kernel_variants.VARIANTS + spanmatch_kernel_variants.VARIANTS
-              + evalobj_kernel_variants.VARIANTS + spancls_kernel_variants.VARIANTS):
+              + evalobj_kernel_variants.VARIANTS + spancls_kernel_variants.VARIANTS
+              + detect_kernel_variants.VARIANTS):
         if not any(node.partition("::")[0] in files for node in r["tests"]):
             continue
         checked += 1
