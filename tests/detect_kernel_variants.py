@@ -6,13 +6,18 @@ tests/test_detector_reference_host.py keeps this table equal to the sources and 
 exist; tools/check_kernel_variants.py checks a `rocprofv3 --kernel-trace --stats` run against this table too.
 
 Granularities: the two decode kernels run one thread per (image, candidate) or (image, proposal), 256 to a workgroup
-(1 x 1, 3 x 5 and 9 x 7 maps with 3 and 15 anchors; 1, 65 and 300 proposals); the NMS selection runs one 1024-thread
-workgroup per group (groups of 0, 1, 63 ... 2049 candidates: below, at and past one pass of the workgroup, and past
-pre_topk), the mask kernel one wave per 64 x 64 tile of the upper triangle (1, 2, 3, 17 and 32 column blocks), the scan
-one wave per group with the removed bits of column blocks l and l + 64 on lane l, the offsets kernel 256 offsets per
-launch; the final top-k runs one 1024-thread workgroup per image."""
+(1 x 1, 3 x 5, 9 x 7 and 20 x 24 maps with 3 and 15 anchors; 1, 65, 70 and 300 proposals); the NMS selection runs one
+1024-thread workgroup per group (groups of 0, 1, 63 ... 2049 candidates: below, at and past one pass of the workgroup, and
+past pre_topk; 4096 ... 8300 and 70 000 candidates at M = 4096 ... 8192: the 8192-slot sort, full and with up to 4095 pad
+slots, and ties cut above index 65 536), the mask kernel one wave per 64 x 64 tile of the upper triangle (1, 2, 3, 17, 32,
+64, 65, 94 and 128 column blocks), the scan one wave per group with the removed bits of column blocks l and l + 64 on lane
+l (both halves: suppressor and suppressed on either side of block 64, dead rows and the early exit past it), the offsets
+kernel 256 offsets per launch (one, two and three launches: 1 ... 70, 255 ... 257, 280 and 511 ... 513 groups); the final
+top-k runs one 1024-thread workgroup per image (Q = K R up to 80 000, D up to the limit 1024).  The sizes past 2049
+candidates and 70 groups are those of tests/test_gpu_box_nms_limits.py."""
 
 BN = "tests/test_gpu_box_nms.py::"
+BL = "tests/test_gpu_box_nms_limits.py::"
 DD = "tests/test_gpu_detect_decode.py::"
 DT = "tests/test_gpu_detector.py::"
 NMS = "tspn_box_nms_f32"
@@ -25,7 +30,16 @@ def _row(kernel, inst, entry, when, tests, align="no alignment requirement"):
 NMS_TESTS = [BN + "test_one_group_at_the_block_edges", BN + "test_three_unequal_groups_with_an_empty_one",
              BN + "test_all_none_and_exact_threshold", BN + "test_post_topk_below_and_above_the_survivors",
              BN + "test_invalid_rows_inside_and_outside_the_topk_and_min_size", BN + "test_nan_and_infinite_scores_and_boxes",
-             BN + "test_the_result_does_not_depend_on_the_scratch", DT + "test_compositions_equal_the_restatement"]
+             BN + "test_the_result_does_not_depend_on_the_scratch", DT + "test_compositions_equal_the_restatement",
+             BL + "test_random_grids_past_4096_selected", BL + "test_dead_rows_past_4096_selected",
+             BL + "test_lower_half_suppresses_upper_half", BL + "test_upper_half_suppresses_upper_half",
+             BL + "test_a_dead_row_past_4096_suppresses_nobody", BL + "test_early_exit_deep_in_the_list",
+             BL + "test_survivors_on_both_sides_of_the_half_boundary", BL + "test_unequal_groups_under_one_capacity",
+             BL + "test_group_counts_on_the_offset_chunk_edges", BL + "test_rpn_proposals_where_6000_cuts",
+             BL + "test_box_detections_with_280_class_groups"]
+SELECT_ONLY_TESTS = [BN + "test_the_selection_alone", BL + "test_selection_alone_at_the_big_capacity",
+                     BL + "test_selection_alone_with_nans_above_65536",
+                     BL + "test_selection_alone_three_groups_and_a_prefix"]
 
 VARIANTS = [
     # ------------------------------------------------------------------------------------ detect/tspn_detect.hip
@@ -33,23 +47,24 @@ VARIANTS = [
          "B > 0 and M > 0; one thread per (image, candidate): the anchor of the candidate's flat index, apply_deltas with "
          "weights 1, the clip, the validity byte",
          [DD + "test_rpn_decode_is_within_the_derived_bound", DD + "test_rpn_decode_exact_cases",
-          DT + "test_compositions_equal_the_restatement"],
+          DT + "test_compositions_equal_the_restatement", BL + "test_rpn_proposals_where_6000_cuts"],
          align="out_boxes 16-byte aligned (written as float4); every other operand at its natural alignment"),
     _row("box_head_decode_f32_kernel", None, "tspn_box_head_decode_f32",
          "B > 0 and R > 0; one thread per (image, proposal): softmax over K + 1 logits, K class boxes, class-major stores",
          [DD + "test_box_head_decode_is_within_the_derived_bounds", DD + "test_box_head_decode_exact_cases",
-          DT + "test_compositions_equal_the_restatement"],
+          DT + "test_compositions_equal_the_restatement", BL + "test_box_detections_with_280_class_groups"],
          align="proposals and out_boxes 16-byte aligned (float4 rows); every other operand at its natural alignment"),
     _row("box_nms_offsets_kernel", None, NMS,
          "G > 0; ceil((G + 1) / 256) launches: the host group offsets, 256 per launch by value, into the scratch",
-         NMS_TESTS + [BN + "test_the_selection_alone"], align="scratch 16-byte aligned"),
+         NMS_TESTS + SELECT_ONLY_TESTS, align="scratch 16-byte aligned"),
     _row("box_nms_select_kernel", "false", NMS,
          "G > 0 and boxes != NULL; one workgroup per group: tspn::select_topk_sorted at capacity 8192, then the sorted flat "
          "indices (-1: invalid or small), the sorted boxes and the count into the scratch; out_keep zeroed",
          NMS_TESTS, align="boxes 16-byte aligned (float4 rows)"),
     _row("box_nms_select_kernel", "true", NMS,
          "G > 0 and boxes == NULL: the selection is the result (out_index, out_count)",
-         [BN + "test_the_selection_alone", DT + "test_compositions_equal_the_restatement"],
+         SELECT_ONLY_TESTS + [DT + "test_compositions_equal_the_restatement",
+                              BL + "test_group_counts_on_the_offset_chunk_edges", BL + "test_rpn_proposals_where_6000_cuts"],
          align="out_index and out_count 8-byte aligned"),
     _row("box_nms_mask_kernel", None, NMS,
          "boxes != NULL and the largest group is not empty; G * nb * nb workgroups of one wave, nb = ceil(min(pre_topk, "
@@ -61,6 +76,7 @@ VARIANTS = [
          NMS_TESTS, align="out_index and out_count 8-byte aligned"),
     _row("detections_topk_kernel", None, "tspn_detections_topk_f32",
          "B > 0; one workgroup per image: counts the kept candidates, tspn::select_topk_sorted over i = r K + c, gathers",
-         [DT + "test_compositions_equal_the_restatement", DT + "test_detections_topk_ties_and_counts"],
+         [DT + "test_compositions_equal_the_restatement", DT + "test_detections_topk_ties_and_counts",
+          BL + "test_box_detections_with_280_class_groups", BL + "test_detections_topk_at_the_box_heads_size"],
          align="boxes and out_boxes 16-byte aligned"),
 ]

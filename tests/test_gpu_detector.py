@@ -38,6 +38,8 @@ def test_compositions_equal_the_restatement(tspn, device, pre, post):
     logits.reshape(-1)[rng.integers(0, logits.size, 5)] = np.inf        # first in the selection, dropped after it
     sizes = np.array([[100.0, 90.0], [144.0, 112.0]], np.float32)
     d = [dev(x, device) for x in (logits, deltas, cell, sizes)]
+    # HWA = 945, so M is 945 in the (6000, 1000) row too: the selection that does cut at 6000, and the NMS of 6000
+    # candidates, are tests/test_gpu_box_nms_limits.py::test_rpn_proposals_where_6000_cuts
     M = min(pre, HWA)
     cand, _, _ = ops.box_nms(None, d[0].reshape(-1), range(0, (B + 1) * HWA, HWA), M, 0.0, M)
     assert np.array_equal(cand.cpu().numpy(), ref.rpn_proposals_select(logits, pre))
