@@ -1177,6 +1177,52 @@ int tspn_detections_topk_f32(const float* scores, const float* boxes, const uint
                              int64_t D, float* out_boxes, float* out_scores, int64_t* out_classes, int64_t* out_count,
                              void* stream);
 
+/* ---- tracklet linking: per-frame detections -> tracks -> dense tracklet boxes (csrc/link/tspn_link.hip) -----------
+ * Build-defined (DESIGN.md 2 "tracklet linking"): a deterministic IoU tracker with constant-velocity prediction, exact
+ * against the numpy restatement.  Operands as tspn_detections_topk_f32 leaves them, F frames of D detection rows:
+ * boxes fp32 [F, D, 4] (16-byte aligned), scores fp32 [F, D], classes int64 [F, D], count int64 [F] on the device.
+ * video_off int64 [V + 1] lives in HOST memory and is read before the call returns: video v is the frames
+ * [video_off[v], video_off[v + 1]), ascending from 0 to F; a video may be empty.  Frame numbers in the outputs count
+ * from the video's first frame.  No entry synchronises, allocates or clears memory.
+ *
+ * tspn_link_detections_f32: one persistent workgroup per video.  At frame t a detection d < count[t] whose four
+ *   coordinates and score are finite and whose score >= min_score is a candidate.  A track (cls, first, t_last, t_prev,
+ *   hits, the boxes at t_last and t_prev, a float64 score sum) is confirmed when hits >= min_hits; it is live at t if
+ *   confirmed and t - t_last <= max_age, or tentative and t - t_last == 1.  Its predicted box is, for hits >= 2,
+ *   last + (last - prev) / float(t_last - t_prev) * float(t - t_last) per coordinate in fp32, else last.  A live track
+ *   and a candidate (of the track's class if class_aware) form an edge iff inter / (a + b - inter) >= iou_thresh in
+ *   fp32; the edges are taken greedily in the order (IoU descending, track id ascending, d ascending), a track and a
+ *   detection once.  A matched track moves last to prev, takes the detection and counts a hit.  The unmatched
+ *   candidates, in ascending d, start tracks with the video's next id while fewer than max_live tracks are live and
+ *   fewer than max_tracks ids are used; the others stay unlinked and are counted in dropped[v].
+ *   Outputs, every element written: track_of_det int32 [F, D] (the video-local id, -1: none); n_tracks, dropped int64
+ *   [V]; tables [V, max_tracks]: trk_first, trk_last, trk_hits int32, trk_cls int64, trk_score fp32 = fp32(score sum /
+ *   hits); past n_tracks they hold -1, -1, 0, -1, 0.
+ *   Limits: 1 <= D <= 1024, 1 <= max_live <= 4096, max_tracks < 2^24, V max_tracks < 2^31, F < 2^21, 0 < iou_thresh <= 1.
+ *
+ * tspn_link_fill_f32: dense boxes of R selected tracks (sel_video, sel_track int64 [R] on the device; a pair outside
+ *   the tables gives an absent row; a repeated pair gives equal rows).  out_boxes fp32 [R, Fmax, 4] and out_state uint8
+ *   [R, Fmax], Fmax the longest video: state 1 and the detection's box where the track was detected; inside
+ *   [first, last] otherwise state 2 and a + (b - a) * (float(t - ta) / float(tb - ta)) from the neighbouring detected
+ *   frames ta < t < tb; state 0 and zeros elsewhere.
+ *
+ * scratch: at least tspn_link_scratch_bytes(V, max_live, max_tracks, R, Fmax, fill) bytes (fill == 0: the link pass,
+ *   which reads V and max_live; else the fill pass, which reads V, max_tracks, R and Fmax), 16-byte aligned
+ *   (TSPN_EWORKSPACE otherwise); it may hold anything on entry, nothing outside those bytes is touched, and every byte of
+ *   which a call reads it has written before.  The query returns 0 for what the entries refuse, for V == 0 and, for the
+ *   fill pass, R == 0. */
+size_t tspn_link_scratch_bytes(int64_t V, int64_t max_live, int64_t max_tracks, int64_t R, int64_t Fmax, int fill);
+int tspn_link_detections_f32(const float* boxes, const float* scores, const int64_t* classes, const int64_t* count,
+                             const int64_t* video_off, int64_t V, int64_t F, int64_t D, float iou_thresh, int64_t max_age,
+                             int64_t min_hits, float min_score, int class_aware, int64_t max_live, int64_t max_tracks,
+                             int32_t* track_of_det, int64_t* n_tracks, int64_t* dropped, int32_t* trk_first,
+                             int32_t* trk_last, int32_t* trk_hits, int64_t* trk_cls, float* trk_score, void* scratch,
+                             size_t scratch_bytes, void* stream);
+int tspn_link_fill_f32(const float* boxes, const int32_t* track_of_det, const int64_t* video_off, int64_t V, int64_t F,
+                       int64_t D, const int32_t* trk_first, const int32_t* trk_last, int64_t max_tracks,
+                       const int64_t* sel_video, const int64_t* sel_track, int64_t R, float* out_boxes, uint8_t* out_state,
+                       void* scratch, size_t scratch_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,5 +23,7 @@ from . import roi_head  # noqa: F401
 from .roi_head import Res5RoIHead, ResNetC4  # noqa: F401
 from . import detector  # noqa: F401
 from .detector import BoxPredictor, FasterRCNNC4, RPNHead  # noqa: F401
+from . import tracklets  # noqa: F401
+from .tracklets import Tracks, link_detections, segment_tracklets, video_tracklets  # noqa: F401
 
 __version__ = "0.1.0"

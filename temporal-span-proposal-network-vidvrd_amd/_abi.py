@@ -213,6 +213,12 @@ PROTOTYPES = {
     "tspn_box_nms_f32": (_int, [_vp] * 3 + [_i64, ctypes.POINTER(_i64), _i64, _i64, ctypes.c_float, _i64, ctypes.c_float]
                          + [_vp] * 4 + [_sz, _vp]),
     "tspn_detections_topk_f32": (_int, [_vp] * 3 + [_i64] * 4 + [_vp] * 5),
+    "tspn_link_scratch_bytes": (_sz, [_i64] * 5 + [_int]),
+    "tspn_link_detections_f32": (_int, [_vp] * 4 + [ctypes.POINTER(_i64)] + [_i64] * 3 + [ctypes.c_float, _i64, _i64,
+                                                                                        ctypes.c_float, _int, _i64, _i64]
+                                 + [_vp] * 9 + [_sz, _vp]),
+    "tspn_link_fill_f32": (_int, [_vp] * 2 + [ctypes.POINTER(_i64)] + [_i64] * 3 + [_vp] * 2 + [_i64] + [_vp] * 2 + [_i64]
+                           + [_vp] * 3 + [_sz, _vp]),
 }
 
 _lib = None

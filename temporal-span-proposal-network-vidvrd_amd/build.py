@@ -29,6 +29,7 @@ CSRC_SPANMATCH = os.path.join(CSRC, "spanmatch")   # span-bounded association ma
 CSRC_EVALOBJ = os.path.join(CSRC, "evalobj")   # object detection evaluation (its variant table: tests/evalobj_kernel_variants.py)
 CSRC_SPANCLS = os.path.join(CSRC, "spancls")   # span-pooled predicate training (its variant table: tests/spancls_kernel_variants.py)
 CSRC_DETECT = os.path.join(CSRC, "detect")   # RPN / box head decode, box NMS (its variant table: tests/detect_kernel_variants.py)
+CSRC_LINK = os.path.join(CSRC, "link")   # tracklet linking: detections -> tracks -> dense boxes (its variant table: tests/link_kernel_variants.py)
 LIB_NAME = "libtspn_mi355x.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 ARCH = "gfx950"
@@ -62,7 +63,8 @@ def sources():
                   glob.glob(os.path.join(CSRC_PAIRF16, "*.hip")) + glob.glob(os.path.join(CSRC_SPANSAMPLE, "*.hip")) +
                   glob.glob(os.path.join(CSRC_PAIRLABELS, "*.hip")) + glob.glob(os.path.join(CSRC_INPUTF16, "*.hip")) +
                   glob.glob(os.path.join(CSRC_SPANMATCH, "*.hip")) + glob.glob(os.path.join(CSRC_EVALOBJ, "*.hip")) +
-                  glob.glob(os.path.join(CSRC_SPANCLS, "*.hip")) + glob.glob(os.path.join(CSRC_DETECT, "*.hip")))
+                  glob.glob(os.path.join(CSRC_SPANCLS, "*.hip")) + glob.glob(os.path.join(CSRC_DETECT, "*.hip")) +
+                  glob.glob(os.path.join(CSRC_LINK, "*.hip")))
 
 
 def _headers():
@@ -73,6 +75,7 @@ def _headers():
         glob.glob(os.path.join(CSRC_PAIRLABELS, "*.h")) + glob.glob(os.path.join(CSRC_INPUTF16, "*.h")) + \
         glob.glob(os.path.join(CSRC_SPANMATCH, "*.h")) + glob.glob(os.path.join(CSRC_EVALOBJ, "*.h")) + \
         glob.glob(os.path.join(CSRC_SPANCLS, "*.h")) + glob.glob(os.path.join(CSRC_DETECT, "*.h")) + \
+        glob.glob(os.path.join(CSRC_LINK, "*.h")) + \
         glob.glob(os.path.join(ROOT, "include", "*.h")) + \
         [os.path.abspath(__file__)]
 

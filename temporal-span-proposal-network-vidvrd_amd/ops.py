@@ -29,6 +29,7 @@ __all__ = [
     "pack_conv2d", "pack_conv2d_frag", "conv2d_nhwc", "roi_align_nhwc", "pack_conv2d_frag_bf16", "conv2d_nhwc_bf16", "max_pool_nhwc", "pack_conv2d_frag_cin4", "conv2d_nhwc_cin4", "max_pool_nhwc_bf16", "pack_stem_bf16", "stem_conv_bf16", "stem_pool_bf16", "bottleneck_tail_bf16",
     "eval_traj_volume", "eval_viou", "eval_greedy_match", "evalobj_tiou", "evalobj_claim",
     "rpn_decode", "box_head_decode", "box_nms", "box_nms_workspace_bytes", "detections_topk", "rpn_proposals", "box_detections",
+    "link_detections", "link_fill",
     "status_words", "status_fault", "status_clear", "status_selftest",
 ]
 
@@ -2318,6 +2319,74 @@ def box_detections(cls_logits, deltas, proposals, proposal_count, image_sizes, s
     _, _, keep = box_nms(boxes.view(-1, 4), scores.view(-1), range(0, (B * K + 1) * R, R), R, nms_thresh, R, min_size=-1.0,
                          valid=valid.view(-1), want_keep=True, workspace=workspace)
     return detections_topk(scores, boxes, keep.view(B, K, R), detections_per_image)
+
+
+# ---- tracklet linking: detections -> tracks -> dense tracklet boxes (csrc/link/tspn_link.hip)
+def _link_operands(who, boxes, video_off):
+    if _dev(boxes, "boxes").dim() != 3 or boxes.shape[2] != 4:
+        raise ValueError(f"{who}: boxes must be fp32 [F, D, 4], got {tuple(boxes.shape)}")
+    F, D = boxes.shape[:2]
+    arr, V = _group_off(who, [0, F] if video_off is None else video_off)
+    return F, D, arr, V
+
+
+def link_detections(boxes, scores, classes, count, video_off=None, iou_thresh=0.3, max_age=30, min_hits=3, min_score=0.0,
+                    class_aware=True, max_live=1024, max_tracks=16384, workspace=None):
+    """The link pass (tspn_link_detections_f32) over the outputs of FasterRCNNC4.forward: boxes fp32 [F,D,4], scores fp32
+    [F,D], classes int64 [F,D], count int64 [F]; video_off V + 1 host frame offsets ascending from 0 to F (None: one
+    video).  A deterministic IoU tracker with constant-velocity prediction ("tracklet linking").  Returns
+    (track_of_det int32 [F,D], n_tracks int64 [V], dropped int64 [V], first, last, hits int32 [V,max_tracks], cls int64
+    [V,max_tracks], score fp32 [V,max_tracks]); frames count from the video's first.  No host synchronisation."""
+    who = "link_detections"
+    F, D, arr, V = _link_operands(who, boxes, video_off)
+    if tuple(_dev(scores, "scores").shape) != (F, D) or tuple(_dev(classes, "classes", torch.int64).shape) != (F, D) or \
+            tuple(_dev(count, "count", torch.int64).shape) != (F,):
+        raise ValueError(f"{who}: scores [{F}, {D}], classes int64 [{F}, {D}] and count int64 [{F}] expected, got "
+                         f"{tuple(scores.shape)}, {tuple(classes.shape)} and {tuple(count.shape)}")
+    max_live, max_tracks = int(max_live), int(max_tracks)
+    dev = boxes.device
+    l = _abi.lib()
+    tod = torch.empty((F, D), dtype=torch.int32, device=dev)
+    n_tracks = torch.empty((V,), dtype=torch.int64, device=dev)
+    dropped = torch.empty((V,), dtype=torch.int64, device=dev)
+    shape = (V, max(max_tracks, 0))
+    first, last, hits = (torch.empty(shape, dtype=torch.int32, device=dev) for _ in range(3))
+    cls = torch.empty(shape, dtype=torch.int64, device=dev)
+    score = torch.empty(shape, dtype=torch.float32, device=dev)
+    need = l.tspn_link_scratch_bytes(V, max_live, max_tracks, 0, 0, 0)
+    ws = _workspace(workspace, need, dev, who, sizes=True)
+    _abi.check(l.tspn_link_detections_f32(_p(boxes), _p(scores), _p(classes), _p(count), arr, V, F, D, float(iou_thresh),
+                                          int(max_age), int(min_hits), float(min_score), 1 if class_aware else 0, max_live,
+                                          max_tracks, _p(tod), _p(n_tracks), _p(dropped), _p(first), _p(last), _p(hits),
+                                          _p(cls), _p(score), _p(ws), ws.numel() * ws.element_size(), _stream()))
+    return tod, n_tracks, dropped, first, last, hits, cls, score
+
+
+def link_fill(boxes, track_of_det, first, last, sel_video, sel_track, video_off=None, workspace=None):
+    """The fill pass (tspn_link_fill_f32): dense boxes of the selected tracks (sel_video, sel_track int64 [R] on the
+    device) from the detections and the link pass's track_of_det and first / last tables.  Returns (track_boxes fp32
+    [R,Fmax,4], state uint8 [R,Fmax]: 0 absent, 1 detected, 2 interpolated), Fmax the longest video."""
+    who = "link_fill"
+    F, D, arr, V = _link_operands(who, boxes, video_off)
+    if tuple(_dev(track_of_det, "track_of_det", torch.int32).shape) != (F, D):
+        raise ValueError(f"{who}: track_of_det must be int32 [{F}, {D}]")
+    _dev(first, "first", torch.int32), _dev(last, "last", torch.int32)
+    if first.dim() != 2 or first.shape[0] != V or last.shape != first.shape:
+        raise ValueError(f"{who}: first and last must be int32 [{V}, max_tracks]")
+    _dev(sel_video, "sel_video", torch.int64), _dev(sel_track, "sel_track", torch.int64)
+    if sel_video.dim() != 1 or sel_track.shape != sel_video.shape:
+        raise ValueError(f"{who}: sel_video and sel_track must be int64 [R]")
+    R, max_tracks = sel_video.shape[0], first.shape[1]
+    Fmax = max([arr[v + 1] - arr[v] for v in range(V)] + [0])
+    dev = boxes.device
+    l = _abi.lib()
+    out = torch.empty((R, Fmax, 4), dtype=torch.float32, device=dev)
+    state = torch.empty((R, Fmax), dtype=torch.uint8, device=dev)
+    need = l.tspn_link_scratch_bytes(V, 1, max_tracks, R, Fmax, 1)
+    ws = _workspace(workspace, need, dev, who, sizes=True)
+    _abi.check(l.tspn_link_fill_f32(_p(boxes), _p(track_of_det), arr, V, F, D, _p(first), _p(last), max_tracks, _p(sel_video),
+                                    _p(sel_track), R, _p(out), _p(state), _p(ws), ws.numel() * ws.element_size(), _stream()))
+    return out, state
 
 
 # every public operator runs with the device of its operands made current (see _on_tensor_device)

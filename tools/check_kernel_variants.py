@@ -5,7 +5,7 @@ tests/pairlist_kernel_variants.py for csrc/pairlist/*.hip, tests/spanbf16_kernel
 tests/spanloss_kernel_variants.py for csrc/spanloss/*.hip, tests/spansample_kernel_variants.py for csrc/spansample/*.hip,
 tests/pairlabels_kernel_variants.py for csrc/pairlabels/*.hip, tests/spanmatch_kernel_variants.py for csrc/spanmatch/*.hip,
 tests/evalobj_kernel_variants.py for csrc/evalobj/*.hip, tests/spancls_kernel_variants.py for csrc/spancls/*.hip,
-tests/detect_kernel_variants.py for csrc/detect/*.hip).
+tests/detect_kernel_variants.py for csrc/detect/*.hip, tests/link_kernel_variants.py for csrc/link/*.hip).
 
     rocprofv3 --kernel-trace --stats -d OUT -o run -- python -m pytest FILE... -q -m gpu
     python tools/check_kernel_variants.py OUT/.../run_kernel_stats.csv FILE...   (or OUT/.../run_results.db)
@@ -27,6 +27,7 @@ import detect_kernel_variants  # noqa: E402
 import eval_kernel_variants  # noqa: E402
 import evalobj_kernel_variants  # noqa: E402
 import kernel_variants  # noqa: E402
+import link_kernel_variants  # noqa: E402
 import pairlabels_kernel_variants  # noqa: E402
 import pairlist_kernel_variants  # noqa: E402
 import relations_kernel_variants  # noqa: E402
@@ -147,7 +148,7 @@ def main(argv):
               + spanloss_kernel_variants.VARIANTS + spansample_kernel_variants.VARIANTS
               + pairlabels_kernel_variants.VARIANTS + spanmatch_kernel_variants.VARIANTS
               + evalobj_kernel_variants.VARIANTS + spancls_kernel_variants.VARIANTS
-              + detect_kernel_variants.VARIANTS):
+              + detect_kernel_variants.VARIANTS + link_kernel_variants.VARIANTS):
         if not any(node.partition("::")[0] in files for node in r["tests"]):
             continue
         checked += 1
